@@ -10,12 +10,16 @@ the timed region starts.  `value` = aligned frames / s over all GPUs (weak scali
     python bench.py --gpus N --steps 8 --warmup 2        (N > 1 without a launcher: re-executes itself as N ranks, one per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Protocol: `--reps` (5) repetitions, each = reset, keyframe frame, W untimed warm-up steps, then EXACTLY K timed steps bracketed by a
-barrier + device synchronisation on both sides (max over ranks); `value` is the median repetition, all of them are listed.  Prints ONE
-JSON line (rank 0) with `roofline` (level-0 residual + normal-equation kernel, timed with HIP events inside the timed regions),
-`parity` (duplicate lanes bit-identical; one lane of EVERY distinct stream against the CPU oracle over all timed steps -- the oracle is the
-checker here, after the timed regions), `extra_configs` (the headline workload in the EXACT numerics class, fused and as the reference's kernel
-sequence; BASELINE configs 1, 4 and 5) and `cpu_baseline` (the CPU oracle -- a scalar port of the reference algorithm -- on the host cores;
+Protocol: `--reps` repetitions (1; 5 with --full), each = reset, keyframe frame, W untimed warm-up steps, then EXACTLY K timed steps bracketed
+by a barrier + device synchronisation on both sides (max over ranks); `value` is the median repetition, all of them are listed.  Prints ONE
+JSON line (rank 0) with `roofline` (level-0 residual + normal-equation kernel, timed with HIP events inside the timed regions; with --graph 1
+only under --full, which times it in an extra eager pass) and `parity` (duplicate lanes bit-identical).  `--dump-outputs DIR` writes what the
+last timed step handed its caller (every lane's pose record, the fused keyframe maps of a seeded sample of lanes) as .npy files.
+
+A plain run does only that.  `--full` adds everything else, after the timed regions: the default 5 repetitions, one lane of EVERY distinct
+stream against the CPU oracle over all timed steps (the oracle is the checker here), the selection check of the FAST kernels, the PCIe-inclusive
+leg, `extra_configs` (the headline workload in the EXACT numerics class, fused and as the reference's kernel sequence; smaller lane counts;
+BASELINE configs 1, 4 and 5; KeyframeAlign) and `cpu_baseline` (the CPU oracle -- a scalar port of the reference algorithm -- on the host cores;
 baseline, not target).  Config 4 (ONE long sequence cut into chunks, strong-scaled over the ranks) runs through the C++ driver
 rgbid_dist_track_sequence (csrc/dist.cpp; command line: rgbid-slam_amd/bin/rgbid_track_sequence).
 """
@@ -39,12 +43,70 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md); measured float
 U3_BYTES_PER_FRAME = 275.6e6   # SURVEY.md section 8d: algorithmic bytes of one aligned 640x480 frame (3 levels, {10,5,3})
 
 
+def _sensor_noise(nd, nc, drop, seed, dropout=0.03):
+    """the draws synth.make_frame takes from frame `seed`'s CPU generator, in its order (depth noise, intensity noise, dropout mask), written into
+    one frame's host buffers; single-threaded (the comparison in numpy: a torch one could start an OpenMP team in every calling thread)"""
+    from rgbid import synth
+    g = torch.Generator(device="cpu").manual_seed(synth.SEED + 31 * seed)
+    torch.randn(nd.shape, generator=g, dtype=torch.float64, out=nd)
+    torch.randn(nc.shape, generator=g, dtype=torch.float64, out=nc)
+    np.less(torch.rand(drop.shape, generator=g, dtype=torch.float64).numpy(), dropout, out=drop.numpy())
+
+
+def _draw_noise(pool, seed, n_frames, rows, cols, device):
+    """one stream's sensor noise, drawn by the threads of `pool` into pinned host buffers: (depth noise, intensity noise, dropout mask, futures)"""
+    pin = torch.device(device).type == "cuda"
+    nd = torch.empty((n_frames, rows, cols), dtype=torch.float64, pin_memory=pin)
+    nc = torch.empty((n_frames, rows, cols, 3), dtype=torch.float64, pin_memory=pin)
+    drop = torch.empty((n_frames, rows, cols), dtype=torch.bool, pin_memory=pin)
+    return nd, nc, drop, [pool.submit(_sensor_noise, nd[k], nc[k], drop[k], seed * 1000 + k) for k in range(n_frames)]
+
+
+def make_sequence(n_frames, seed, K, rows, cols, device, noise, chunk=32):
+    """synth.make_sequence(n_frames, seed, K, rows, cols, device), value for value, in a fraction of its time: synth.render and the sensor model of
+    synth.make_frame are elementwise (plus table gathers), so `chunk` frames go through them at once (the ray directions are the same per-frame
+    matrix product); `noise` is the stream's _draw_noise, uploaded without blocking the host"""
+    from rgbid import synth
+    scene = synth.Scene(seed=seed, device=device)
+    Rs, ts = synth.camera_path(n_frames, seed=seed)
+    fx, fy, cx, cy = K
+    v, u = torch.meshgrid(torch.arange(rows, dtype=torch.float64, device=device), torch.arange(cols, dtype=torch.float64, device=device), indexing="ij")
+    dc = torch.stack([(u - cx) / fx, (v - cy) / fy, torch.ones_like(u)], dim=-1)
+    depths, rgbs = [], []
+    for a in range(0, n_frames, chunk):
+        ks = range(a, min(a + chunk, n_frames))
+        dw = torch.stack([dc @ torch.as_tensor(Rs[k], dtype=torch.float64, device=device).T for k in ks])
+        t = torch.stack([torch.as_tensor(ts[k], dtype=torch.float64, device=device) for k in ks])[:, None, None, :]
+        lam = torch.full_like(dw[..., 0], scene.z0)
+        for _ in range(40):
+            P = t + lam[..., None] * dw
+            lam = (scene.depth(P[..., 0], P[..., 1]) - t[..., 2]) / dw[..., 2]
+        P = t + lam[..., None] * dw
+        rgb = scene.albedo(P[..., 0], P[..., 1])
+        for k in ks:
+            noise[3][k].result()
+        nd, nc, drop = [x[ks.start:ks.stop].to(device, non_blocking=True) for x in noise[:3]]
+        depth = lam + (1.4e-3 * lam ** 2) * nd
+        rgb = rgb + 2.0 * nc
+        d_mm = torch.clamp(torch.round(depth * 1000.0), 0, 65535)
+        depths.append(torch.where(drop, torch.zeros_like(d_mm), d_mm).to(torch.int32))
+        rgbs.append(torch.clamp(torch.round(rgb), 0, 255).to(torch.uint8))
+    return {"depth": torch.cat(depths), "rgb": torch.cat(rgbs), "R_wc": Rs, "t_wc": ts, "K": K}
+
+
 def make_inputs(lanes, n_frames, rows, cols, K, device, n_unique=32):
     """[T, B] stacks of `n_unique` distinct synthetic streams (different scene seed, different camera path), dealt round-robin onto the
     lanes: lane l carries stream l % n_unique."""
+    from concurrent.futures import ThreadPoolExecutor
     from rgbid import synth
     n = min(lanes, n_unique)
-    seqs = [synth.make_sequence(n_frames, seed=synth.SEED + 17 * i, K=K, rows=rows, cols=cols, device=device) for i in range(n)]
+    seeds = [synth.SEED + 17 * i for i in range(n)]
+    seqs = []
+    with ThreadPoolExecutor(max(1, min(usable_cores(), 16))) as pool:
+        nxt = _draw_noise(pool, seeds[0], n_frames, rows, cols, device)
+        for i in range(n):      # the next stream's noise is drawn while this one renders
+            cur, nxt = nxt, (_draw_noise(pool, seeds[i + 1], n_frames, rows, cols, device) if i + 1 < n else None)
+            seqs.append(make_sequence(n_frames, seeds[i], K, rows, cols, device, cur))
     depth_u = torch.stack([s["depth"].to(torch.int16) for s in seqs], 1)   # [T, n, rows, cols]
     rgb_u = torch.stack([s["rgb"] for s in seqs], 1)
     idx = torch.arange(lanes, device=depth_u.device) % n
@@ -243,8 +305,9 @@ def oracle_check(depth, rgb, lanes_to_check, rows, cols, K, levels, iters, rec, 
 
 
 def run_config(ctx, dev, work_stream, rows, cols, levels, iters, B, Kst, W, reps, n_unique, graph, fused, keyframes, K, dist_env, check_streams=0,
-               fast_numerics=1, inputs=None, defer_maps=0):
-    """the timed protocol on one engine configuration; returns (result dict, inputs kept for the PCIe leg)"""
+               fast_numerics=1, inputs=None, defer_maps=0, roofline_pass=True):
+    """the timed protocol on one engine configuration; returns (result dict, inputs kept for the PCIe leg).  roofline_pass = 0: with graph = 1
+    the level-0 kernel is not timed (it would take an extra eager pass)"""
     from rgbid import engine as E
     T = 1 + W + Kst
     seqs, depth, rgb = inputs if inputs is not None else make_inputs(B, T, rows, cols, K, dev, n_unique)
@@ -308,7 +371,7 @@ def run_config(ctx, dev, work_stream, rows, cols, levels, iters, B, Kst, W, reps
             k_ms_tot += ms; k_n_tot += n
         times.append(el)
         recs.append(rec.copy())
-    if not profile_in_timed:
+    if not profile_in_timed and roofline_pass:
         # graph replay cannot be event-bracketed per kernel: time the same kernel in an extra eager pass over the same frames
         eng.reset()
         eng.step(depth[0], rgb[0])
@@ -324,6 +387,7 @@ def run_config(ctx, dev, work_stream, rows, cols, levels, iters, B, Kst, W, reps
     tracked = int(np.count_nonzero(rec["status"] & E.ST_TRACKED))
     avg_s = (k_ms_tot / max(k_n_tot, 1)) * 1e-3
     achieved = k_bytes / avg_s / 1e9 if k_n_tot else 0.0
+    profiled = profile_in_timed or roofline_pass
     n_streams = min(B, n_unique)
     # ---- parity of the benchmarked surface (after the timed regions) ----
     reps_identical = all(recs[i].tobytes() == recs[0].tobytes() for i in range(1, len(recs)))
@@ -353,7 +417,9 @@ def run_config(ctx, dev, work_stream, rows, cols, levels, iters, B, Kst, W, reps
         "launches_per_step": eng.launches_per_step(), "engine_hbm_bytes": eng.bytes(), "tracked": tracked, "expected": B * Kst,
         "keyframes_exported": int(np.count_nonzero(rec["status"] & E.ST_KF_EXPORTED)), "n_unique_streams": n_streams,
         "u1": {"achieved": achieved, "avg_launch_us": avg_s * 1e6, "launches_timed": k_n_tot, "bytes_per_launch": k_bytes,
-               "timed_in": "timed regions" if profile_in_timed else "separate eager pass"},
+               "timed_in": "timed regions" if profile_in_timed else "separate eager pass"} if profiled else
+              {"achieved": None, "avg_launch_us": None, "launches_timed": 0, "bytes_per_launch": None,
+               "timed_in": "not timed (hipGraph replay: --full times the kernel in a separate eager pass)"},
         "parity": parity,
     }
     keep = (seqs, depth, rgb, eng, rec, gathered)
@@ -404,6 +470,27 @@ def pcie_leg(ctx, dev, work, eng, depth, rgb, W, Kst, ref_rec=None):
         out["records_identical_to_resident_run"] = bool(rec_h.tobytes() == ref_rec.tobytes())
     del depth_h, rgb_h, bufs
     return out
+
+
+def dump_outputs(path, eng, step, rows, cols, prefix=""):
+    """--dump-outputs: what the timed path handed its caller in its last step `step` -- every lane's pose record (rgbid_pose_record, one
+    array per field, [lanes, ...]) and the fused keyframe maps (inverse depth, weight) of a fixed, seeded sample of lanes -- as float32 /
+    float64 .npy files (a few MB at the headline size, at most ~34 MB).  The keyframe map marks pixels without an inverse depth with NaN:
+    they are written as 0 (a valid inverse depth is > 0) and flagged in keyframe_valid (1 / 0), so every array is finite"""
+    os.makedirs(path, exist_ok=True)
+    save = lambda name, a: np.save(os.path.join(path, f"{prefix}{name}.npy"), a)
+    rec = eng.records(step, 1)[0]
+    for f in rec.dtype.names:
+        save(f"record_{f}", rec[f].astype(np.float32 if rec[f].dtype == np.float32 else np.float64))
+    n = int(max(1, min(4, rec.shape[0], 32e6 // (rows * cols * 12))))
+    lanes = np.sort(np.random.default_rng(0).choice(rec.shape[0], n, replace=False))
+    maps = [eng.keyframe_maps(int(l)) for l in lanes]
+    save("keyframe_lanes", lanes.astype(np.float64))
+    depthinv = np.stack([m[0] for m in maps])
+    valid = np.isfinite(depthinv)
+    save("keyframe_depthinv", np.where(valid, depthinv, np.float32(0)))
+    save("keyframe_valid", valid.astype(np.float32))
+    save("keyframe_weight", np.stack([m[1] for m in maps]))
 
 
 def extra_config1(ctx, dev, K):
@@ -646,11 +733,16 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--reps", type=int, default=5, help="timed repetitions of the K steps (value = median)")
+    ap.add_argument("--full", action="store_true", help="also run everything besides the headline figure, after the timed regions: the oracle check, "
+                    "the selection check, the PCIe-inclusive leg, extra_configs, cpu_baseline, the record gather cross-check (the options below "
+                    "that shape those legs apply to it); a plain run sets up, warms up, times the K steps and prints the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step computed (pose records of every lane, "
+                    "fused keyframe maps of a seeded sample of lanes) as DIR/<name>.npy")
+    ap.add_argument("--reps", type=int, default=None, help="timed repetitions of the K steps (value = median); default 1, 5 with --full")
     ap.add_argument("--lanes", type=int, default=0, help="independent RGB-D streams per GPU; 0 = 2 048 (126 GB of engine state at 640x480; per-lane cost 512 -> 2 048: -5 %), "
                     "reduced in steps of 256 if the engine + the resident input frames of W + K + 1 steps would not fit the device's free memory")
     ap.add_argument("--streams", type=int, default=32, help="distinct synthetic input streams dealt onto the lanes")
-    ap.add_argument("--check-streams", type=int, default=32, help="lanes (one per distinct stream) held to the CPU oracle over all timed steps, after the timed regions (default: every distinct stream)")
+    ap.add_argument("--check-streams", type=int, default=32, help="with --full: lanes (one per distinct stream) held to the CPU oracle over all timed steps, after the timed regions (default: every distinct stream)")
     ap.add_argument("--seq-frames", type=int, default=2500, help="frames of the ONE long sequence of extra config 4 (BASELINE config 4: fr3/long_office has ~2 500)")
     ap.add_argument("--seq-chunks-per-gpu", type=int, default=0, help="chunks (= engine lanes) per GPU of extra config 4; 0 = the rule of DESIGN section 6 / tools/shard_sweep.py: "
                                                                        "chunks of >= 10 frames (ATE within ~35 %% of the unsharded run), at most 128 lanes per GPU")
@@ -666,7 +758,7 @@ def main():
     ap.add_argument("--gather", default="rccl-cabi", choices=["rccl-cabi", "torch"], help="transport of the record all-gather at N > 1: the product's C-ABI helper over RCCL "
                     "(a failure of it ENDS the run with a non-zero exit code), or torch.distributed when asked for explicitly")
     ap.add_argument("--h2d", type=int, default=-1, help="also time the same steps with the frames streamed from pinned host memory (PCIe-inclusive rate at the headline lane count; never `value`); "
-                                                          "default: on for the single-GPU run (costs ~13 s: 31 GB of frames are copied to pinned host memory)")
+                                                          "with --full; default: on for the single-GPU run (costs ~13 s: 31 GB of frames are copied to pinned host memory)")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -727,31 +819,36 @@ def main():
                 sys.stderr.flush()
                 os._exit(3)
         flush_c_stdio()
-    res, keep = run_config(ctx, dev, work, rows, cols, args.levels, iters, B, Kst, W, max(1, args.reps), args.streams, args.graph, args.fused,
-                           args.keyframes, K, dist_env, check_streams=args.check_streams if rank == 0 else 0, fast_numerics=args.fast)
+    reps = args.reps if args.reps is not None else (5 if args.full else 1)
+    res, keep = run_config(ctx, dev, work, rows, cols, args.levels, iters, B, Kst, W, max(1, reps), args.streams, args.graph, args.fused,
+                           args.keyframes, K, dist_env, check_streams=args.check_streams if rank == 0 and args.full else 0, fast_numerics=args.fast,
+                           roofline_pass=args.full)
     seqs, depth, rgb, eng, rec, gathered = keep
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, W + Kst, rows, cols, prefix=f"rank{rank}_" if world > 1 else "")
     rccl_ranks = rccl_ranks_all = None
     gather_ok = None
     if use_dist:
         import torch.distributed as dist
         from rgbid import dist as D
-        # cross-check of the gathered records (outside the timed regions): every rank's block equals what torch.distributed gathers
-        packed = D.pack_engine_records(eng, 1 + W, Kst)
-        ctx.sync()
-        ref = torch.empty(world * packed.numel(), dtype=torch.uint8, device=dev)
-        dist.all_gather_into_tensor(ref, packed)
-        gather_ok = bool(torch.equal(ref, gathered))
+        if args.full:
+            # cross-check of the gathered records (outside the timed regions): every rank's block equals what torch.distributed gathers
+            packed = D.pack_engine_records(eng, 1 + W, Kst)
+            ctx.sync()
+            ref = torch.empty(world * packed.numel(), dtype=torch.uint8, device=dev)
+            dist.all_gather_into_tensor(ref, packed)
+            gather_ok = bool(torch.equal(ref, gathered))
         rccl_ranks = dist_env["comm"].world() if dist_env["comm"] is not None else dist.get_world_size()
         rr = torch.zeros(world, dtype=torch.int64, device=dev)
         dist.all_gather_into_tensor(rr, torch.tensor([rccl_ranks], dtype=torch.int64, device=dev))
         rccl_ranks_all = [int(v) for v in rr.cpu()]
 
     pcie = None
-    if args.h2d > 0 or (args.h2d < 0 and world == 1 and not args.no_extras):
+    if args.full and (args.h2d > 0 or (args.h2d < 0 and world == 1 and not args.no_extras)):
         # PCIe-inclusive leg at the headline lane count: the same timed steps with every frame uploaded from pinned host memory
         pcie = pcie_leg(ctx, dev, work, eng, depth, rgb, W, Kst, rec)
     selection = None
-    if rank == 0 and world == 1 and args.fast and args.check_streams > 0 and Kst >= 2:
+    if args.full and rank == 0 and world == 1 and args.fast and args.check_streams > 0 and Kst >= 2:
         try:
             selection = selection_check(ctx, dev, depth, rgb, rec[1], 1 + W + 1, min(8, B, res["n_unique_streams"]), rows, cols, K)
         except Exception as e_:
@@ -790,7 +887,7 @@ def main():
                              "note": "engine_*: what the (fused) engine actually has to move per aligned frame x frames/s per GPU -- the fraction of the HBM roofline "
                                      "a step draws; u3_equivalent_*: frames/s priced at SURVEY 8d's UNFUSED budget U3 (275.6 MB/frame), i.e. the rate an unfused "
                                      "implementation would need -- not traffic that happened"} if headline else None),
-            "roofline": {"bound": "hbm", "achieved": u1["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": u1["achieved"] / HBM_PEAK_GBS,
+            "roofline": {"bound": "hbm", "achieved": u1["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": u1["achieved"] / HBM_PEAK_GBS if u1["achieved"] is not None else None,
                          "traffic": traffic, "traffic_from": traffic_from,
                          "kernel": ("rgbid::k_build_system<ByLane<SysParams>, true, 0, 2, 1> (the level-0 Gauss-Newton iterations) and <..., 0, 2, 2> (the covariance pass: same kernel, fixed-nu weights; "
                                     "1 launch in 11): level-0 Gauss-Newton evaluation, FUSED -- warp of the current frame (gathers) + residual rows + "
@@ -816,7 +913,7 @@ def main():
     # sequence), BASELINE configs 1, 5 and 4, the mounted datasets.  Multi-GPU run: config 4 only (every rank takes part: it is strong-scaled).
     headline_shape = rows == 480 and cols == 640 and args.levels == 3
     extras = []
-    if world == 1 and rank == 0 and not args.no_extras and headline_shape:
+    if args.full and world == 1 and rank == 0 and not args.no_extras and headline_shape:
         inputs = (seqs, depth, rgb)
         for name, fu, fa in (("exact-fused: the headline workload with the gather / filter kernels in the EXACT numerics class (bit-exact pixel selection; the fused kernel k_build_system<..., 1, 0>)", 1, 0),
                              ("exact-unfused: the reference's kernel sequence (warp pair, sigma / nu on stored maps, normal equations k_build_system<..., 0, 0>) in the EXACT class", 0, 0)):
@@ -869,7 +966,7 @@ def main():
             except Exception as e:
                 extras.append({"config": f"lanes-{Bs}", "error": f"{type(e).__name__}: {e}"})
         del inputs
-    if rank == 0 and world == 1 and not args.no_extras and headline_shape:
+    if args.full and rank == 0 and world == 1 and not args.no_extras and headline_shape:
         del depth, rgb, keep, gathered
         torch.cuda.empty_cache()
         try:
@@ -892,7 +989,7 @@ def main():
                            "u1_launches_timed": r5["u1"]["launches_timed"], "engine_hbm_bytes": r5["engine_hbm_bytes"]})
         except Exception as e:
             extras.append({"config": "5", "error": f"{type(e).__name__}: {e}"})
-    if not args.no_extras and headline_shape and args.seq_frames > 0:
+    if args.full and not args.no_extras and headline_shape and args.seq_frames > 0:
         if world > 1:
             del depth, rgb, keep, gathered
             torch.cuda.empty_cache()
@@ -905,12 +1002,12 @@ def main():
                 sys.stderr.write(f"[bench] rank {rank}: extra config 4 failed ({type(e).__name__}: {e})\n"); sys.stderr.flush()
                 os._exit(4)
             extras.append({"config": "4", "error": f"{type(e).__name__}: {e}"})
-    if rank == 0 and world == 1 and not args.no_extras and headline_shape:
+    if args.full and rank == 0 and world == 1 and not args.no_extras and headline_shape:
         try:
             extras.append(extra_kfalign(ctx, dev, K))
         except Exception as e:
             extras.append({"config": "f-1 (KeyframeAlign batched)", "error": f"{type(e).__name__}: {e}"})
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         try:
             ds = dataset_configs(K)
             if ds is not None:
@@ -928,7 +1025,7 @@ def main():
                     "achieved": x["u1_achieved_gbs"], "frac": x["u1_frac_of_hbm_peak"], "avg_launch_us": x["u1_avg_launch_us"], "unit": "GB/s",
                     "from": "extra_configs `exact-unfused` (the headline workload run as the reference's kernel sequence; HIP events over its timed level-0 launches)"}
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(seqs[0], rows, cols, K)
         else:
             result["cpu_baseline"] = None

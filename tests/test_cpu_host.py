@@ -1,9 +1,11 @@
 """CPU tests of the host-side product code (librgbid_host.so): SE(3) helpers and the INI parser.
   * SE(3): product (Jacobi inverse-square-root polar factor) vs oracle (Newton polar iteration) vs scipy expm/logm --
     three independent implementations;
-  * settings: product parser vs the REFERENCE's own parser compiled from /root/reference/src/settings.cpp into
-    oracle/_ref (skipped if that build is absent) on a committed fixture that exercises every syntax rule."""
+  * settings: product parser vs the REFERENCE's own parser (its answers recorded under tests/golden/ by make_reference_fixtures.py;
+    also run live where oracle/_ref is built) on a committed fixture that exercises every syntax rule, on the configuration files
+    the reference ships and on seeded random files."""
 import ctypes
+import json
 import os
 
 import numpy as np
@@ -15,6 +17,7 @@ from rgbid import host
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INI = os.path.join(ROOT, "tests", "golden", "visodo_test.ini")
+REF_ANSWERS = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_settings_answers.json")))
 
 
 def skew(w):
@@ -142,77 +145,45 @@ def test_settings_known_answers():
     assert g("NOPE", "x") is None and g("VISODO", "missing") is None
 
 
-def test_settings_match_reference_parser():
+def _match_recorded_reference_answers(path, triples):
+    """the product's parser against the reference parser's answers recorded in tests/golden/reference_settings_answers.json
+    (tests/golden/make_reference_fixtures.py); where oracle/_ref is built, the recorded answers are held to the live parser too"""
     so = os.path.join(ROOT, "oracle", "_ref", "libref_settings.so")
-    if not os.path.exists(so):
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
-    ref = ctypes.CDLL(so)
-    for sec, key in QUERIES:
-        buf = ctypes.create_string_buffer(4096)
-        n = ref.ref_settings_get(INI.encode(), sec.encode(), key.encode(), buf, 4096)
-        want = None if n < 0 else buf.value.decode()
-        assert host.settings_get(INI, sec, key) == want, (sec, key, want)
+    ref = ctypes.CDLL(so) if os.path.exists(so) else None
+    for sec, key, want in triples:
+        if ref is not None:
+            buf = ctypes.create_string_buffer(8192)
+            n = ref.ref_settings_get(path.encode(), sec.encode(), key.encode(), buf, 8192)
+            assert (None if n < 0 else buf.value.decode()) == want, ("recorded answer differs from oracle/_ref", path, sec, key, want)
+        assert host.settings_get(path, sec, key) == want, (path, sec, key, want)
+    return sum(want is not None for _, _, want in triples)
+
+
+def test_settings_match_reference_parser():
+    triples = REF_ANSWERS["visodo_test"]
+    assert [(s, k) for s, k, _ in triples] == QUERIES
+    _match_recorded_reference_answers(INI, triples)
 
 
 def test_settings_match_reference_parser_on_shipped_config_files():
-    """Every (section, key) of the nine configuration / calibration files the reference ships (config_data/*.ini), read by the
-    reference's own parser (oracle/_ref, built from /root/reference/src/settings.cpp) and by the product's parser.  Runs only where
-    /root/reference exists (the authoring container); nothing is copied."""
-    import glob
-    import re
-    so = os.path.join(ROOT, "oracle", "_ref", "libref_settings.so")
-    files = sorted(glob.glob("/root/reference/config_data/*.ini"))
-    if not os.path.exists(so) or not files:
-        pytest.skip("needs /root/reference and oracle/_ref")
-    ref = ctypes.CDLL(so)
+    """Every (section, key) of the nine configuration / calibration files the reference ships (config_data/*.ini, stored under
+    tests/golden/reference_config_data), as read by the reference's own parser and by the product's parser."""
     n_keys = 0
-    for f in files:
-        text = open(f).read()
-        sections = set(m.strip() for m in re.findall(r"^\s*\[([^\]]*)\]", text, re.M)) | {"VISODO", "CALIBRATION"}
-        keys = set(m.strip() for m in re.findall(r"^\s*([A-Za-z_][A-Za-z0-9_]*)\s*=", text, re.M)) | {"fx", "kd", "dRc", "t_dc", "q0", "missing"}
-        for sec in sections:
-            for key in keys:
-                buf = ctypes.create_string_buffer(8192)
-                n = ref.ref_settings_get(f.encode(), sec.encode(), key.encode(), buf, 8192)
-                want = None if n < 0 else buf.value.decode()
-                assert host.settings_get(f, sec, key) == want, (f, sec, key, want)
-                n_keys += want is not None
+    assert len(REF_ANSWERS["config_data"]) == 9
+    for name, triples in REF_ANSWERS["config_data"].items():
+        n_keys += _match_recorded_reference_answers(os.path.join(ROOT, "tests", "golden", "reference_config_data", name), triples)
     assert n_keys > 60
 
 
 def test_settings_match_reference_parser_on_random_grammar(tmp_path):
     """The product's INI loader is written from the file grammar (host/settings.cpp), not from the reference's source: hold it to the
-    reference's own parser (oracle/_ref) on randomly generated files that mix every production -- headers with and without ']', repeated
-    headers, keys before any header, repeated keys, empty keys, empty values, continuation lines after accepted, refused and dropped
-    assignments, comments, blank and blank-padded lines."""
-    so = os.path.join(ROOT, "oracle", "_ref", "libref_settings.so")
-    if not os.path.exists(so):
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
-    ref = ctypes.CDLL(so)
-    rs = np.random.default_rng(20260929)
-    secs, keys = ["A", "B", "", "A B"], ["k", "x", "kd", "long key", ""]
-    pad = lambda: " " * int(rs.integers(0, 3)) + "\t" * int(rs.integers(0, 2))
+    reference's own parser on 40 seeded random files (recorded with their answers) that mix every production -- headers with and without
+    ']', repeated headers, keys before any header, repeated keys, empty keys, empty values, continuation lines after accepted, refused and
+    dropped assignments, comments, blank and blank-padded lines."""
     n_hits = 0
-    for case in range(40):
-        lines = []
-        for _ in range(int(rs.integers(5, 40))):
-            kind = int(rs.integers(0, 9))
-            s, k = secs[int(rs.integers(0, len(secs)))], keys[int(rs.integers(0, len(keys)))]
-            v = " ".join(str(int(q)) for q in rs.integers(0, 99, int(rs.integers(0, 4))))
-            if kind == 0: body = ""
-            elif kind == 1: body = ("#" if rs.random() < 0.5 else ";") + " note = 1"
-            elif kind == 2: body = "[" + pad() + s + pad() + ("]" if rs.random() < 0.8 else "") + (" trailing" if rs.random() < 0.2 else "")
-            elif kind in (3, 4, 5): body = k + pad() + "=" + pad() + v + ("= 7" if rs.random() < 0.1 else "")
-            elif kind == 6: body = "=" + v
-            else: body = v if v else "word"
-            lines.append(pad() + body + pad() + ("\r" if rs.random() < 0.1 else ""))
+    assert len(REF_ANSWERS["random_grammar"]) == 40
+    for case, c in enumerate(REF_ANSWERS["random_grammar"]):
         path = tmp_path / f"case{case}.ini"
-        path.write_text("\n".join(lines) + ("\n" if rs.random() < 0.5 else ""))
-        for s in secs + ["missing"]:
-            for k in keys + ["missing"]:
-                buf = ctypes.create_string_buffer(8192)
-                n = ref.ref_settings_get(str(path).encode(), s.encode(), k.encode(), buf, 8192)
-                want = None if n < 0 else buf.value.decode()
-                assert host.settings_get(str(path), s, k) == want, (case, s, k, want, lines)
-                n_hits += want is not None
+        path.write_text(c["text"])
+        n_hits += _match_recorded_reference_answers(str(path), c["answers"])
     assert n_hits > 100

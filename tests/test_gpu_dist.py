@@ -110,7 +110,8 @@ def test_bench_small_run_reports_every_section():
     """bench.py end to end on a small batch: the result line carries roofline, the engine's own bytes per frame, the oracle check of every
     distinct stream, the EXACT-class variants, configs 1 / 5 and config 4 through the C++ sequence driver"""
     import json
-    p = _run_bench(["--lanes", "8", "--streams", "4", "--steps", "3", "--warmup", "1", "--reps", "2", "--seq-frames", "61", "--seq-chunks-per-gpu", "4", "--no-cpu-baseline"])
+    p = _run_bench(["--full", "--lanes", "8", "--streams", "4", "--steps", "3", "--warmup", "1", "--reps", "2", "--seq-frames", "61", "--seq-chunks-per-gpu", "4",
+                    "--no-cpu-baseline"])
     assert p.returncode == 0, p.stderr[-2000:]
     r = json.loads(p.stdout.strip().splitlines()[-1])
     assert r["roofline"]["frac"] > 0 and r["roofline"]["bound"] == "hbm"
@@ -127,10 +128,50 @@ def test_bench_small_run_reports_every_section():
     assert c4["chunk_head_deviation_vs_unsharded"]["max_rot_rad"] < 5e-3 and c4["chunk_head_deviation_vs_unsharded"]["max_trans_m"] < 1e-2
 
 
+def test_bench_inputs_are_the_synthetic_sequences():
+    """bench.make_inputs renders several frames per launch: every lane's frames equal synth.make_sequence's of its stream, bit for bit, across
+    the render's chunk boundaries"""
+    import bench
+    K = (131.25, 131.25, 79.875, 59.875)
+    _, depth, rgb = bench.make_inputs(5, 70, 120, 160, K, torch.device("cuda"), n_unique=3)
+    for i in range(3):
+        ref = synth.make_sequence(70, seed=synth.SEED + 17 * i, K=K, rows=120, cols=160, device="cuda")
+        for lane in (i, i + 3):
+            if lane < 5:
+                assert torch.equal(depth[:, lane], ref["depth"].to(torch.int16)) and torch.equal(rgb[:, lane], ref["rgb"]), (i, lane)
+
+
+def test_bench_plain_run_times_only_the_headline_and_dumps_its_outputs(tmp_path):
+    """without --full the run times exactly K steps once and prints the headline line only (no oracle check, no extras, no CPU baseline);
+    --dump-outputs writes the last timed step's records and keyframe maps as float32 / float64 .npy, the same in two runs of one command"""
+    import json, os
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"out{i}"
+        p = _run_bench(["--lanes", "8", "--streams", "4", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)], timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        r = json.loads(p.stdout.strip().splitlines()[-1])
+        assert r["steps"] == 3 and r["warmup"] == 1 and r["repetitions"]["n"] == 1 and r["ms_per_step"] > 0 and r["value"] > 0
+        assert r["unit"] == "frames/s" and r["higher_is_better"] and r["dtype"] == "f32" and r["roofline"]["frac"] > 0
+        assert r["cpu_baseline"] is None and "extra_configs" not in r and "pcie_inclusive" not in r and "oracle_checked_lanes" not in r["parity"]
+        files = sorted(os.listdir(d))
+        arrs = {f: np.load(d / f) for f in files}
+        assert "record_R.npy" in files and "record_t.npy" in files and "keyframe_depthinv.npy" in files
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values()) and sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert all(np.isfinite(a).all() for a in arrs.values()), [f for f, a in arrs.items() if not np.isfinite(a).all()]
+        kv, kd = arrs["keyframe_valid.npy"], arrs["keyframe_depthinv.npy"]
+        assert set(np.unique(kv)) <= {0.0, 1.0} and 0 < kv.mean() < 1 and (kd[kv == 1] > 0).all() and (kd[kv == 0] == 0).all()
+        assert arrs["record_R.npy"].shape == (8, 3, 3) and arrs["record_status.npy"].shape == (8,) and arrs["keyframe_depthinv.npy"].shape == (4, 480, 640)
+        dumps.append(arrs)
+    assert dumps[0].keys() == dumps[1].keys()
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
+
+
 def test_bench_fails_loudly_when_the_cabi_communicator_fails():
     """the product's record exchange is the C-ABI RCCL helper: if it cannot come up the run ENDS non-zero instead of reporting a number measured
     through torch.distributed; asked for explicitly (--gather torch) that transport is allowed"""
-    args = ["--lanes", "4", "--streams", "2", "--steps", "1", "--warmup", "0", "--reps", "1", "--no-extras", "--no-cpu-baseline", "--check-streams", "0"]
+    args = ["--full", "--lanes", "4", "--streams", "2", "--steps", "1", "--warmup", "0", "--reps", "1", "--no-extras", "--no-cpu-baseline", "--check-streams", "0"]
     p = _run_bench(args, {"RGBID_FORCE_DIST": "1", "RGBID_BENCH_FORCE_COMM_FAILURE": "1"})
     assert p.returncode == 3 and "refusing to report" in p.stderr and "{" not in p.stdout, (p.returncode, p.stderr[-800:])
     p = _run_bench(args + ["--gather", "torch"], {"RGBID_FORCE_DIST": "1", "RGBID_BENCH_FORCE_COMM_FAILURE": "1"})

@@ -40,7 +40,7 @@ print(f"| 1. single 640x480 pair, U1 + 6x6 solve | {t1*1e3:.2f} ms ({u1/t1/1e9:.
 
 
 def bench(extra):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, capture_output=True, text=True)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + extra, capture_output=True, text=True)
     line = [l for l in out.stdout.split("\n") if l.startswith("{")][-1]
     return json.loads(line)
 

@@ -10,7 +10,7 @@ OUT=$ROOT/gpurun_out/profiles_$ROUND
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 LIGHT="--reps 1 --no-extras --check-streams 0 --no-cpu-baseline"     # what the profiled passes drop: repetitions, the extra configurations, the oracle check
-python $ROOT/bench.py ${EXTRA:-} > $OUT/bench.json 2> $OUT/bench.err
+python $ROOT/bench.py --full ${EXTRA:-} > $OUT/bench.json 2> $OUT/bench.err
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o trace -- python $ROOT/bench.py ${EXTRA:-} $LIGHT > $OUT/bench_under_rocprof.json 2>/dev/null
 timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT -o pmc_fetch -- python $ROOT/bench.py ${EXTRA:-} $LIGHT --steps 3 --warmup 1 > /dev/null 2>&1
 timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT -o pmc_write -- python $ROOT/bench.py ${EXTRA:-} $LIGHT --steps 3 --warmup 1 > /dev/null 2>&1
