@@ -160,6 +160,31 @@ class Engine:
             out.update(overlap_mask=mask, colors=colors, depthinv=iD, normals=nrm)
         return out
 
+    def keyframe_sources(self, pairs):
+        """(lane, seq) pairs -> (cloud sources, headers): rgbid.cloud.Source of each export's ring block on the device with the pose of its
+        header, and the header fields (read_keyframe without the images).  Raises unless the export is in the ring: seq < count,
+        seq >= count - keyframe_capacity and the slot's header carries that seq (the check of rgbid_engine_read_keyframe)."""
+        from . import cloud
+        hdr_p, blk_p, nbytes = C.c_void_p(), C.c_void_p(), C.c_size_t()
+        check(self.L.rgbid_engine_keyframes_dev(self._h, C.byref(hdr_p), C.byref(blk_p), C.byref(nbytes)))
+        cap, B = self.cfg.keyframe_capacity, self.cfg.lanes
+        counts = self.keyframe_counts()                       # synchronises: the ring below is complete
+        ring = (KeyframeHeader * (B * cap))()
+        check(self.L.rgbid_memcpy_d2h(self.ctx._h, C.cast(ring, C.c_void_p), hdr_p, C.c_size_t(C.sizeof(ring))))
+        sources, headers = [], []
+        for lane, seq in pairs:
+            lane, seq = int(lane), int(seq)
+            if not (0 <= lane < B and 0 <= seq < counts[lane] and seq >= counts[lane] - cap):
+                raise _lib.RgbidError(f"keyframe export (lane {lane}, seq {seq}) is not in the ring (exports {counts[lane] if 0 <= lane < B else '-'}, capacity {cap})")
+            slot = lane * cap + seq % cap
+            h = ring[slot]
+            if h.seq != seq or h.lane != lane:
+                raise _lib.RgbidError(f"keyframe export (lane {lane}, seq {seq}): ring slot holds seq {h.seq}")
+            R = np.array(h.R).reshape(3, 3); t = np.array(h.t)
+            sources.append(cloud.source(blk_p.value + slot * nbytes.value, R, t))
+            headers.append(dict(id=h.id, end_id=h.end_id, lane=h.lane, seq=h.seq, R=R, t=t))
+        return sources, headers
+
     def profile_begin(self, max_launches):
         check(self.L.rgbid_engine_profile_begin(self._h, int(max_launches)))
 

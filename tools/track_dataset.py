@@ -33,6 +33,9 @@ def main():
     ap.add_argument("--rows", type=int, default=480)
     ap.add_argument("--cols", type=int, default=640)
     ap.add_argument("--force-dist", action="store_true", help="initialise torch.distributed (RCCL) even with a single rank")
+    ap.add_argument("--cloud", default="", metavar="PATH", help="also write the coloured point cloud of the exported keyframes as binary PLY "
+                    "(the novel points, as the reference's viewer draws them); with several ranks each writes PATH with .rank<r> before the extension")
+    ap.add_argument("--cloud-all", action="store_true", help="with --cloud: every valid pixel of every keyframe instead of the novel ones")
     ap.add_argument("--K", type=float, nargs=4, default=[525.0, 525.0, 319.5, 239.5], help="fx fy cx cy (tools/evaluation.cpp:64-67)")
     args = ap.parse_args()
 
@@ -70,8 +73,20 @@ def main():
             comm = D.Comm(ctx, world, rank)          # the C-ABI RCCL helper (librgbid_dist.so); the id travels through torch's store
         except Exception as e:                       # transport problem: say so, gather through torch.distributed instead
             sys.stderr.write(f"[track_dataset] WARNING: C-ABI RCCL communicator failed ({e}); gathering through torch.distributed\n")
-    R, t, ranges = sequence.track_chunked(ctx, depth, rgb, args.chunks, tuple(args.K), comm=comm, use_graph=0)
+    if args.cloud:
+        R, t, ranges, pc = sequence.track_chunked(ctx, depth, rgb, args.chunks, tuple(args.K), comm=comm, use_graph=0,
+                                                  cloud="all" if args.cloud_all else "novel")
+    else:
+        R, t, ranges = sequence.track_chunked(ctx, depth, rgb, args.chunks, tuple(args.K), comm=comm, use_graph=0)
     el = time.perf_counter() - t0
+    if args.cloud:
+        from rgbid import cloud as CL
+        path = args.cloud
+        if world > 1:
+            root, ext = os.path.splitext(path)
+            path = f"{root}.rank{rank}{ext}"
+        CL.write_ply(path, pc.points)
+        print(f"rank {rank}: {len(pc)} points of {len(pc.keyframes)} keyframes -> {path}")
     if comm is not None:
         comm.close()
     if rank == 0:
