@@ -196,8 +196,9 @@ int rgbid_kfalign_create(rgbid_kfalign** out, rgbid_ctx* ctx, int rows, int cols
     const size_t n = (size_t)lattice_samples(pr, pc, KFA_NSAMPLES);
     if (n > a->res_cap) a->res_cap = n;
     // the partials buffer must hold the launch plan of EVERY pair count up to max_pairs: the plan of few pairs (<= 32) comes from a schedule-length
-    // model, so blocks per pair are not monotonic in the pair count
-    for (int b = 1; b <= max_pairs; b = (b < 64 || b == max_pairs) ? b + 1 : (2 * b < max_pairs ? 2 * b : max_pairs)) {   // 1 .. 64, powers of two, max_pairs
+    // model, so blocks per pair are not monotonic in the pair count.  Every count is visited: a sampled set (1 .. 64, powers of two)
+    // left counts such as 65 .. 127 refused
+    for (int b = 1; b <= max_pairs; ++b) {
       const int nb = system_blocks_per_lane(pr, pc, b);
       if (nb > a->nblk_cap) a->nblk_cap = nb;
     }

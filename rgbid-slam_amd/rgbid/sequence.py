@@ -10,7 +10,7 @@ from . import dist as D
 from . import engine as E
 
 
-def track_chunked(ctx, depth, rgb, n_chunks, K, group=None, comm=None, cloud=None, **cfg_kw):
+def track_chunked(ctx, depth, rgb, n_chunks, K, group=None, comm=None, cloud=None, optimise=None, loops=None, loop_options=None, **cfg_kw):
     """depth [T, rows, cols] 16-bit, rgb [T, rows, cols, 3] uint8 CUDA tensors of ONE sequence.
     Returns (R [T,3,3], t [T,3], ranges); the per-frame status / covariance are in track_chunked.last = (status, cov).
 
@@ -19,9 +19,21 @@ def track_chunked(ctx, depth, rgb, n_chunks, K, group=None, comm=None, cloud=Non
     export ring of keyframe_capacity = chunk length slots per lane -- a lane exports at most one keyframe per step, so no export is
     overwritten -- which costs 20 * rows * cols * chunk length bytes of device memory per lane (an allocation failure is raised).
     Each keyframe is placed with the composed trajectory's pose of the frame it was created at, so the cloud lines up with the
-    trajectory; the final, never-exported keyframe of each chunk has no points."""
+    trajectory; the final, never-exported keyframe of each chunk has no points.
+
+    optimise = "auto" | "multilevel" | "single" runs the pose-graph back-end once over the whole run (rgbid.posegraph.optimise_run, the
+    reference's final performOptimisation, keyframe_manager.cpp:229-243): SEQ_ODO from the records, SEQ_KF from the export headers, and with
+    loops = "auto" or [(kf_a, kf_b), ...] (export indices in frame order) LC_KF constraints from the dense verifier.  "auto" uses multilevel
+    when every keyframe-level component is anchored, else single level (a chunk's keyframe chain ends at its last export, so chunked runs
+    without seam-crossing loops run single level).  The returned trajectory (and the cloud) are then the optimised ones; what ran is in
+    track_chunked.last_optimise (mode, status, chi2, loops).  It needs the whole run on one rank.  loop_options: keyword arguments of
+    rgbid.posegraph.loop_constraints (radius, angle, gate, min_separation)."""
     if cloud not in (None, "novel", "all"):
         raise ValueError(f"cloud must be None, 'novel' or 'all', not {cloud!r}")
+    if optimise not in (None, "auto", "multilevel", "single"):
+        raise ValueError(f"optimise must be None, 'auto', 'multilevel' or 'single', not {optimise!r}")
+    if loops is not None and optimise is None:
+        raise ValueError("loops needs optimise")
     T, rows, cols = depth.shape
     ranges = D.chunk_ranges(T, n_chunks)
     distributed = torch.distributed.is_available() and torch.distributed.is_initialized()
@@ -31,7 +43,9 @@ def track_chunked(ctx, depth, rgb, n_chunks, K, group=None, comm=None, cloud=Non
     lanes = D.lanes_per_rank(n_chunks, world)          # ranks owning one chunk fewer pad with a lane that re-tracks their last chunk (never read)
     owned = mine + [mine[-1] if mine else 0] * (lanes - len(mine))
     L = max(b - a + 1 for a, b in ranges)
-    if cloud is not None:
+    if optimise is not None and world > 1:
+        raise ValueError("optimise needs the whole run on one rank (torch.distributed has several)")
+    if cloud is not None or optimise is not None:
         cfg_kw = dict(cfg_kw, keyframe_capacity=L)
     eng = E.Engine(ctx, E.default_config(rows=rows, cols=cols, lanes=lanes, K=K, record_capacity=L, **cfg_kw))
     # Lane-major staging of the whole run, built once and kept alive until the records are read: the engine consumes its inputs
@@ -53,6 +67,12 @@ def track_chunked(ctx, depth, rgb, n_chunks, K, group=None, comm=None, cloud=Non
         allrec = D.gather_records_torch(local, group) if distributed else local[None]
     R, t, st, cov = D.compose_trajectory(allrec, world, n_chunks, ranges)
     track_chunked.last = (st, cov)
+    if optimise is not None:
+        try:
+            R, t = _optimise(ctx, eng, mine, ranges, allrec[0], R, t, K, optimise, loops, loop_options or {}, L)
+        except Exception:
+            eng.close()
+            raise
     if cloud is None:
         eng.close()
         return R, t, ranges
@@ -62,3 +82,25 @@ def track_chunked(ctx, depth, rgb, n_chunks, K, group=None, comm=None, cloud=Non
     finally:
         eng.close()
     return R, t, ranges, pc
+
+
+def _optimise(ctx, eng, mine, ranges, rec, R, t, K, optimise, loops, loop_options, steps):
+    """the pose-graph pass of track_chunked: records and exports of the lanes of this (single) rank -> optimised R, t"""
+    from . import posegraph as PG
+    counts = eng.keyframe_counts()
+    chunk_records, first, headers, keyframes = [], [], [], []
+    for lane, c in enumerate(mine):
+        a, b = ranges[c]
+        chunk_records.append(rec[lane, :b - a + 1])
+        first.append(a)
+        assert counts[lane] <= steps, (lane, counts[lane], steps)   # at most one export per step: the ring holds them all
+        for s in range(int(counts[lane])):
+            h = eng.read_keyframe(lane, s, images=loops is not None)
+            headers.append((lane, h))
+            if loops is not None:
+                keyframes.append(dict(frame=a + int(h["id"]), depthinv=h["depthinv"], colors=h["colors"]))
+    keyframes.sort(key=lambda k: k["frame"])
+    Ro, to, info = PG.optimise_run(ctx, R, t, chunk_records, first, headers, keyframes, K, optimise, loops, **loop_options)
+    track_chunked.last_optimise = info
+    return Ro, to
+

@@ -36,6 +36,9 @@ def main():
     ap.add_argument("--cloud", default="", metavar="PATH", help="also write the coloured point cloud of the exported keyframes as binary PLY "
                     "(the novel points, as the reference's viewer draws them); with several ranks each writes PATH with .rank<r> before the extension")
     ap.add_argument("--cloud-all", action="store_true", help="with --cloud: every valid pixel of every keyframe instead of the novel ones")
+    ap.add_argument("--optimise", nargs="?", const="auto", default=None, choices=["auto", "multilevel", "single"],
+                    help="optimise the trajectory with the pose-graph back-end once over the run (single rank; DESIGN.md section 11)")
+    ap.add_argument("--loops", default=None, choices=["auto"], help="with --optimise: add loop constraints from the dense keyframe verifier")
     ap.add_argument("--K", type=float, nargs=4, default=[525.0, 525.0, 319.5, 239.5], help="fx fy cx cy (tools/evaluation.cpp:64-67)")
     args = ap.parse_args()
 
@@ -73,11 +76,18 @@ def main():
             comm = D.Comm(ctx, world, rank)          # the C-ABI RCCL helper (librgbid_dist.so); the id travels through torch's store
         except Exception as e:                       # transport problem: say so, gather through torch.distributed instead
             sys.stderr.write(f"[track_dataset] WARNING: C-ABI RCCL communicator failed ({e}); gathering through torch.distributed\n")
+    if args.loops and not args.optimise:
+        ap.error("--loops needs --optimise")
+    opt = dict(optimise=args.optimise, loops=args.loops) if args.optimise else {}
     if args.cloud:
         R, t, ranges, pc = sequence.track_chunked(ctx, depth, rgb, args.chunks, tuple(args.K), comm=comm, use_graph=0,
-                                                  cloud="all" if args.cloud_all else "novel")
+                                                  cloud="all" if args.cloud_all else "novel", **opt)
     else:
-        R, t, ranges = sequence.track_chunked(ctx, depth, rgb, args.chunks, tuple(args.K), comm=comm, use_graph=0)
+        R, t, ranges = sequence.track_chunked(ctx, depth, rgb, args.chunks, tuple(args.K), comm=comm, use_graph=0, **opt)
+    if args.optimise:
+        info = sequence.track_chunked.last_optimise
+        print(f"pose graph: {info['mode']}, status {info['status']}, chi2 {info['chi2'][0]:.4g} -> {info['chi2'][1]:.4g}, "
+              f"loops accepted {info['accepted']} of {len(info['loops'])}")
     el = time.perf_counter() - t0
     if args.cloud:
         from rgbid import cloud as CL
