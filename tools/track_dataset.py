@@ -36,11 +36,16 @@ def main():
     ap.add_argument("--cloud", default="", metavar="PATH", help="also write the coloured point cloud of the exported keyframes as binary PLY "
                     "(the novel points, as the reference's viewer draws them); with several ranks each writes PATH with .rank<r> before the extension")
     ap.add_argument("--cloud-all", action="store_true", help="with --cloud: every valid pixel of every keyframe instead of the novel ones")
+    ap.add_argument("--voxel", type=float, default=None, metavar="LEAF",
+                    help="with --cloud: write the voxel-grid filtered map (centroids of LEAF-metre cells, as the reference writes its map: "
+                    "0.01) instead of every point; with several ranks each rank filters its own points (voxels are not merged across ranks)")
     ap.add_argument("--optimise", nargs="?", const="auto", default=None, choices=["auto", "multilevel", "single"],
                     help="optimise the trajectory with the pose-graph back-end once over the run (single rank; DESIGN.md section 11)")
     ap.add_argument("--loops", default=None, choices=["auto"], help="with --optimise: add loop constraints from the dense keyframe verifier")
     ap.add_argument("--K", type=float, nargs=4, default=[525.0, 525.0, 319.5, 239.5], help="fx fy cx cy (tools/evaluation.cpp:64-67)")
     args = ap.parse_args()
+    if args.voxel is not None and not args.cloud:
+        ap.error("--voxel needs --cloud")
 
     world = int(os.environ.get("WORLD_SIZE", "1")); rank = int(os.environ.get("RANK", "0")); local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     assert torch.cuda.is_available(), "needs a HIP device (there is no CPU path)"
@@ -95,8 +100,14 @@ def main():
         if world > 1:
             root, ext = os.path.splitext(path)
             path = f"{root}.rank{rank}{ext}"
-        CL.write_ply(path, pc.points)
-        print(f"rank {rank}: {len(pc)} points of {len(pc.keyframes)} keyframes -> {path}")
+        if args.voxel is None:
+            CL.write_ply(path, pc.points)
+            print(f"rank {rank}: {len(pc)} points of {len(pc.keyframes)} keyframes -> {path}")
+        else:
+            from rgbid import voxel as VX
+            vox, plan = VX.voxel_grid(ctx, pc.points, args.voxel, return_plan=True)
+            CL.write_ply(path, vox)
+            print(f"rank {rank}: {len(pc)} points of {len(pc.keyframes)} keyframes -> {plan.voxels} voxels of {args.voxel:g} m -> {path}")
     if comm is not None:
         comm.close()
     if rank == 0:
