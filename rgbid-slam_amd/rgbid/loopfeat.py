@@ -1,0 +1,310 @@
+"""Appearance stage of loop closure on the device (binding of include/rgbid_loopfeat.h): binary features of keyframes,
+2-NN Hamming matching with the ratio test, the appearance proposal, and the 3-point RANSAC over 3-D correspondences that starts the dense
+verifier (LoopCloser::detectLoopClosures / computeRANSACTrafo3D, src/loop_closer.cpp:193-716).
+
+    lf = LoopFeat(ctx, rows, cols)
+    feats = lf.extract(grey [n, rows, cols] uint8, invdepth [n, rows, cols] float32, K)
+    pairs, scores = propose(lf, feats)                         # uses no pose
+    res = lf.ransac(feats, pairs, *lf.match(feats, pairs))     # qTc_ini, best iteration, inliers, mask per pair
+
+`appearance_loops` strings the stages together for rgbid.posegraph.optimise_run(loops="appearance")."""
+import ctypes as C
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check
+
+KP_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("response", "<f4"), ("direction", "<i4"), ("desc", "u1", (32,)), ("X", "<f8", (3,)),
+                     ("cov", "<f8", (6,))])
+assert KP_DTYPE.itemsize == 120
+MATCH_DTYPE = np.dtype([("query", "<i4"), ("train", "<i4"), ("distance", "<i4"), ("second", "<i4")])
+assert MATCH_DTYPE.itemsize == 16
+
+CELL, CELL_MAX, BORDER, DIRECTIONS, TESTS = 32, 64, 16, 32, 256
+MAX_KEYPOINTS, MAX_ITERS = 1536, 4096
+EXPORTS = ["rgbid_loopfeat_create", "rgbid_loopfeat_destroy", "rgbid_loopfeat_tables", "rgbid_loopfeat_layout", "rgbid_loopfeat_extract",
+           "rgbid_loopfeat_match", "rgbid_loopfeat_ransac", "rgbid_loopfeat_timing"]
+STAGES = ("response", "select", "describe", "match", "ransac")
+
+# the reference's settings (config_data/visodoRGBDconfig.ini, loop_closer.cpp)
+MATCH_RATIO = 0.75             # MATCH_SCORE_RATIO_THRESHOLD
+SCORE_THRESHOLD = 0.6          # NORMALISED_BOW_SCORE_THRESHOLD
+MIN_INLIERS = 10               # MIN_REQUIRED_INLIERS
+MIN_HULL_RATIO = 0.05
+MAHALANOBIS_TH = 4.11
+RANSAC_SEED = 0x34985739
+RANSAC_CONFIDENCE, RANSAC_INLIER_RATIO, RANSAC_MIN_POINTS = 0.99, 0.3, 3
+
+
+def num_iters(confidence=RANSAC_CONFIDENCE, inlier_ratio=RANSAC_INLIER_RATIO, points=RANSAC_MIN_POINTS):
+    """loop_closer.cpp:386 in float32, as its 1.f and std::pow(float, float) evaluate it: (int)(log(1 - conf) / log(1 - ratio^points) - 1) + 1.
+    168 for the reference's settings."""
+    f = np.float32
+    c, r = f(confidence), f(inlier_ratio)
+    v = np.log(f(1.0) - c) / np.log(f(1.0) - np.power(r, f(points), dtype=np.float32)) - f(1.0)
+    return int(f(v)) + 1
+
+
+def uniform_draws(iters, seed=RANSAC_SEED):
+    """3 * iters values of Sampler::rand_uniform01 (sampler.cpp:46-51) after prng.reset(seed): MT19937 seeded by init_genrand, as boost::mt19937
+    and numpy's RandomState(seed) both are; u = x / 2^32"""
+    rs = np.random.RandomState(int(seed))
+    return mt19937_words(rs, 3 * int(iters)).astype(np.float64) / (float(0xFFFFFFFF) + 1.0)
+
+
+def mt19937_words(rs, n):
+    """the next n raw 32-bit outputs of a numpy RandomState"""
+    return np.frombuffer(rs.bytes(4 * int(n)), dtype="<u4").copy()
+
+
+def tables():
+    """the library's host tables -> (pattern int8 [256, 4], rotated int8 [32, 256, 4], bounds float64 [16, 2])"""
+    L = _lib.lib()
+    pat = np.zeros((TESTS, 4), np.int8); rot = np.zeros((DIRECTIONS, TESTS, 4), np.int8); bnd = np.zeros((16, 2), np.float64)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    L.rgbid_loopfeat_tables.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    check(L.rgbid_loopfeat_tables(p(pat), p(rot), p(bnd)))
+    return pat, rot, bnd
+
+
+def layout(rows, cols, max_keypoints):
+    """(cells_x, cells_y, keypoints kept per cell) of include/rgbid_loopfeat.h; ValueError for the sizes the library refuses"""
+    rows, cols, max_keypoints = int(rows), int(cols), int(max_keypoints)
+    if rows < 2 * BORDER + 1 or cols < 2 * BORDER + 1 or rows > 8192 or cols > 8192:
+        raise ValueError(f"rows, cols must be {2 * BORDER + 1} .. 8192, got {rows} x {cols}")
+    cx, cy = (cols + CELL - 1) // CELL, (rows + CELL - 1) // CELL
+    if not cx * cy <= max_keypoints <= MAX_KEYPOINTS:
+        raise ValueError(f"max_keypoints must be {cx * cy} (one per cell) .. {MAX_KEYPOINTS}, got {max_keypoints}")
+    return cx, cy, min(max_keypoints // (cx * cy), CELL_MAX)
+
+
+class Features:
+    """records [n, max_keypoints, 120] uint8 and counts [n] int32 on the device"""
+
+    def __init__(self, kps, counts):
+        self.kps, self.counts = kps, counts
+
+    def __len__(self):
+        return int(self.kps.shape[0])
+
+    def numpy(self):
+        """-> (structured KP_DTYPE [n, max_keypoints], counts [n])"""
+        return self.kps.cpu().numpy().view(KP_DTYPE).reshape(self.kps.shape[0], self.kps.shape[1]), self.counts.cpu().numpy()
+
+
+class LoopFeat:
+    """Feature extractor, matcher and RANSAC for keyframes of rows x cols pixels, on the context's stream."""
+
+    def __init__(self, ctx, rows, cols, max_keypoints=1000):
+        self.ctx, self.rows, self.cols, self.max_keypoints = ctx, int(rows), int(cols), int(max_keypoints)
+        self.cells_x, self.cells_y, self.per_cell = layout(rows, cols, max_keypoints)
+        self.L = L = _lib.lib()
+        vp, ci = C.c_void_p, C.c_int
+        L.rgbid_loopfeat_create.argtypes = [vp, vp, ci, ci, ci]
+        L.rgbid_loopfeat_destroy.argtypes = [vp]
+        L.rgbid_loopfeat_extract.argtypes = [vp, vp, vp, ci, vp, vp, vp]
+        L.rgbid_loopfeat_match.argtypes = [vp, vp, vp, ci, vp, ci, C.c_float, vp, vp]
+        L.rgbid_loopfeat_ransac.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, ci, C.c_double, vp, vp, vp]
+        L.rgbid_loopfeat_timing.argtypes = [vp, ci, vp]
+        self._h = C.c_void_p()
+        check(L.rgbid_loopfeat_create(C.byref(self._h), ctx._h, self.rows, self.cols, self.max_keypoints))
+        ctx._dependents.add(self)
+        self.dev = f"cuda:{ctx.device}"
+
+    def close(self):
+        if self._h:
+            if self.ctx._h:
+                self.L.rgbid_loopfeat_destroy(self._h)
+            self._h = None
+            self.ctx._dependents.discard(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _dev(self, a, dtype):
+        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+        return t.to(device=self.dev, dtype=dtype).contiguous()
+
+    def timing(self, enable=True):
+        """record HIP events around the stages of the following calls; -> the device ms of the last ones {stage: ms}"""
+        ms = (C.c_float * 5)()
+        check(self.L.rgbid_loopfeat_timing(self._h, int(enable), ms))
+        return dict(zip(STAGES, ms[:]))
+
+    def extract(self, grey, invdepth, K):
+        """grey [n, rows, cols] uint8 and invdepth [n, rows, cols] float32 (numpy or tensors), K = (fx, fy, cx, cy) -> Features.  Synchronises."""
+        g, w = self._dev(grey, torch.uint8), self._dev(invdepth, torch.float32)
+        assert g.dim() == 3 and tuple(g.shape[1:]) == (self.rows, self.cols) and g.shape == w.shape, (g.shape, w.shape)
+        n = int(g.shape[0])
+        kps = torch.empty((n, self.max_keypoints, 120), dtype=torch.uint8, device=self.dev)
+        counts = torch.zeros((n,), dtype=torch.int32, device=self.dev)
+        Kc = (C.c_float * 4)(*[float(v) for v in K])
+        self.ctx.wait_torch_stream()
+        check(self.L.rgbid_loopfeat_extract(self._h, g.data_ptr() if n else None, w.data_ptr() if n else None, n, Kc,
+                                            kps.data_ptr() if n else None, counts.data_ptr() if n else None))
+        self.ctx.sync()
+        return Features(kps, counts)
+
+    def _pairs(self, pairs):
+        p = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
+        return p, self._dev(p, torch.int32)
+
+    def match(self, feats, pairs, ratio=MATCH_RATIO, lists=True):
+        """pairs [(query, candidate)] keyframe indices -> (matches [P, max_keypoints, 16] uint8 on the device (None without lists), counts [P]
+        int32 on the device).  Synchronises."""
+        p, pd = self._pairs(pairs)
+        P = len(p)
+        counts = torch.zeros((P,), dtype=torch.int32, device=self.dev)
+        m = torch.zeros((P, self.max_keypoints, 16), dtype=torch.uint8, device=self.dev) if lists else None
+        self.ctx.wait_torch_stream()
+        check(self.L.rgbid_loopfeat_match(self._h, feats.kps.data_ptr() if len(feats) else None, feats.counts.data_ptr() if len(feats) else None,
+                                          len(feats), pd.data_ptr() if P else None, P, C.c_float(float(ratio)),
+                                          m.data_ptr() if (lists and P) else None, counts.data_ptr() if P else None))
+        self.ctx.sync()
+        return m, counts
+
+    def ransac(self, feats, pairs, matches, match_counts, iters=None, seed=RANSAC_SEED, threshold=MAHALANOBIS_TH, u=None):
+        """-> dict(R [P, 3, 3], t [P, 3], best [P], inliers [P], mask [P, max_keypoints] uint8) as numpy arrays.  u: the 3 * iters uniform
+        draws (default: uniform_draws(iters, seed); iters default num_iters()).  Synchronises."""
+        p, pd = self._pairs(pairs)
+        P = len(p)
+        if u is None:
+            iters = num_iters() if iters is None else int(iters)
+            u = uniform_draws(iters, seed)
+        u = np.ascontiguousarray(u, np.float64)
+        iters = len(u) // 3
+        ud = self._dev(u, torch.float64)
+        pose = torch.zeros((P, 12), dtype=torch.float64, device=self.dev)
+        res = torch.zeros((P, 2), dtype=torch.int32, device=self.dev)
+        mask = torch.zeros((P, self.max_keypoints), dtype=torch.uint8, device=self.dev)
+        self.ctx.wait_torch_stream()
+        q = lambda t_: t_.data_ptr() if P else None
+        check(self.L.rgbid_loopfeat_ransac(self._h, feats.kps.data_ptr() if len(feats) else None, len(feats), q(pd), P,
+                                           matches.data_ptr() if (matches is not None and P) else None, q(match_counts), ud.data_ptr(), iters,
+                                           C.c_double(float(threshold)), q(pose), q(res), q(mask)))
+        self.ctx.sync()
+        po, r = pose.cpu().numpy(), res.cpu().numpy()
+        return dict(R=po[:, :9].reshape(-1, 3, 3).copy(), t=po[:, 9:].copy(), best=r[:, 0].copy(), inliers=r[:, 1].copy(), mask=mask.cpu().numpy())
+
+
+# ---- host side of the proposal and of the gates ----
+def all_pairs(n, min_separation=3):
+    """every (q, c) the proposal scores: c <= q - min_separation, and (q, q - 1) for the normalisation"""
+    out = []
+    for q in range(1, n):
+        out.append((q, q - 1))
+        out += [(q, c) for c in range(0, q - min_separation + 1)]
+    return out
+
+
+def select_candidates(n, counts, min_separation=3, score_threshold=SCORE_THRESHOLD, per_query=(2, 2)):
+    """loop_closer.cpp:203-271 with the match count as the appearance score: counts {(q, c): matches}.  For each keyframe q the candidates
+    c <= q - min_separation whose count / count(q, q - 1) exceeds the threshold (float32, as the reference divides); of those the
+    per_query[0] of largest separation, then the per_query[1] of best score (the later keyframe first on equal scores, as the reference's
+    multimap is walked from its end), without duplicates.  -> ([(q, c)], {(q, c): normalised score})"""
+    out, scores = [], {}
+    for q in range(1, n):
+        ref = np.float32(counts.get((q, q - 1), 0))
+        if not ref > 0:
+            continue
+        cands = []
+        for c in range(0, q - min_separation + 1):
+            s = np.float32(counts.get((q, c), 0)) / ref
+            if s > np.float32(score_threshold):
+                cands.append((c, float(s)))
+        pick = [c for c, _ in sorted(cands, key=lambda x: x[0])[:per_query[0]]]
+        for c, _ in sorted(cands, key=lambda x: (-x[1], -x[0]))[:per_query[1]]:
+            if c not in pick:
+                pick.append(c)
+        sc = dict(cands)
+        for c in pick:
+            out.append((q, c))
+            scores[(q, c)] = sc[c]
+    return out, scores
+
+
+def propose(lf, feats, min_separation=3, score_threshold=SCORE_THRESHOLD, per_query=(2, 2), ratio=MATCH_RATIO):
+    """Appearance proposal over the keyframes of `feats` (in order): one matching call over all (q, c) pairs, then select_candidates.
+    It uses no pose.  -> ([(q, c)], {(q, c): normalised score})"""
+    n = len(feats)
+    pairs = all_pairs(n, min_separation)
+    if not pairs:
+        return [], {}
+    _, mc = lf.match(feats, pairs, ratio, lists=False)
+    counts = dict(zip(pairs, [int(v) for v in mc.cpu().numpy()]))
+    return select_candidates(n, counts, min_separation, score_threshold, per_query)
+
+
+def hull_area(points):
+    """computeConvexHullArea (util_funcs.cpp:256-274) over an own monotone-chain hull: |sum (x_{i+1} - x_i) (y_{i+1} + y_i) / 2|"""
+    pts = sorted(set((float(x), float(y)) for x, y in points))
+    if len(pts) < 3:
+        return 0.0
+
+    def half(seq):
+        h = []
+        for p in seq:
+            while len(h) >= 2 and (h[-1][0] - h[-2][0]) * (p[1] - h[-2][1]) - (h[-1][1] - h[-2][1]) * (p[0] - h[-2][0]) <= 0:
+                h.pop()
+            h.append(p)
+        return h
+    lo, up = half(pts), half(pts[::-1])
+    ch = lo[:-1] + up[:-1]
+    area = 0.0
+    for i in range(len(ch)):
+        a, b = ch[i], ch[(i + 1) % len(ch)]
+        area += (b[0] - a[0]) * ((b[1] + a[1]) / 2.0)
+    return abs(area)
+
+
+def gate(kq, kc, matches, mask, rows, cols, min_inliers=MIN_INLIERS, min_hull=MIN_HULL_RATIO):
+    """loop_closer.cpp:463-479: enough inliers and the inlier pixels' hull covers min_hull of the image in both keyframes.
+    kq, kc: KP_DTYPE records of the two keyframes; matches: MATCH_DTYPE records; mask: 1 per inlier.  -> (ok, inliers, hull_q, hull_c)"""
+    sel = matches[np.asarray(mask[:len(matches)], bool)]
+    hq = hull_area(zip(kq["x"][sel["query"]], kq["y"][sel["query"]])) / float(rows * cols)
+    hc = hull_area(zip(kc["x"][sel["train"]], kc["y"][sel["train"]])) / float(rows * cols)
+    ok = len(sel) >= min_inliers and hq >= min_hull and hc >= min_hull
+    return bool(ok), int(len(sel)), hq, hc
+
+
+def appearance_loops(ctx, keyframes, K, grey=None, max_keypoints=1000, min_separation=3, score_threshold=SCORE_THRESHOLD, per_query=(2, 2),
+                     batch=64):
+    """features of all exported keyframes, `propose`, RANSAC and its gates.  keyframes: [dict(frame, depthinv, colors)] in export order.
+    -> (pairs [(q, c)] that passed, guesses [(R, t)] = qTc_ini of each, report [dict(query, candidate, score, matches, inliers, hull_query,
+    hull_candidate, ransac_ok)] over every proposed pair)"""
+    from .posegraph import grey_from_colors
+    if len(keyframes) < 2:
+        return [], [], []
+    rows, cols = keyframes[0]["depthinv"].shape
+    if grey is None:
+        grey = [grey_from_colors(k["colors"]) for k in keyframes]
+    lf = LoopFeat(ctx, rows, cols, max_keypoints)
+    try:
+        parts = [lf.extract(np.stack(grey[s:s + batch]), np.stack([k["depthinv"] for k in keyframes[s:s + batch]]), K)
+                 for s in range(0, len(keyframes), batch)]   # records do not depend on the batch
+        feats = Features(torch.cat([p.kps for p in parts]), torch.cat([p.counts for p in parts]))
+        pairs, scores = propose(lf, feats, min_separation, score_threshold, per_query)
+        if not pairs:
+            return [], [], []
+        m, mc = lf.match(feats, pairs)
+        res = lf.ransac(feats, pairs, m, mc)
+        kps, _ = feats.numpy()
+        mh, mch = m.cpu().numpy().view(MATCH_DTYPE).reshape(len(pairs), -1), mc.cpu().numpy()
+    finally:
+        lf.close()
+    good, guess, report = [], [], []
+    for k, (q, c) in enumerate(pairs):
+        mm = mh[k, :mch[k]]
+        ok, inl, hq, hc = gate(kps[q], kps[c], mm, res["mask"][k], rows, cols) if res["best"][k] >= 0 else (False, 0, 0.0, 0.0)
+        report.append(dict(query=q, candidate=c, score=scores[(q, c)], matches=int(mch[k]), inliers=inl, hull_query=hq, hull_candidate=hc,
+                           ransac_ok=ok))
+        if ok:
+            good.append((q, c))
+            guess.append((res["R"][k].copy(), res["t"][k].copy()))
+    return good, guess, report

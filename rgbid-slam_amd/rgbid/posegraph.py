@@ -206,7 +206,7 @@ def propose_loops(frames, R, t, radius=0.5, angle=0.5, min_separation=3, per_que
     return out
 
 
-def loop_constraints(ctx, keyframes, R, t, K, pairs=None, radius=0.5, angle=0.5, gate=(0.1, 0.1), min_separation=3, batch=64):
+def loop_constraints(ctx, keyframes, R, t, K, pairs=None, radius=0.5, angle=0.5, gate=(0.1, 0.1), min_separation=3, batch=64, guess=None):
     """LC_KF constraints from the dense verifier (KfAlign.align, KeyframeAlign::alignKeyframes) over candidate pairs of exported keyframes.
 
     keyframes: [dict(frame=global frame, depthinv=float32 [rows, cols], colors=uint8 [rows, cols, 3])] in export order; R, t: the current
@@ -219,6 +219,9 @@ def loop_constraints(ctx, keyframes, R, t, K, pairs=None, radius=0.5, angle=0.5,
     if pairs is None:
         pairs = propose_loops(frames, R, t, radius, angle, min_separation)
     pairs = [(int(q), int(c)) for q, c in pairs]
+    if guess is not None and len(guess) != len(pairs):
+        raise ValueError(f"guess: one (R, t) per pair, got {len(guess)} for {len(pairs)} pairs")
+    given = guess
     rows, report = [], []
     if not pairs:
         return edges(rows), report
@@ -228,7 +231,10 @@ def loop_constraints(ctx, keyframes, R, t, K, pairs=None, radius=0.5, angle=0.5,
     try:
         for s in range(0, len(pairs), batch):
             chunk = pairs[s:s + batch]
-            guess = [_relative(R, t, frames[q], frames[c]) for q, c in chunk]
+            if given is None:
+                guess = [_relative(R, t, frames[q], frames[c]) for q, c in chunk]
+            else:
+                guess = [(np.asarray(g[0], np.float64).reshape(3, 3), np.asarray(g[1], np.float64).reshape(3)) for g in given[s:s + batch]]
             Ra, ta, cov = al.align(np.stack([keyframes[q]["depthinv"] for q, _ in chunk]), np.stack([grey[q] for q, _ in chunk]),
                                    np.stack([keyframes[c]["depthinv"] for _, c in chunk]), np.stack([grey[c] for _, c in chunk]), K,
                                    np.stack([g[0] for g in guess]), np.stack([g[1] for g in guess]))
@@ -245,25 +251,39 @@ def loop_constraints(ctx, keyframes, R, t, K, pairs=None, radius=0.5, angle=0.5,
                     ok = ok and corr[0] <= gate[0] and corr[1] <= gate[1]
                 if ok:
                     rows.append((frames[q], frames[c], LC_KF, Ra[k], ta[k], cov[k]))
-                report.append(dict(query=q, candidate=c, accepted=ok, correction=corr))
+                report.append(dict(query=q, candidate=c, accepted=ok, correction=corr, **({} if given is None else dict(R=Ra[k].copy(), t=ta[k].copy(), guess=guess[k]))))
     finally:
         al.close()
     return edges(rows), report
 
 
 def optimise_run(ctx, R, t, chunk_records, first_frames, headers, keyframes, K, optimise="auto", loops=None, **loop_kw):
-    """graph_from_run + loop_constraints + one device optimisation: -> (R [F, 3, 3], t [F, 3], info dict(mode, status, chi2, loops))"""
+    """graph_from_run + loop_constraints + one device optimisation: -> (R [F, 3, 3], t [F, 3], info dict(mode, status, chi2, loops)).
+    loops: None, "auto" (candidates by distance on the trajectory), "appearance" (rgbid.loopfeat.appearance_loops: features, appearance
+    proposal and RANSAC, no pose involved; each report row of a verified pair then also holds score, matches, inliers and hull ratios, and
+    info["appearance"] lists every proposed pair) or a list of (kf_a, kf_b)."""
     if optimise not in ("auto", "multilevel", "single"):
         raise ValueError(f"optimise must be 'auto', 'multilevel' or 'single', not {optimise!r}")
     P, E = graph_from_run(R, t, chunk_records, first_frames, headers)
     report = []
     if loops is not None:
-        pairs = None if isinstance(loops, str) and loops == "auto" else list(loops)
-        if isinstance(loops, str) and loops != "auto":
-            raise ValueError(f"loops must be None, 'auto' or a list of (kf_a, kf_b), not {loops!r}")
-        lc, report = loop_constraints(ctx, keyframes, R, t, K, pairs, **loop_kw)
+        if isinstance(loops, str) and loops not in ("auto", "appearance"):
+            raise ValueError(f"loops must be None, 'auto', 'appearance' or a list of (kf_a, kf_b), not {loops!r}")
+        if isinstance(loops, str) and loops == "appearance":
+            from . import loopfeat
+            akw = {k: loop_kw.pop(k) for k in ("max_keypoints", "score_threshold", "per_query") if k in loop_kw}
+            pairs, guess, appearance = loopfeat.appearance_loops(ctx, keyframes, K, min_separation=loop_kw.get("min_separation", 3), **akw)
+            lc, report = loop_constraints(ctx, keyframes, R, t, K, pairs, guess=guess, **loop_kw)
+            by_pair = {(a["query"], a["candidate"]): a for a in appearance}
+            for row in report:
+                a = by_pair[(row["query"], row["candidate"])]
+                row.update({k: a[k] for k in ("score", "matches", "inliers", "hull_query", "hull_candidate")})
+        else:
+            pairs = None if isinstance(loops, str) else list(loops)
+            lc, report = loop_constraints(ctx, keyframes, R, t, K, pairs, **loop_kw)
         E = np.concatenate([E, lc])
     mode = choose_mode([(P, E)]) if optimise == "auto" else optimise
+    appearance = appearance if isinstance(loops, str) and loops == "appearance" else None
     pg = PoseGraph(ctx)
     try:
         out, status, chi2 = pg.optimise([(P, E)], multilevel=mode == "multilevel")
@@ -272,7 +292,7 @@ def optimise_run(ctx, R, t, chunk_records, first_frames, headers, keyframes, K, 
     Ro = out[0][:, :9].reshape(-1, 3, 3).copy()
     to = out[0][:, 9:].copy()
     return Ro, to, dict(mode=mode, status=int(status[0]), chi2=chi2[0].copy(), loops=report,
-                        accepted=sum(1 for r in report if r["accepted"]), edges=E)
+                        accepted=sum(1 for r in report if r["accepted"]), edges=E, **({} if appearance is None else dict(appearance=appearance)))
 
 
 # ---- synthetic graphs (tests, tools/posegraph_bench.py) ----

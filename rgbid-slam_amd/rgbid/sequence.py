@@ -23,7 +23,9 @@ def track_chunked(ctx, depth, rgb, n_chunks, K, group=None, comm=None, cloud=Non
 
     optimise = "auto" | "multilevel" | "single" runs the pose-graph back-end once over the whole run (rgbid.posegraph.optimise_run, the
     reference's final performOptimisation, keyframe_manager.cpp:229-243): SEQ_ODO from the records, SEQ_KF from the export headers, and with
-    loops = "auto" or [(kf_a, kf_b), ...] (export indices in frame order) LC_KF constraints from the dense verifier.  "auto" uses multilevel
+    loops = "auto", "appearance" or [(kf_a, kf_b), ...] (export indices in frame order) LC_KF constraints from the dense verifier; "auto"
+    proposes candidates by distance on the trajectory, "appearance" by features, Hamming matching and RANSAC without any pose
+    (rgbid.loopfeat).  optimise="auto" uses multilevel
     when every keyframe-level component is anchored, else single level (a chunk's keyframe chain ends at its last export, so chunked runs
     without seam-crossing loops run single level).  The returned trajectory (and the cloud) are then the optimised ones; what ran is in
     track_chunked.last_optimise (mode, status, chi2, loops).  It needs the whole run on one rank.  loop_options: keyword arguments of

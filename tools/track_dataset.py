@@ -41,7 +41,9 @@ def main():
                     "0.01) instead of every point; with several ranks each rank filters its own points (voxels are not merged across ranks)")
     ap.add_argument("--optimise", nargs="?", const="auto", default=None, choices=["auto", "multilevel", "single"],
                     help="optimise the trajectory with the pose-graph back-end once over the run (single rank; DESIGN.md section 11)")
-    ap.add_argument("--loops", default=None, choices=["auto"], help="with --optimise: add loop constraints from the dense keyframe verifier")
+    ap.add_argument("--loops", default=None, choices=["auto", "appearance"],
+                    help="with --optimise: add loop constraints from the dense keyframe verifier; auto: candidates by distance on the trajectory, "
+                         "appearance: by binary features, Hamming matching and RANSAC (DESIGN.md section 13)")
     ap.add_argument("--K", type=float, nargs=4, default=[525.0, 525.0, 319.5, 239.5], help="fx fy cx cy (tools/evaluation.cpp:64-67)")
     args = ap.parse_args()
     if args.voxel is not None and not args.cloud:
@@ -93,6 +95,9 @@ def main():
         info = sequence.track_chunked.last_optimise
         print(f"pose graph: {info['mode']}, status {info['status']}, chi2 {info['chi2'][0]:.4g} -> {info['chi2'][1]:.4g}, "
               f"loops accepted {info['accepted']} of {len(info['loops'])}")
+        for a in info.get("appearance", []):
+            print(f"  appearance pair {a['query']} <- {a['candidate']}: score {a['score']:.3f}, matches {a['matches']}, inliers {a['inliers']}, "
+                  f"hull {a['hull_query']:.3f} / {a['hull_candidate']:.3f}, ransac {'ok' if a['ransac_ok'] else 'refused'}")
     el = time.perf_counter() - t0
     if args.cloud:
         from rgbid import cloud as CL
