@@ -19,7 +19,7 @@ class PoseGraph {
   void setIterations(int level2, int level1, int single) { iters_[0] = level2; iters_[1] = level1; iters_[2] = single; }
   // poses: one vertex each, in the order given (the first is fixed, fix_last_flag_ = false); constraints: ini_id_ / end_id_ name pose ids
   void buildGraph(const std::vector<Pose>& poses, const std::vector<PoseConstraint>& constraints);
-  // false: the graph was refused (an unknown pose id, an unanchored component, too many separators) or a pivot was not positive
+  // false: the graph was refused (an unknown pose id, an unanchored component) or a pivot was not positive
   bool optimiseGraph();
   // poses of the graph take their optimised estimate; poses the tracker appended since buildGraph (ids not in the graph) are re-anchored on
   // the last pose of the graph: T_new = T_last_after * T_last_before^-1 * T  (:218-237)

@@ -14,9 +14,11 @@
  *
  * Any number of graphs of any sizes run in ONE call on the device, FP64 throughout, with one read-back at the end.  Each iteration
  * is a Schur split of H: the runs of vertices with only frame-order neighbour edges are eliminated by block-
- * tridiagonal LDL^T, the remaining free vertices (separators: keyframes, loop endpoints) form a dense reduced system factored by
- * block Cholesky, one workgroup per graph.  Results are bitwise reproducible and do not depend on the other graphs of the call nor on
- * a graph's position in it.
+ * tridiagonal LDL^T, the remaining free vertices (separators: keyframes, loop endpoints) form the reduced system, factored by block
+ * Cholesky.  Two solvers do that with the same roundings in the same order, hence the same bytes: the dense one (one workgroup per
+ * graph, at most RGBID_PG_MAX_SEPARATORS separators) and the envelope one (one wave per graph, only the blocks first(i) .. i of every
+ * block row in frame order, no cap); rgbid_pg_set_limits chooses.  Results are bitwise reproducible and do not depend on the other
+ * graphs of the call nor on a graph's position in it.
  */
 #ifndef RGBID_POSEGRAPH_H_
 #define RGBID_POSEGRAPH_H_
@@ -31,8 +33,9 @@ extern "C" {
 /* PoseConstraint::type_ (include/rgbid/visodo.h) */
 enum { RGBID_PG_SEQ_ODO = 0, RGBID_PG_SEQ_KF = 1, RGBID_PG_LC_KF = 2 };
 
-/* at most this many separators per graph and stage (the reduced system is dense: (6 * 256)^2 doubles = 18.9 MB); more -> RGBID_E_INVALID.
- * In the multilevel level-2 stage every keyframe is a separator: a graph of more than ~256 keyframes is refused, never solved partially. */
+/* the default limit of separators per graph and stage, and the most the dense solver takes (its reduced system is (6 * 256)^2 doubles =
+ * 18.9 MB, its right-hand side an LDS vector of this size); more -> RGBID_E_INVALID unless rgbid_pg_set_limits raised the limit, which
+ * hands such graphs to the envelope solver.  In the multilevel level-2 stage every keyframe is a separator.  A graph is never solved partially. */
 #define RGBID_PG_MAX_SEPARATORS 256
 
 /* one constraint from -> to (vertex ids local to its graph, 0 .. n_vertices - 1): measurement R (row-major) | t, covariance cov (row-major,
@@ -59,7 +62,7 @@ int rgbid_pg_destroy(rgbid_pg* p);
 /* Optimise n_graphs graphs.  poses (host, [V][12] = R row-major | t, in/out), edges (host).  multilevel: 1 = the reference's default
  * schedule, 0 = single level.  iters (NULL = {10, 5, 10}): level-2, level-1 and single-level iteration counts.
  * Refused with RGBID_E_INVALID before any launch: a bad range or vertex id, a self edge, an unknown type, a component of a stage's active
- * edges without a fixed vertex, more than RGBID_PG_MAX_SEPARATORS separators.
+ * edges without a fixed vertex, more separators than the limit (RGBID_PG_MAX_SEPARATORS unless rgbid_pg_set_limits changed it).
  * status (host, [n_graphs], may be NULL): RGBID_PG_OK, or RGBID_PG_NOT_PD when a factorisation met a non-positive pivot -- that graph then
  * stops and keeps the poses of its last completed iteration.  chi2 (host, [n_graphs][2], may be NULL): g2o's activeChi2, the sum of
  * e^T Omega e over the active edges of the first stage before its first iteration and over those of the last stage after its last one
@@ -67,12 +70,27 @@ int rgbid_pg_destroy(rgbid_pg* p);
 int rgbid_pg_optimise(rgbid_pg* p, int n_graphs, const rgbid_pg_graph* graphs, double* poses, const rgbid_pg_edge* edges, int multilevel,
                       const int* iters, int* status, double* chi2);
 
+/* max_separators: graphs with more separators in a stage are refused (default RGBID_PG_MAX_SEPARATORS; any value >= 1).
+ * envelope_from: a stage of a graph with at least this many separators is solved by the envelope factorisation, below it by the dense one
+ * (default RGBID_PG_MAX_SEPARATORS + 1, i.e. never under the default limit; 1 = always; values above that default are clamped to it: the
+ * dense solver never sees more than RGBID_PG_MAX_SEPARATORS).  Results do not depend on envelope_from.  A value < 1 -> RGBID_E_INVALID.
+ * The envelope storage (36 doubles per block, sum over the rows of i - first(i) + 1 blocks) comes from the solver's workspace; when that
+ * cannot be allocated rgbid_pg_optimise returns RGBID_E_NOMEM before any launch with the poses untouched, and the solver stays usable. */
+int rgbid_pg_set_limits(rgbid_pg* p, int max_separators, int envelope_from);
+
+/* Structure only, no device: the separators of one stage of one graph (stage 0 / 1: level 2 / level 1 of the multilevel schedule, 2: the
+ * single level) in frame order and the envelope the envelope solver lays out: sep_vertex[i] the vertex of separator i, first[i] the
+ * smallest separator index coupled to i by an edge or by a segment between the two (first[i] <= i).  A graph rgbid_pg_optimise would refuse ->
+ * RGBID_E_INVALID; so do more separators than capacity, with *n_separators set to their number.  sep_vertex and first may be NULL. */
+int rgbid_pg_envelope(int n_vertices, int n_edges, const rgbid_pg_edge* edges, int stage, int capacity, int* n_separators, int32_t* sep_vertex,
+                      int32_t* first);
+
 /* device times (ms, HIP events) of the last optimise with timing on: [0] linearise, [1] assemble, [2] segment elimination, [3] reduced
  * factor + solve, [4] back-substitution + update, [5] chi2, each summed over its launches; [6] the whole call on the device, from the first
  * upload to the last read-back; and the launch count.  Timing costs a little: off by default. */
 int rgbid_pg_set_timing(rgbid_pg* p, int on);
 int rgbid_pg_last_times(const rgbid_pg* p, double ms[7], int* launches);
-/* flops of the reduced factorisations and solves of the last optimise, and the bytes the linearise and segment kernels moved */
+/* flops of the reduced factorisations and solves of the last optimise (dense: n^3 / 3 + 2 n^2; envelope: those done inside the envelope), and the bytes the linearise and segment kernels moved */
 int rgbid_pg_last_work(const rgbid_pg* p, double* reduced_flops, double* linearise_bytes, double* segment_bytes);
 
 #ifdef __cplusplus

@@ -11,6 +11,9 @@
 //                    separator; the segment's Schur contribution on its bounding separators
 //   k_pg_reduced     one workgroup per graph: the dense reduced separator system (diagonal blocks, separator-separator edges, segment
 //                    contributions in a fixed order), block Cholesky 6 columns at a time, both substitutions -> separator updates
+//   k_pg_env_assemble / k_pg_env_factor   the same reduced system for the graphs of envelope_from separators and more (rgbid_pg_set_limits):
+//                    only the block envelope first(i) .. i of every block row is stored and factored, one wave per graph, in the dense
+//                    kernel's order of roundings (same bytes), the right-hand side in global memory: no cap on the separators
 //   k_pg_backsub     one thread per segment: the segment's updates, last vertex first
 //   k_pg_update      one thread per free vertex: T <- T exp(dx)
 // Every value is computed by one thread in an order fixed by the graph's own structure, so results are bitwise reproducible and a graph's
@@ -50,6 +53,12 @@ struct PgFree { int v, graph, inc0, ninc; };
 struct PgSeg { int graph, slot0, v0, m, slotA, slotB, pad0, pad1; };   // slotA / slotB: free slot of the bounding separator, -1: none
 struct PgGraphStage { int graph, ns, sep0, sse0, nsse, seg0, nseg, pad; long long mat; };
 struct PgSse { int lin, a, b, pad; };                          // an active edge between separators a (its i) and b (its j)
+// envelope path: block row i of a graph holds the blocks first .. i, 36 doubles each, from block `off` of the envelope storage
+struct PgEnvRow { long long off; int graph, i, first, slot, c0, nc; };
+// one contribution to a block row, in the dense kernel's order: 36 doubles at src of lin (flags & 1: of segs_out), transposed when flags & 2,
+// added to block (i, col); rsrc >= 0: 6 doubles of segs_out added to the row's right-hand side
+struct PgEnvC { long long src, rsrc; int col, flags; };
+struct PgEnvGraph { int graph, ns, row0, pad; };
 
 // ---- 6x6 helpers (row-major, one thread) ----
 __device__ __forceinline__ bool chol6(const double* A, double* L) {
@@ -362,6 +371,155 @@ __global__ void __launch_bounds__(PG_RT) k_pg_reduced(const PgGraphStage* __rest
   for (int q = tid; q < n; q += PG_RT) delta[(size_t)6 * slots[q / 6] + q % 6] = r[q];
 }
 
+// ---- the envelope solver ----
+// The reduced system of a keyframe chain is block tridiagonal plus a few loop rows.  Block row i stores only first(i) .. i, first(i) the
+// smallest separator coupled to i (a separator-separator edge or a segment between the two); Cholesky fill stays inside that envelope.
+// Every entry goes through the roundings of k_pg_reduced in the same order: the contributions are added in the same order, block (i, k)
+// loses one 6-term sum per block column J ascending (those the envelope leaves out are exact zeros there), then the pivot block's chol6
+// or the panel's triangular solve; the substitutions likewise.  So the two solvers return the same bytes.
+constexpr int PG_ET = 64;       // one wave per block row (assembly) and per graph (factorisation)
+
+__global__ void __launch_bounds__(PG_ET) k_pg_env_assemble(const PgEnvRow* __restrict__ rows, const PgEnvC* __restrict__ contrib, const double* __restrict__ lin,
+                                                            const double* __restrict__ D, const double* __restrict__ b, const double* __restrict__ segs_out,
+                                                            const int* __restrict__ failed, double* __restrict__ env, double* __restrict__ renv) {
+  RGBID_FP_STRICT
+  const PgEnvRow R = rows[blockIdx.x];
+  if (failed[R.graph]) return;
+  const int tid = threadIdx.x, w = R.i - R.first;          // w off-diagonal blocks, then the diagonal one
+  double* Lr = env + (size_t)36 * (size_t)R.off;
+  for (long long q = tid; q < 36ll * w; q += PG_ET) Lr[q] = 0.0;
+  __syncthreads();
+  if (tid < 36) {                                           // entry tid of every block of the row belongs to this lane alone
+    const int tt = (tid % 6) * 6 + tid / 6;
+    double v = D[(size_t)36 * R.slot + tid];
+    for (int k = 0; k < R.nc; ++k) {
+      const PgEnvC c = contrib[R.c0 + k];
+      const double* src = ((c.flags & 1) ? segs_out : lin) + c.src;
+      const double h = src[(c.flags & 2) ? tt : tid];
+      if (c.col == R.i) v += h;
+      else Lr[(size_t)36 * (c.col - R.first) + tid] += h;
+    }
+    Lr[(size_t)36 * w + tid] = v;
+  } else if (tid < 42) {
+    const int q = tid - 36;
+    double v = b[(size_t)6 * R.slot + q];
+    for (int k = 0; k < R.nc; ++k) {
+      const PgEnvC c = contrib[R.c0 + k];
+      if (c.rsrc >= 0) v += segs_out[c.rsrc + q];
+    }
+    renv[(size_t)6 * blockIdx.x + q] = v;
+  }
+}
+
+// One wave per graph, left-looking, row by row: L(i, k) = (M(i, k) - sum_J L(i, J) L(k, J)^T) L(k, k)^-T for k = first(i) .. i - 1, the pivot
+// block by chol6, then the row's forward substitution; the backward substitution column by column.  Lane e < 36 owns entry e of the
+// block at hand (lanes 36 .. 63 shadow lane 35 and store nothing).  Blocks and the right-hand side live in global memory; what one lane
+// wrote is read by another only after a barrier of the (one-wave) workgroup.
+__global__ void __launch_bounds__(PG_ET) k_pg_env_factor(const PgEnvGraph* __restrict__ eg, const PgEnvRow* __restrict__ rows, double* __restrict__ env,
+                                                          double* __restrict__ renv, int* __restrict__ failed, double* __restrict__ delta) {
+  RGBID_FP_STRICT
+  __shared__ double blk[36];
+  __shared__ double y[6];
+  __shared__ int bad;
+  const PgEnvGraph g = eg[blockIdx.x];
+  if (failed[g.graph]) return;
+  const PgEnvRow* R = rows + g.row0;
+  double* r = renv + (size_t)6 * g.row0;
+  const int tid = threadIdx.x, e = tid < 36 ? tid : 35, er = e / 6, ec = e % 6;
+  const bool own = tid < 36;
+  if (tid == 0) bad = 0;
+  __syncthreads();
+  for (int i = 0; i < g.ns; ++i) {
+    const PgEnvRow Ri = R[i];
+    const int fi = Ri.first;
+    double* Li = env + (size_t)36 * (size_t)Ri.off;
+    for (int k = fi; k <= i; ++k) {
+      const PgEnvRow Rk = R[k];
+      const int fk = Rk.first;
+      const double* Lk = env + (size_t)36 * (size_t)Rk.off;
+      double acc = Li[(size_t)36 * (k - fi) + e];
+      for (int J = fi > fk ? fi : fk; J < k; ++J) {
+        const double* a = Li + (size_t)36 * (J - fi) + 6 * er;
+        const double* c = Lk + (size_t)36 * (J - fk) + 6 * ec;
+        double s = 0.0;
+        for (int l = 0; l < 6; ++l) s += a[l] * c[l];
+        acc -= s;
+      }
+      if (k < i) {                                          // row er of the block times L(k, k)^-T
+        const double* Lkk = Lk + (size_t)36 * (k - fk);
+        for (int c = 0; c < 6; ++c) {
+          if (ec == c) acc = acc / Lkk[c * 6 + c];
+          const double xc = __shfl(acc, er * 6 + c, PG_ET);
+          if (ec > c) acc -= xc * Lkk[ec * 6 + c];
+        }
+        if (own) Li[(size_t)36 * (k - fi) + e] = acc;
+        __syncthreads();
+      } else {
+        if (own) blk[e] = acc;
+        __syncthreads();
+        if (tid == 0) {
+          double P[36], L[36];
+          for (int q = 0; q < 36; ++q) P[q] = blk[q];
+          if (!chol6(P, L)) bad = 1;
+          for (int q = 0; q < 36; ++q) blk[q] = L[q];
+        }
+        __syncthreads();
+        if (bad) { if (tid == 0) failed[g.graph] = 1; return; }
+        if (own) Li[(size_t)36 * (k - fi) + e] = blk[e];
+      }
+    }
+    // L y = r, row i
+    if (tid < 6) {
+      double v = r[(size_t)6 * i + tid];
+      for (int J = fi; J < i; ++J) {
+        const double* a = Li + (size_t)36 * (J - fi) + 6 * tid;
+        const double* yj = r + (size_t)6 * J;
+        double s = 0.0;
+        for (int l = 0; l < 6; ++l) s += a[l] * yj[l];
+        v -= s;
+      }
+      y[tid] = v;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      double z[6];
+      for (int k = 0; k < 6; ++k) {
+        double s = y[k];
+        for (int l = 0; l < k; ++l) s -= blk[k * 6 + l] * z[l];
+        z[k] = s / blk[k * 6 + k];
+      }
+      for (int k = 0; k < 6; ++k) r[(size_t)6 * i + k] = z[k];
+    }
+    __syncthreads();
+  }
+  // L^T x = y
+  for (int J = g.ns - 1; J >= 0; --J) {
+    const PgEnvRow Rj = R[J];
+    const int fj = Rj.first;
+    const double* Lj = env + (size_t)36 * (size_t)Rj.off;
+    if (tid == 0) {
+      const double* Ljj = Lj + (size_t)36 * (J - fj);
+      double z[6];
+      for (int k = 5; k >= 0; --k) {
+        double s = r[(size_t)6 * J + k];
+        for (int l = k + 1; l < 6; ++l) s -= Ljj[l * 6 + k] * z[l];
+        z[k] = s / Ljj[k * 6 + k];
+      }
+      for (int k = 0; k < 6; ++k) r[(size_t)6 * J + k] = z[k];
+    }
+    __syncthreads();
+    for (long long q = tid; q < 6ll * (J - fj); q += PG_ET) {
+      const int K = fj + (int)(q / 6), c = (int)(q % 6);
+      const double* a = Lj + (size_t)36 * (K - fj);
+      double s = 0.0;
+      for (int l = 0; l < 6; ++l) s += a[l * 6 + c] * r[(size_t)6 * J + l];
+      r[(size_t)6 * K + c] -= s;
+    }
+    __syncthreads();
+  }
+  for (long long q = tid; q < 6ll * g.ns; q += PG_ET) delta[(size_t)6 * R[q / 6].slot + q % 6] = r[q];
+}
+
 __global__ void __launch_bounds__(PG_T) k_pg_backsub(const PgSeg* __restrict__ segs, int n, const double* __restrict__ segv, const int* __restrict__ failed,
                                                       double* __restrict__ delta) {
   RGBID_FP_STRICT
@@ -454,6 +612,12 @@ struct Stage {
   std::vector<int> sep_slot, sep_idx;   // sep_idx: per free slot, its separator index in its graph (-1: segment vertex)
   std::vector<PgSse> sse;
   long long mat_doubles = 0;
+  // graphs of envelope_from separators and more: their block rows, contributions and storage
+  std::vector<PgEnvGraph> eg;
+  std::vector<PgEnvRow> erow;
+  std::vector<PgEnvC> ec;
+  long long env_blocks = 0;
+  double env_flops = 0;                 // of one factorisation and solve of every envelope graph
   int iters = 0;
 };
 
@@ -463,7 +627,8 @@ int find(std::vector<int>& p, int x) {
 }
 
 // level: 2 / 1 / 0 (all edges).  fixed (graph-local flags, in/out for the multilevel schedule) is extended by nothing here.
-int build_stage(Stage& st, int ng, const rgbid_pg_graph* graphs, const rgbid_pg_edge* edges, int level, const std::vector<std::vector<char>>& fixed) {
+int build_stage(Stage& st, int ng, const rgbid_pg_graph* graphs, const rgbid_pg_edge* edges, int level, const std::vector<std::vector<char>>& fixed,
+                int max_sep, int env_from) {
   for (int g = 0; g < ng; ++g) {
     const rgbid_pg_graph& G = graphs[g];
     const int nv = G.n_vertices;
@@ -513,7 +678,7 @@ int build_stage(Stage& st, int ng, const rgbid_pg_graph* graphs, const rgbid_pg_
       if (slot[v] >= 0 && sep[v]) { sidx[v] = gs.ns++; st.sep_slot.push_back(slot[v]); }
     st.sep_idx.resize(st.fr.size(), -1);
     for (int v = 0; v < nv; ++v) if (slot[v] >= 0) st.sep_idx[slot[v]] = sidx[v];
-    if (gs.ns > RGBID_PG_MAX_SEPARATORS) return RGBID_E_INVALID;
+    if (gs.ns > max_sep) return RGBID_E_INVALID;
     for (int v = 0; v < nv;) {
       if (slot[v] < 0 || sep[v]) { ++v; continue; }
       int w = v;
@@ -529,10 +694,89 @@ int build_stage(Stage& st, int ng, const rgbid_pg_graph* graphs, const rgbid_pg_
       if (sidx[e.from] >= 0 && sidx[e.to] >= 0) st.sse.push_back(PgSse{lin0 + (int)q, sidx[e.from], sidx[e.to], 0});
     }
     gs.nsse = (int)st.sse.size() - gs.sse0;
-    if (gs.ns > 0) {
+    if (gs.ns >= env_from) {
+      // the envelope: per block row the contributions in the dense kernel's order (separator-separator edges, then segments) and first(i)
+      std::vector<std::vector<PgEnvC>> rc(gs.ns);
+      std::vector<int> first(gs.ns);
+      std::iota(first.begin(), first.end(), 0);
+      for (int q = gs.sse0; q < gs.sse0 + gs.nsse; ++q) {
+        const PgSse& e = st.sse[q];
+        const int hi = std::max(e.a, e.b), lo = std::min(e.a, e.b);
+        rc[hi].push_back(PgEnvC{(long long)PG_LIN * e.lin + 36, -1, lo, e.a > e.b ? 0 : 2});
+        first[hi] = std::min(first[hi], lo);
+      }
+      for (int q = gs.seg0; q < gs.seg0 + gs.nseg; ++q) {
+        const PgSeg& sg = st.seg[q];
+        const long long o = (long long)PG_SEGS * q;
+        const int A = sg.slotA >= 0 ? st.sep_idx[sg.slotA] : -1, B = sg.slotB >= 0 ? st.sep_idx[sg.slotB] : -1;
+        if (A >= 0) rc[A].push_back(PgEnvC{o, o + 108, A, 1});
+        if (B >= 0) rc[B].push_back(PgEnvC{o + 72, o + 114, B, 1});
+        if (A >= 0 && B >= 0) { rc[B].push_back(PgEnvC{o + 36, -1, A, 1 | 2}); first[B] = std::min(first[B], A); }
+      }
+      st.eg.push_back(PgEnvGraph{g, gs.ns, (int)st.erow.size(), 0});
+      double products = 0, offdiag = 0;
+      for (int i = 0; i < gs.ns; ++i) {
+        st.erow.push_back(PgEnvRow{st.env_blocks, g, i, first[i], st.sep_slot[gs.sep0 + i], (int)st.ec.size(), (int)rc[i].size()});
+        st.ec.insert(st.ec.end(), rc[i].begin(), rc[i].end());
+        st.env_blocks += i - first[i] + 1;
+        offdiag += i - first[i];
+        for (int k = first[i]; k <= i; ++k) products += k - std::max(first[i], first[k]);
+      }
+      // per block product 36 (6 mul + 6 add + 1 sub), per panel block 6 rows (15 mul + 15 sub + 6 div), per pivot block chol6 (6 sqrt, 15 div,
+      // 35 mul + 35 sub), per off-diagonal block of both substitutions 36 mul + 36 add + 6 sub, per diagonal block 15 mul + 15 sub + 6 div
+      st.env_flops += 468.0 * products + 216.0 * offdiag + 91.0 * gs.ns + 2.0 * (78.0 * offdiag + 36.0 * gs.ns);
+    } else if (gs.ns > 0) {
       st.gst.push_back(gs);
       st.mat_doubles += 36ll * gs.ns * gs.ns;
     }
+  }
+  return RGBID_OK;
+}
+
+bool pg_edges_valid(const rgbid_pg_graph& G, const rgbid_pg_edge* edges) {
+  for (int k = 0; k < G.n_edges; ++k) {
+    const rgbid_pg_edge& e = edges[G.e0 + k];
+    if (e.from < 0 || e.to < 0 || e.from >= G.n_vertices || e.to >= G.n_vertices || e.from == e.to) return false;
+    if (e.type != RGBID_PG_SEQ_ODO && e.type != RGBID_PG_SEQ_KF && e.type != RGBID_PG_LC_KF) return false;
+  }
+  return true;
+}
+
+// the fixing rules (buildGraph, pose_graph_manager.cpp:89-151) and the structure of every stage of the schedule
+int pg_plan(std::vector<Stage>& stages, int ng, const rgbid_pg_graph* graphs, const rgbid_pg_edge* edges, int multilevel, const int it[3], int max_sep,
+            int env_from) {
+  std::vector<std::vector<char>> fixed(ng);
+  for (int g = 0; g < ng; ++g) {
+    const rgbid_pg_graph& G = graphs[g];
+    fixed[g].assign(G.n_vertices, 0);
+    fixed[g][0] = 1;                                            // fix_last_flag_ = false: the first pose
+    int lc_min = -1;
+    for (int k = 0; k < G.n_edges; ++k) {
+      const rgbid_pg_edge& e = edges[G.e0 + k];
+      if (e.type == RGBID_PG_LC_KF) { const int m = std::min(e.from, e.to); lc_min = lc_min < 0 ? m : std::min(lc_min, m); }
+    }
+    if (lc_min >= 0) fixed[g][lc_min] = 1;                      // the smallest LC_KF endpoint (:147-150)
+  }
+  if (multilevel) {
+    stages.resize(2);
+    int r = build_stage(stages[0], ng, graphs, edges, 2, fixed, max_sep, env_from);
+    if (r) return r;
+    for (int g = 0; g < ng; ++g) {                               // every vertex active in level 2 is fixed for level 1 (:188-193)
+      const rgbid_pg_graph& G = graphs[g];
+      for (int k = 0; k < G.n_edges; ++k) {
+        const rgbid_pg_edge& e = edges[G.e0 + k];
+        if (e.type != RGBID_PG_SEQ_ODO) fixed[g][e.from] = fixed[g][e.to] = 1;
+      }
+    }
+    r = build_stage(stages[1], ng, graphs, edges, 1, fixed, max_sep, env_from);
+    if (r) return r;
+    stages[0].iters = it[0];
+    stages[1].iters = it[1];
+  } else {
+    stages.resize(1);
+    int r = build_stage(stages[0], ng, graphs, edges, 0, fixed, max_sep, env_from);
+    if (r) return r;
+    stages[0].iters = it[2];
   }
   return RGBID_OK;
 }
@@ -543,6 +787,7 @@ struct rgbid_pg {
   rgbid_ctx* ctx = nullptr;
   void* ws = nullptr;              // device workspace
   size_t ws_cap = 0;
+  int max_sep = RGBID_PG_MAX_SEPARATORS, env_from = RGBID_PG_MAX_SEPARATORS + 1;
   bool timing = false;
   double ms[7] = {0, 0, 0, 0, 0, 0, 0};
   hipEvent_t span[2] = {nullptr, nullptr};
@@ -588,6 +833,32 @@ int rgbid_pg_last_times(const rgbid_pg* p, double ms[7], int* launches) {
   return RGBID_OK;
 }
 
+int rgbid_pg_set_limits(rgbid_pg* p, int max_separators, int envelope_from) {
+  if (!p || max_separators < 1 || envelope_from < 1) return RGBID_E_INVALID;
+  p->max_sep = max_separators;
+  p->env_from = std::min(envelope_from, RGBID_PG_MAX_SEPARATORS + 1);   // the dense kernel's right-hand side is an LDS vector of the cap's size
+  return RGBID_OK;
+}
+
+int rgbid_pg_envelope(int n_vertices, int n_edges, const rgbid_pg_edge* edges, int stage, int capacity, int* n_separators, int32_t* sep_vertex,
+                      int32_t* first) {
+  if (n_vertices < 1 || n_edges < 0 || (n_edges > 0 && !edges) || stage < 0 || stage > 2 || capacity < 0 || !n_separators) return RGBID_E_INVALID;
+  const rgbid_pg_graph G = {0, n_vertices, 0, n_edges};
+  if (!pg_edges_valid(G, edges)) return RGBID_E_INVALID;
+  std::vector<Stage> stages;
+  const int it[3] = {1, 1, 1};
+  const int r = pg_plan(stages, 1, &G, edges, stage < 2, it, n_vertices, 1);
+  if (r) return r;
+  const Stage& st = stages[stage == 1 ? 1 : 0];
+  *n_separators = (int)st.erow.size();
+  if ((int)st.erow.size() > capacity) return RGBID_E_INVALID;
+  for (size_t i = 0; i < st.erow.size(); ++i) {
+    if (sep_vertex) sep_vertex[i] = st.fr[st.erow[i].slot].v;
+    if (first) first[i] = st.erow[i].first;
+  }
+  return RGBID_OK;
+}
+
 int rgbid_pg_last_work(const rgbid_pg* p, double* reduced_flops, double* linearise_bytes, double* segment_bytes) {
   if (!p) return RGBID_E_INVALID;
   if (reduced_flops) *reduced_flops = p->reduced_flops;
@@ -601,7 +872,7 @@ int rgbid_pg_optimise(rgbid_pg* p, int ng, const rgbid_pg_graph* graphs, double*
   if (!p || ng < 0 || (ng > 0 && (!graphs || !poses))) return RGBID_E_INVALID;
   const int it[3] = {iters ? iters[0] : 10, iters ? iters[1] : 5, iters ? iters[2] : 10};
   if (it[0] < 0 || it[1] < 0 || it[2] < 0) return RGBID_E_INVALID;
-  // ---- validation and the fixing rules (buildGraph, pose_graph_manager.cpp:89-151) ----
+  // ---- validation ----
   long long V = 0, E = 0;
   std::vector<std::pair<int, int>> vr, er;
   for (int g = 0; g < ng; ++g) {
@@ -611,50 +882,14 @@ int rgbid_pg_optimise(rgbid_pg* p, int ng, const rgbid_pg_graph* graphs, double*
     E = std::max(E, (long long)G.e0 + G.n_edges);
     vr.push_back({G.v0, G.v0 + G.n_vertices});
     if (G.n_edges) er.push_back({G.e0, G.e0 + G.n_edges});
-    for (int k = 0; k < G.n_edges; ++k) {
-      const rgbid_pg_edge& e = edges[G.e0 + k];
-      if (e.from < 0 || e.to < 0 || e.from >= G.n_vertices || e.to >= G.n_vertices || e.from == e.to) return RGBID_E_INVALID;
-      if (e.type != RGBID_PG_SEQ_ODO && e.type != RGBID_PG_SEQ_KF && e.type != RGBID_PG_LC_KF) return RGBID_E_INVALID;
-    }
+    if (!pg_edges_valid(G, edges)) return RGBID_E_INVALID;
   }
   std::sort(vr.begin(), vr.end());
   for (size_t q = 1; q < vr.size(); ++q) if (vr[q].first < vr[q - 1].second) return RGBID_E_INVALID;   // graphs share no vertex
   std::sort(er.begin(), er.end());
   for (size_t q = 1; q < er.size(); ++q) if (er[q].first < er[q - 1].second) return RGBID_E_INVALID;   // nor an edge
-  std::vector<std::vector<char>> fixed(ng);
-  for (int g = 0; g < ng; ++g) {
-    const rgbid_pg_graph& G = graphs[g];
-    fixed[g].assign(G.n_vertices, 0);
-    fixed[g][0] = 1;                                            // fix_last_flag_ = false: the first pose
-    int lc_min = -1;
-    for (int k = 0; k < G.n_edges; ++k) {
-      const rgbid_pg_edge& e = edges[G.e0 + k];
-      if (e.type == RGBID_PG_LC_KF) { const int m = std::min(e.from, e.to); lc_min = lc_min < 0 ? m : std::min(lc_min, m); }
-    }
-    if (lc_min >= 0) fixed[g][lc_min] = 1;                      // the smallest LC_KF endpoint (:147-150)
-  }
   std::vector<Stage> stages;
-  if (multilevel) {
-    stages.resize(2);
-    int r = build_stage(stages[0], ng, graphs, edges, 2, fixed);
-    if (r) return r;
-    for (int g = 0; g < ng; ++g) {                               // every vertex active in level 2 is fixed for level 1 (:188-193)
-      const rgbid_pg_graph& G = graphs[g];
-      for (int k = 0; k < G.n_edges; ++k) {
-        const rgbid_pg_edge& e = edges[G.e0 + k];
-        if (e.type != RGBID_PG_SEQ_ODO) fixed[g][e.from] = fixed[g][e.to] = 1;
-      }
-    }
-    r = build_stage(stages[1], ng, graphs, edges, 1, fixed);
-    if (r) return r;
-    stages[0].iters = it[0];
-    stages[1].iters = it[1];
-  } else {
-    stages.resize(1);
-    int r = build_stage(stages[0], ng, graphs, edges, 0, fixed);
-    if (r) return r;
-    stages[0].iters = it[2];
-  }
+  { const int r = pg_plan(stages, ng, graphs, edges, multilevel, it, p->max_sep, p->env_from); if (r) return r; }
   if (ng == 0) return RGBID_OK;
   // ---- edges as the kernels read them: Pinv = inverse6(inverse6(cov)), the constraint's information and its inverse (:84-104) ----
   std::vector<PgEdgeDev> ed((size_t)std::max<long long>(E, 1));
@@ -672,11 +907,12 @@ int rgbid_pg_optimise(rgbid_pg* p, int ng, const rgbid_pg_graph* graphs, double*
     }
   }
   // ---- workspace layout ----
-  size_t nlin = 0, nfr = 0, nseg = 0, ninc = 0, ngst = 0, nsep = 0, nsse = 0, nmat = 0;
+  size_t nlin = 0, nfr = 0, nseg = 0, ninc = 0, ngst = 0, nsep = 0, nsse = 0, nmat = 0, neg = 0, nerow = 0, nec = 0, nenv = 0;
   for (const Stage& s : stages) {
     nlin = std::max(nlin, s.lin_edge.size()); nfr = std::max(nfr, s.fr.size()); nseg = std::max(nseg, s.seg.size());
     ninc = std::max(ninc, s.inc.size()); ngst = std::max(ngst, s.gst.size()); nsep = std::max(nsep, s.sep_slot.size());
     nsse = std::max(nsse, s.sse.size()); nmat = std::max(nmat, (size_t)s.mat_doubles);
+    neg = std::max(neg, s.eg.size()); nerow = std::max(nerow, s.erow.size()); nec = std::max(nec, s.ec.size()); nenv = std::max(nenv, (size_t)s.env_blocks);
   }
   size_t off = 0;
   auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
@@ -686,8 +922,9 @@ int rgbid_pg_optimise(rgbid_pg* p, int ng, const rgbid_pg_graph* graphs, double*
                o_inc = take(sizeof(PgInc) * ninc), o_D = take(sizeof(double) * 36 * nfr), o_b = take(sizeof(double) * 6 * nfr),
                o_delta = take(sizeof(double) * 6 * nfr), o_sepidx = take(sizeof(int) * nfr), o_seg = take(sizeof(PgSeg) * nseg),
                o_segv = take(sizeof(double) * PG_SEGV * nfr), o_segs = take(sizeof(double) * PG_SEGS * nseg), o_gst = take(sizeof(PgGraphStage) * ngst),
-               o_sep = take(sizeof(int) * nsep), o_sse = take(sizeof(PgSse) * nsse), o_mat = take(sizeof(double) * nmat);
-  (void)o_mat;
+               o_sep = take(sizeof(int) * nsep), o_sse = take(sizeof(PgSse) * nsse), o_mat = take(sizeof(double) * nmat),
+               o_eg = take(sizeof(PgEnvGraph) * neg), o_erow = take(sizeof(PgEnvRow) * nerow), o_ec = take(sizeof(PgEnvC) * nec),
+               o_renv = take(sizeof(double) * 6 * nerow), o_env = take(sizeof(double) * 36 * nenv);
   (void)hipSetDevice(p->ctx->device);
   hipStream_t s = p->ctx->stream;
   if (off > p->ws_cap) {
@@ -756,6 +993,10 @@ int rgbid_pg_optimise(rgbid_pg* p, int ng, const rgbid_pg_graph* graphs, double*
     PgGraphStage* d_gst = (PgGraphStage*)(w + o_gst);
     int* d_sep = (int*)(w + o_sep);
     PgSse* d_sse = (PgSse*)(w + o_sse);
+    PgEnvGraph* d_eg = (PgEnvGraph*)(w + o_eg);
+    PgEnvRow* d_erow = (PgEnvRow*)(w + o_erow);
+    PgEnvC* d_ec = (PgEnvC*)(w + o_ec);
+    double *d_renv = (double*)(w + o_renv), *d_env = (double*)(w + o_env);
     auto up = [&](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess; };
     PG_HIPC(up(d_linedge, st.lin_edge.data(), sizeof(int) * st.lin_edge.size()));
     PG_HIPC(up(d_fr, st.fr.data(), sizeof(PgFree) * st.fr.size()));
@@ -765,9 +1006,13 @@ int rgbid_pg_optimise(rgbid_pg* p, int ng, const rgbid_pg_graph* graphs, double*
     PG_HIPC(up(d_gst, st.gst.data(), sizeof(PgGraphStage) * st.gst.size()));
     PG_HIPC(up(d_sep, st.sep_slot.data(), sizeof(int) * st.sep_slot.size()));
     PG_HIPC(up(d_sse, st.sse.data(), sizeof(PgSse) * st.sse.size()));
+    PG_HIPC(up(d_eg, st.eg.data(), sizeof(PgEnvGraph) * st.eg.size()));
+    PG_HIPC(up(d_erow, st.erow.data(), sizeof(PgEnvRow) * st.erow.size()));
+    PG_HIPC(up(d_ec, st.ec.data(), sizeof(PgEnvC) * st.ec.size()));
     // the stage uploads read pageable host vectors: they complete before the call returns, and the vectors outlive it
     const int nl = (int)st.lin_edge.size(), nf = (int)st.fr.size(), nsg = (int)st.seg.size(), ngs = (int)st.gst.size();
-    double fl = 0;
+    const int neg_ = (int)st.eg.size(), ner = (int)st.erow.size();
+    double fl = st.env_flops;
     for (const PgGraphStage& g : st.gst) { const double n = 6.0 * g.ns; fl += n * n * n / 3.0 + 2.0 * n * n; }
     p->reduced_flops += fl * st.iters;
     p->lin_bytes += (double)st.iters * nl * (sizeof(PgEdgeDev) + 2 * 12 * 8 + PG_LIN * 8 + 4);
@@ -778,6 +1023,10 @@ int rgbid_pg_optimise(rgbid_pg* p, int ng, const rgbid_pg_graph* graphs, double*
       timed(1, [&] { hipLaunchKernelGGL(k_pg_assemble, dim3(pg_grid(nf, PG_T)), dim3(PG_T), 0, s, d_fr, nf, d_inc, d_lin, d_failed, d_D, d_b); });
       if (nsg) timed(2, [&] { hipLaunchKernelGGL(k_pg_segment, dim3(pg_grid(nsg, PG_T)), dim3(PG_T), 0, s, d_seg, nsg, d_fr, d_inc, d_lin, d_D, d_b, d_failed, d_segv, d_segs); });
       if (ngs) timed(3, [&] { hipLaunchKernelGGL(k_pg_reduced, dim3(ngs), dim3(PG_RT), 0, s, d_gst, d_sep, d_sse, d_seg, d_lin, d_D, d_b, d_segs, d_mat, d_sepidx, d_failed, d_delta); });
+      if (neg_) {
+        timed(3, [&] { hipLaunchKernelGGL(k_pg_env_assemble, dim3(ner), dim3(PG_ET), 0, s, d_erow, d_ec, d_lin, d_D, d_b, d_segs, d_failed, d_env, d_renv); });
+        timed(3, [&] { hipLaunchKernelGGL(k_pg_env_factor, dim3(neg_), dim3(PG_ET), 0, s, d_eg, d_erow, d_env, d_renv, d_failed, d_delta); });
+      }
       if (nsg) timed(4, [&] { hipLaunchKernelGGL(k_pg_backsub, dim3(pg_grid(nsg, PG_T)), dim3(PG_T), 0, s, d_seg, nsg, d_segv, d_failed, d_delta); });
       timed(4, [&] { hipLaunchKernelGGL(k_pg_update, dim3(pg_grid(nf, PG_T)), dim3(PG_T), 0, s, d_fr, nf, d_delta, d_failed, d_poses); });
     }

@@ -53,6 +53,8 @@ bool PoseGraph::optimiseGraph() {
   rgbid_pg_graph g = {0, (int32_t)(poses_.size() / 12), 0, (int32_t)edges_.size()};
   std::vector<double> out(poses_);
   int st = RGBID_PG_OK;
+  // more separators than the dense reduced solver takes (a long run): the envelope solver; up to the cap nothing changes
+  if (g.n_vertices > RGBID_PG_MAX_SEPARATORS && rgbid_pg_set_limits(pg_, g.n_vertices, RGBID_PG_MAX_SEPARATORS + 1) != RGBID_OK) return false;
   if (rgbid_pg_optimise(pg_, 1, &g, out.data(), edges_.empty() ? nullptr : edges_.data(), multilevel_ ? 1 : 0, iters_, &st, chi2_) != RGBID_OK)
     return false;
   poses_.swap(out);

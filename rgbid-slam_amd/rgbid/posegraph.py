@@ -22,7 +22,8 @@ EDGE_DTYPE = np.dtype([("from", "<i4"), ("to", "<i4"), ("type", "<i4"), ("reserv
 assert EDGE_DTYPE.itemsize == 400
 GRAPH_DTYPE = np.dtype([("v0", "<i4"), ("n_vertices", "<i4"), ("e0", "<i4"), ("n_edges", "<i4")])
 
-EXPORTS = ["rgbid_pg_create", "rgbid_pg_destroy", "rgbid_pg_optimise", "rgbid_pg_set_timing", "rgbid_pg_last_times", "rgbid_pg_last_work"]
+EXPORTS = ["rgbid_pg_create", "rgbid_pg_destroy", "rgbid_pg_optimise", "rgbid_pg_set_timing", "rgbid_pg_last_times", "rgbid_pg_last_work",
+           "rgbid_pg_set_limits", "rgbid_pg_envelope"]
 
 
 def edges(rows):
@@ -104,6 +105,12 @@ class PoseGraph:
     def set_timing(self, on):
         check(self.L.rgbid_pg_set_timing(self._h, int(bool(on))))
 
+    def set_limits(self, max_separators, envelope_from=None):
+        """max_separators: graphs with more separators in a stage are refused (default MAX_SEPARATORS).  envelope_from: stages with at least
+        this many separators go to the envelope factorisation instead of the dense one (None = the default MAX_SEPARATORS + 1: exactly the
+        graphs the dense solver cannot take; 1 = always).  The results do not depend on envelope_from."""
+        check(self.L.rgbid_pg_set_limits(self._h, int(max_separators), MAX_SEPARATORS + 1 if envelope_from is None else int(envelope_from)))
+
     def last_times(self):
         """(ms [linearise, assemble, segment, reduced, backsub + update, chi2, whole call on the device], launches) of the last timed call"""
         ms = (C.c_double * 7)()
@@ -142,6 +149,19 @@ class PoseGraph:
         E = np.concatenate([np.asarray(E, EDGE_DTYPE) for _, E in graphs]) if graphs else np.zeros(0, EDGE_DTYPE)
         out, status, chi2 = self.optimise_flat(ranges, P, E, multilevel, iters)
         return [out[r["v0"]:r["v0"] + r["n_vertices"]] for r in ranges], status, chi2
+
+
+def envelope(n_vertices, edges, stage):
+    """Host only: the separators of a stage (0 / 1: multilevel level 2 / level 1, 2: single level) of one graph and the block envelope of its
+    reduced system -> (sep_vertex [ns], first [ns]): first[i] is the first block column of block row i."""
+    L = _lib.lib()
+    E = np.ascontiguousarray(edges, EDGE_DTYPE)
+    n = C.c_int()
+    sv = np.zeros(max(int(n_vertices), 1), np.int32)
+    fi = np.zeros(max(int(n_vertices), 1), np.int32)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    check(L.rgbid_pg_envelope(int(n_vertices), len(E), p(E) if len(E) else None, int(stage), len(sv), C.byref(n), p(sv), p(fi)))
+    return sv[:n.value].copy(), fi[:n.value].copy()
 
 
 # ---- graphs from a run of the engine ----
@@ -286,6 +306,8 @@ def optimise_run(ctx, R, t, chunk_records, first_frames, headers, keyframes, K, 
     appearance = appearance if isinstance(loops, str) and loops == "appearance" else None
     pg = PoseGraph(ctx)
     try:
+        # a long run has more separators than the dense reduced solver takes: those stages go to the envelope solver (same bytes below the cap)
+        pg.set_limits(max(MAX_SEPARATORS, len(P)))
         out, status, chi2 = pg.optimise([(P, E)], multilevel=mode == "multilevel")
     finally:
         pg.close()
