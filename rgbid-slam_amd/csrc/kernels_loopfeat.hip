@@ -1,7 +1,9 @@
 // kernels_loopfeat.hip -- appearance stage of loop closure (include/rgbid_loopfeat.h; LoopCloser::detectLoopClosures and
 // computeRANSACTrafo3D, src/loop_closer.cpp:193-716; Keyframe::lift2DKeypointsto3DPointsWithCovariance, src/keyframe.cpp:232-274).
 //
-//   features  k_lf_response   Harris response per pixel: a 24 x 24 grey tile and its 22 x 22 integer derivatives in LDS, 49 products per pixel
+//   features  k_lf_pyramid    level l of the scale pyramid from level l - 1 (extractors of several levels): integer bilinear, 4 pixels per thread
+//             the three kernels below run once over all levels: a flat grid over (level, tile | cell | slot) x keyframe, the level from a table
+//             k_lf_response   Harris response per pixel: a 24 x 24 grey tile and its 22 x 22 integer derivatives in LDS, 49 products per pixel
 //             k_lf_select     one workgroup per 32 x 32 cell: strict local maxima appended to an LDS list (integer LDS counter; the list's
 //                             order does not matter), ranked by counting (response descending, raster index ascending); the best k go to a
 //                             staging table [keyframe][cell][rank]
@@ -31,6 +33,7 @@ using namespace rgbid;
 static_assert(sizeof(rgbid_loopfeat_kp) == 120, "rgbid_loopfeat_kp is 120 bytes");
 static_assert(offsetof(rgbid_loopfeat_kp, desc) == 16 && offsetof(rgbid_loopfeat_kp, X) == 48 && offsetof(rgbid_loopfeat_kp, cov) == 72, "record layout");
 static_assert(sizeof(rgbid_loopfeat_corr) == 16, "rgbid_loopfeat_corr is 16 bytes");
+static_assert(sizeof(rgbid_loopfeat_aux) == 16 && offsetof(rgbid_loopfeat_aux, level) == 12, "rgbid_loopfeat_aux is 16 bytes");
 
 namespace {
 
@@ -42,8 +45,17 @@ constexpr int PATCH = 2 * BORDER + 1;                // 33
 constexpr int RCHUNK = 128;                          // matches per LDS chunk of the vote
 constexpr int HARRIS_R = 3;                          // 7 x 7 block
 constexpr int RESP_MARGIN = HARRIS_R + 1;
+constexpr int MAXL = RGBID_LOOPFEAT_MAX_LEVELS;
 
-struct LfGeom { int rows, cols, cells_x, cells_y, per_cell, max_kp; };
+// one pyramid level: its image, its cells and where its tiles, cells, staging slots and describe blocks start in the grids over all levels
+struct LfLevel {
+  int rows, cols, cells_x, cells_y, per_cell;
+  float s;                                       // (float) pow(scale, level): level pixel -> level-0 pixel
+  int img_off, resp_off;                         // per keyframe: bytes into the pyramid scratch (levels >= 1), floats into the response scratch
+  int cell_off, slot_off;                        // cells and staging slots of the levels below
+  int tiles_x, tile_off, dblock_off;             // response tiles of 16 x 16 and describe blocks of the levels below
+};
+struct LfGeom { int rows, cols, levels, max_kp, cells, slots, resp_stride, pyr_stride; };   // level 0's size; totals over the levels; per-keyframe strides
 struct LfKinv { double m[9]; };
 struct LfStaged { int idx; float resp; };
 
@@ -56,17 +68,57 @@ __device__ __forceinline__ int wave_sum(int v) {
   return v;
 }
 
+// the level whose range of a flat grid holds block b (uniform over the block: scalar loads of a table of at most 8 entries)
+__device__ __forceinline__ int lf_level_of(const LfLevel* __restrict__ lv, int levels, int b, int LfLevel::*off) {
+  int l = levels - 1;
+  while (l > 0 && b < lv[l].*off) --l;
+  return l;
+}
+
+__device__ __forceinline__ const uint8_t* lf_image(const uint8_t* grey, const uint8_t* pyr, const LfGeom& g, const LfLevel& lv, int level, int kf) {
+  return level == 0 ? grey + (size_t)kf * g.rows * g.cols : pyr + (size_t)kf * g.pyr_stride + lv.img_off;
+}
+
 // ---- features ----
-__global__ __launch_bounds__(LT) void k_lf_response(const uint8_t* __restrict__ grey, LfGeom g, float scale4, float* __restrict__ resp) {
+// level l from level l - 1: bilinear with 11-bit weights from the host's (x0, w1) tables, in int32.  A thread makes 4 consecutive pixels of the
+// destination image taken as one flat array (they may run over a row end) and stores them as one word; the image's slot in the scratch is
+// padded to a multiple of 4 bytes, so the last word stays inside it.
+__global__ __launch_bounds__(LT) void k_lf_pyramid(const uint8_t* __restrict__ src, size_t src_stride, int srows, int scols, uint8_t* __restrict__ dst,
+                                                   size_t dst_stride, int drows, int dcols, const int2* __restrict__ xtab, const int2* __restrict__ ytab) {
+  const int kf = blockIdx.y, i0 = 4 * (blockIdx.x * LT + threadIdx.x), dpx = drows * dcols;
+  if (i0 >= dpx) return;
+  const uint8_t* S = src + (size_t)kf * src_stride;
+  int y = i0 / dcols, x = i0 - y * dcols;
+  unsigned word = 0;
+  for (int k = 0; k < 4 && i0 + k < dpx; ++k) {
+    const int2 tx = xtab[x], ty = ytab[y];
+    const int x1 = min(tx.x + 1, scols - 1), y1 = min(ty.x + 1, srows - 1);
+    const int w1x = tx.y, w0x = 2048 - w1x, w1y = ty.y, w0y = 2048 - w1y;
+    const uint8_t* r0 = S + (size_t)ty.x * scols;
+    const uint8_t* r1 = S + (size_t)y1 * scols;
+    const int top = w0x * r0[tx.x] + w1x * r0[x1], bot = w0x * r1[tx.x] + w1x * r1[x1];
+    const int v = (w0y * top + w1y * bot + (1 << 21)) >> 22;
+    word |= (unsigned)v << (8 * k);
+    if (++x == dcols) { x = 0; ++y; }
+  }
+  *reinterpret_cast<unsigned*>(dst + (size_t)kf * dst_stride + i0) = word;
+}
+
+// 7 waves per SIMD as with one level: without the hint the allocator takes 88 VGPRs (5 waves) for the same loops
+__global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(7, 8))) void k_lf_response(const uint8_t* __restrict__ grey, const uint8_t* __restrict__ pyr, LfGeom g,
+                                                    const LfLevel* __restrict__ levels, float scale4, float* __restrict__ resp) {
   __shared__ int tile[24][24];
   __shared__ short dIx[22][22], dIy[22][22];
-  const int kf = blockIdx.z, tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-  const int x0 = blockIdx.x * 16, y0 = blockIdx.y * 16;
-  const uint8_t* img = grey + (size_t)kf * g.rows * g.cols;
+  const int level = lf_level_of(levels, g.levels, blockIdx.x, &LfLevel::tile_off);
+  const LfLevel lv = levels[level];
+  const int t = blockIdx.x - lv.tile_off;
+  const int kf = blockIdx.y, tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+  const int x0 = (t % lv.tiles_x) * 16, y0 = (t / lv.tiles_x) * 16;
+  const uint8_t* img = lf_image(grey, pyr, g, lv, level, kf);
   for (int i = threadIdx.x; i < 24 * 24; i += LT) {
     const int ly = i / 24, lx = i % 24;
-    const int y = min(max(y0 + ly - RESP_MARGIN, 0), g.rows - 1), x = min(max(x0 + lx - RESP_MARGIN, 0), g.cols - 1);   // clamped reads feed only refused pixels
-    tile[ly][lx] = img[(size_t)y * g.cols + x];
+    const int y = min(max(y0 + ly - RESP_MARGIN, 0), lv.rows - 1), x = min(max(x0 + lx - RESP_MARGIN, 0), lv.cols - 1);   // clamped reads feed only refused pixels
+    tile[ly][lx] = img[(size_t)y * lv.cols + x];
   }
   __syncthreads();
   for (int i = threadIdx.x; i < 22 * 22; i += LT) {
@@ -80,9 +132,9 @@ __global__ __launch_bounds__(LT) void k_lf_response(const uint8_t* __restrict__ 
   }
   __syncthreads();
   const int x = x0 + tx, y = y0 + ty;
-  if (x >= g.cols || y >= g.rows) return;
+  if (x >= lv.cols || y >= lv.rows) return;
   float r = 0.f;
-  if (x >= RESP_MARGIN && x < g.cols - RESP_MARGIN && y >= RESP_MARGIN && y < g.rows - RESP_MARGIN) {
+  if (x >= RESP_MARGIN && x < lv.cols - RESP_MARGIN && y >= RESP_MARGIN && y < lv.rows - RESP_MARGIN) {
     int sxx = 0, syy = 0, sxy = 0;
     for (int j = 0; j < 7; ++j)
       for (int i = 0; i < 7; ++i) {
@@ -93,38 +145,50 @@ __global__ __launch_bounds__(LT) void k_lf_response(const uint8_t* __restrict__ 
     const float tr = (float)(sxx + syy);
     r = (a - b) - ((0.04f * tr) * tr) * scale4;
   }
-  resp[((size_t)kf * g.rows + y) * g.cols + x] = r;
+  resp[(size_t)kf * g.resp_stride + lv.resp_off + (size_t)y * lv.cols + x] = r;
 }
 
 // a beats b: larger response, or equal response and smaller raster index
 __device__ __forceinline__ bool lf_beats(float ra, int ia, float rb, int ib) { return ra > rb || (ra == rb && ia < ib); }
 
+// the level-0 pixel whose depth a keypoint at coordinate v of a level reads: (int) ((double) ((float) v * s) + 0.5); p receives the float product
+__device__ __forceinline__ int lf_pixel0(int v, float s, float* p) {
+  *p = (float)v * s;
+  return (int)((double)*p + 0.5);
+}
+
 __global__ __launch_bounds__(LT) void k_lf_select(const float* __restrict__ resp, const float* __restrict__ invdepth, LfGeom g,
-                                                  LfStaged* __restrict__ staged, int* __restrict__ cell_counts) {
+                                                  const LfLevel* __restrict__ levels, LfStaged* __restrict__ staged, int* __restrict__ cell_counts) {
   __shared__ int cnt;
   __shared__ float cr[CELL_CAND];
   __shared__ int ci[CELL_CAND];
-  const int kf = blockIdx.y, cell = blockIdx.x, cells = g.cells_x * g.cells_y;
-  const int cx = cell % g.cells_x, cy = cell / g.cells_x;
-  const float* R = resp + (size_t)kf * g.rows * g.cols;
+  const int level = lf_level_of(levels, g.levels, blockIdx.x, &LfLevel::cell_off);
+  const LfLevel lv = levels[level];
+  const int kf = blockIdx.y, cell = blockIdx.x - lv.cell_off;
+  const int cx = cell % lv.cells_x, cy = cell / lv.cells_x;
+  const float* R = resp + (size_t)kf * g.resp_stride + lv.resp_off;
   const float* W = invdepth + (size_t)kf * g.rows * g.cols;
   if (threadIdx.x == 0) cnt = 0;
   __syncthreads();
   for (int p = threadIdx.x; p < CELL * CELL; p += LT) {
     const int x = cx * CELL + p % CELL, y = cy * CELL + p / CELL;
-    if (x < BORDER || x >= g.cols - BORDER || y < BORDER || y >= g.rows - BORDER) continue;   // the 8 neighbours are inside the image
-    const int idx = y * g.cols + x;
+    if (x < BORDER || x >= lv.cols - BORDER || y < BORDER || y >= lv.rows - BORDER) continue;   // the 8 neighbours are inside the image
+    const int idx = y * lv.cols + x;
     const float r = R[idx];
     if (!(r > 0.f)) continue;
     bool is_max = true;
     for (int dy = -1; dy <= 1; ++dy)
       for (int dx = -1; dx <= 1; ++dx) {
         if (dx == 0 && dy == 0) continue;
-        const int j = idx + dy * g.cols + dx;
+        const int j = idx + dy * lv.cols + dx;
         is_max = is_max && lf_beats(r, idx, R[j], j);
       }
-    const float w = W[idx];
-    if (!is_max || !(isfinite(w) && w > 0.f)) continue;
+    if (!is_max) continue;
+    float pf;
+    const int X0 = lf_pixel0(x, lv.s, &pf), Y0 = lf_pixel0(y, lv.s, &pf);
+    if (X0 >= g.cols || Y0 >= g.rows) continue;
+    const float w = W[(size_t)Y0 * g.cols + X0];
+    if (!(isfinite(w) && w > 0.f)) continue;
     const int slot = atomicAdd(&cnt, 1);   // integer LDS counter: the list's order is arbitrary, the ranks below do not depend on it
     if (slot < CELL_CAND) { cr[slot] = r; ci[slot] = idx; }
   }
@@ -135,9 +199,9 @@ __global__ __launch_bounds__(LT) void k_lf_select(const float* __restrict__ resp
     const int idx = ci[threadIdx.x];
     int rank = 0;
     for (int j = 0; j < nc; ++j) rank += lf_beats(cr[j], ci[j], r, idx) ? 1 : 0;
-    if (rank < g.per_cell) staged[((size_t)kf * cells + cell) * g.per_cell + rank] = LfStaged{idx, r};
+    if (rank < lv.per_cell) staged[(size_t)kf * g.slots + lv.slot_off + cell * lv.per_cell + rank] = LfStaged{idx, r};
   }
-  if (threadIdx.x == 0) cell_counts[(size_t)kf * cells + cell] = min(nc, g.per_cell);
+  if (threadIdx.x == 0) cell_counts[(size_t)kf * g.cells + blockIdx.x] = min(nc, lv.per_cell);
 }
 
 __device__ __forceinline__ int lf_box(const uint8_t* patch, int px, int py) {
@@ -147,35 +211,38 @@ __device__ __forceinline__ int lf_box(const uint8_t* patch, int px, int py) {
   return s;
 }
 
-__global__ __launch_bounds__(LT) void k_lf_describe(const uint8_t* __restrict__ grey, const float* __restrict__ invdepth, LfGeom g, LfKinv Ki,
+__global__ __launch_bounds__(LT) void k_lf_describe(const uint8_t* __restrict__ grey, const uint8_t* __restrict__ pyr,
+                                                    const float* __restrict__ invdepth, LfGeom g, const LfLevel* __restrict__ levels, LfKinv Ki,
                                                     const LfStaged* __restrict__ staged, const int* __restrict__ cell_counts,
                                                     const char4* __restrict__ rotated, const double* __restrict__ bounds,
-                                                    rgbid_loopfeat_kp* __restrict__ kps, int* __restrict__ counts) {
+                                                    rgbid_loopfeat_kp* __restrict__ kps, int* __restrict__ counts, rgbid_loopfeat_aux* __restrict__ aux) {
   __shared__ uint8_t patches[LT / 64][PATCH * PATCH + 7];
-  const int kf = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, cells = g.cells_x * g.cells_y;
-  const int slot = blockIdx.x * (LT / 64) + wave;
-  const int cell = slot / g.per_cell, rank = slot % g.per_cell;
-  const int* cc = cell_counts + (size_t)kf * cells;
-  const bool in_table = slot < cells * g.per_cell;
-  int before = 0;
+  const int level = lf_level_of(levels, g.levels, blockIdx.x, &LfLevel::dblock_off);
+  const LfLevel lv = levels[level];
+  const int kf = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int slot = (blockIdx.x - lv.dblock_off) * (LT / 64) + wave;   // within the level
+  const int cell = slot / lv.per_cell, rank = slot % lv.per_cell;
+  const int* cc = cell_counts + (size_t)kf * g.cells;
+  const bool in_table = slot < lv.cells_x * lv.cells_y * lv.per_cell;
+  int before = 0;   // keypoints of the levels below and of this level's cells before this one
   if (in_table)
-    for (int c = lane; c < cell; c += 64) before += cc[c];
+    for (int c = lane; c < lv.cell_off + cell; c += 64) before += cc[c];
   before = wave_sum(before);
-  if (slot == 0) {   // the first wave of a keyframe also writes its keypoint count
+  if (blockIdx.x == 0 && wave == 0) {   // the first wave of a keyframe also writes its keypoint count
     int total = 0;
-    for (int c = lane; c < cells; c += 64) total += cc[c];
+    for (int c = lane; c < g.cells; c += 64) total += cc[c];
     total = wave_sum(total);
     if (lane == 0) counts[kf] = total;
   }
-  const bool active = in_table && rank < cc[cell];
+  const bool active = in_table && rank < cc[lv.cell_off + cell];
   uint8_t* patch = patches[wave];
-  const uint8_t* img = grey + (size_t)kf * g.rows * g.cols;
+  const uint8_t* img = lf_image(grey, pyr, g, lv, level, kf);
   int idx = 0, x = BORDER, y = BORDER;
   float response = 0.f;
   if (active) {
-    const LfStaged st = staged[((size_t)kf * cells + cell) * g.per_cell + rank];
-    idx = st.idx; response = st.resp; x = idx % g.cols; y = idx / g.cols;   // BORDER <= x < cols - BORDER and the same for y: the patch is inside
-    for (int i = lane; i < PATCH * PATCH; i += 64) patch[i] = img[(size_t)(y + i / PATCH - BORDER) * g.cols + (x + i % PATCH - BORDER)];
+    const LfStaged st = staged[(size_t)kf * g.slots + lv.slot_off + cell * lv.per_cell + rank];
+    idx = st.idx; response = st.resp; x = idx % lv.cols; y = idx / lv.cols;   // BORDER <= x < cols - BORDER and the same for y: the patch is inside
+    for (int i = lane; i < PATCH * PATCH; i += 64) patch[i] = img[(size_t)(y + i / PATCH - BORDER) * lv.cols + (x + i % PATCH - BORDER)];
   }
   __syncthreads();
   if (!active) return;
@@ -194,7 +261,8 @@ __global__ __launch_bounds__(LT) void k_lf_describe(const uint8_t* __restrict__ 
   int passed = 0;
   for (int b = 0; b < 16; ++b) passed += (bounds[2 * b] * my - bounds[2 * b + 1] * mx > 0.0) ? 1 : 0;
   const int dir = (passed + (upper ? 0 : 16)) & 31;
-  rgbid_loopfeat_kp* out = kps + (size_t)kf * g.max_kp + before + rank;
+  const size_t rec = (size_t)kf * g.max_kp + before + rank;   // before + rank < sum over levels of cells x per_cell <= max_kp
+  rgbid_loopfeat_kp* out = kps + rec;
   uint8_t* desc = out->desc;
   for (int j = 0; j < 4; ++j) {
     const char4 p = rotated[dir * RGBID_LOOPFEAT_TESTS + j * 64 + lane];
@@ -203,11 +271,15 @@ __global__ __launch_bounds__(LT) void k_lf_describe(const uint8_t* __restrict__ 
     if (lane < 8) desc[j * 8 + lane] = (uint8_t)(m >> (8 * lane));
   }
   if (lane == 0) {
-    out->x = x; out->y = y; out->response = response; out->direction = dir;
-    const float w = invdepth[(size_t)kf * g.rows * g.cols + idx];
-    const double d = (double)(1.f / w), px = (double)x, py = (double)y, pz = 1.0;
+    float pxf, pyf;
+    const int X0 = lf_pixel0(x, lv.s, &pxf), Y0 = lf_pixel0(y, lv.s, &pyf);   // the select kernel has checked them against the level-0 size
+    out->x = X0; out->y = Y0; out->response = response; out->direction = dir;
+    if (aux) aux[rec] = rgbid_loopfeat_aux{pxf, pyf, (int16_t)x, (int16_t)y, level};
+    const float w = invdepth[((size_t)kf * g.rows + Y0) * g.cols + X0];
+    const double d = (double)(1.f / w), px = (double)pxf, py = (double)pyf, pz = 1.0;
     const double inv_d = 1.0 / d;
-    const double s[3] = {(double)(0.5f * 0.5f), (double)(0.5f * 0.5f), (double)(0.00025f * 0.00025f)};
+    const float var = ((lv.s * lv.s) * 0.5f) * 0.5f;   // the pixel variance 0.25 widened by scale^(2 level), formed in float
+    const double s[3] = {(double)var, (double)var, (double)(0.00025f * 0.00025f)};
     double X[3], J[3][3];
     for (int i = 0; i < 3; ++i) {
       const double a0 = d * Ki.m[3 * i], a1 = d * Ki.m[3 * i + 1], a2 = d * Ki.m[3 * i + 2];
@@ -490,22 +562,93 @@ void lf_pattern(int8_t* pattern) {
   }
 }
 
+
+// the levels that exist and each one's cells and share of the keypoints (the header's "level geometry" and "budget per level")
+struct LfPlan { int levels; int rows[MAXL], cols[MAXL], cells_x[MAXL], cells_y[MAXL], per_cell[MAXL]; float s[MAXL]; };
+
+int lf_plan(int rows, int cols, int max_keypoints, int levels, float scale, LfPlan& p) {
+  if (rows < 2 * BORDER + 1 || cols < 2 * BORDER + 1 || rows > 8192 || cols > 8192) return RGBID_E_INVALID;
+  if (levels < 1 || levels > MAXL || !(scale > 1.f && scale <= 2.f)) return RGBID_E_INVALID;
+  if (max_keypoints < 1 || max_keypoints > RGBID_LOOPFEAT_MAX_KEYPOINTS) return RGBID_E_INVALID;
+  p.levels = 0;
+  for (int l = 0; l < levels; ++l) {
+    const float s = (float)std::pow((double)scale, (double)l);
+    const int c = (int)(((float)cols + 0.5f) / s), r = (int)(((float)rows + 0.5f) / s);
+    if (r < 2 * BORDER + 1 || c < 2 * BORDER + 1) break;
+    p.rows[l] = r; p.cols[l] = c; p.s[l] = s;
+    p.cells_x[l] = (c + CELL - 1) / CELL; p.cells_y[l] = (r + CELL - 1) / CELL;
+    p.levels = l + 1;
+  }
+  const double sd = (double)scale, r = 1.0 / (sd * sd);
+  double rL = 1.0;
+  for (int l = 0; l < p.levels; ++l) rL *= r;
+  double rl = 1.0;
+  long long slots = 0;
+  for (int l = 0; l < p.levels; ++l, rl *= r) {
+    const int n = (int)std::floor((double)max_keypoints * (((1.0 - r) * rl) / (1.0 - rL)));   // one level: exactly max_keypoints
+    const int cells = p.cells_x[l] * p.cells_y[l];
+    const int k = n / cells < 1 ? 1 : n / cells;
+    p.per_cell[l] = k < RGBID_LOOPFEAT_CELL_MAX ? k : RGBID_LOOPFEAT_CELL_MAX;
+    slots += (long long)cells * p.per_cell[l];
+  }
+  return slots > max_keypoints ? RGBID_E_INVALID : RGBID_OK;
+}
+
 }  // namespace
 
 struct rgbid_loopfeat {
   rgbid_ctx* ctx = nullptr;
   LfGeom g{};
+  LfLevel lv[MAXL] = {};
+  int tiles = 0, dblocks = 0;        // response tiles and describe blocks over all levels
+  int tab_off[MAXL][2] = {};         // level l's column and row resize tables in `tabs`
   float* resp = nullptr;
   LfStaged* staged = nullptr;
   int* cell_counts = nullptr;
+  uint8_t* pyr = nullptr;            // levels 1 .. L - 1 of cap_kf keyframes
   int cap_kf = 0;
   char4* rotated = nullptr;
   double* bounds = nullptr;
+  LfLevel* levels_dev = nullptr;
+  int2* tabs = nullptr;
   bool timing = false;
-  hipEvent_t ev[8] = {};   // 0-3 extract, 4-5 match, 6-7 ransac
-  bool timed[3] = {false, false, false};
+  hipEvent_t ev[10] = {};   // 0-3 extract, 4-5 match, 6-7 ransac, 8-9 pyramid
+  bool timed[4] = {false, false, false, false};
   void mark(int i) { if (timing) (void)hipEventRecord(ev[i], ctx->stream); }
 };
+
+namespace {
+
+// scratch for n keyframes
+int lf_reserve(rgbid_loopfeat* f, int n) {
+  if (n <= f->cap_kf) return RGBID_OK;
+  RGBID_HIPC(hipStreamSynchronize(f->ctx->stream));
+  for (void* p : {(void*)f->resp, (void*)f->staged, (void*)f->cell_counts, (void*)f->pyr}) if (p) (void)hipFree(p);
+  f->resp = nullptr; f->staged = nullptr; f->cell_counts = nullptr; f->pyr = nullptr; f->cap_kf = 0;
+  const LfGeom& g = f->g;
+  int r = lf_alloc((void**)&f->resp, sizeof(float) * (size_t)n * g.resp_stride);
+  if (!r) r = lf_alloc((void**)&f->staged, sizeof(LfStaged) * (size_t)n * g.slots);
+  if (!r) r = lf_alloc((void**)&f->cell_counts, sizeof(int) * (size_t)n * g.cells);
+  if (!r && g.pyr_stride) r = lf_alloc((void**)&f->pyr, (size_t)n * g.pyr_stride);
+  if (r) return r;
+  f->cap_kf = n;
+  return RGBID_OK;
+}
+
+// levels 1 .. upto of n keyframes into the scratch, each from the level below
+void lf_build_pyramid(rgbid_loopfeat* f, const uint8_t* grey_dev, int n, int upto) {
+  const LfGeom& g = f->g;
+  for (int l = 1; l <= upto; ++l) {
+    const LfLevel &a = f->lv[l - 1], &b = f->lv[l];
+    const uint8_t* src = l == 1 ? grey_dev : f->pyr + a.img_off;
+    const size_t src_stride = l == 1 ? (size_t)g.rows * g.cols : (size_t)g.pyr_stride;
+    const int words = (b.rows * b.cols + 3) / 4;
+    hipLaunchKernelGGL(k_lf_pyramid, dim3((words + LT - 1) / LT, n), dim3(LT), 0, f->ctx->stream, src, src_stride, a.rows, a.cols, f->pyr + b.img_off,
+                       (size_t)g.pyr_stride, b.rows, b.cols, f->tabs + f->tab_off[l][0], f->tabs + f->tab_off[l][1]);
+  }
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -531,28 +674,88 @@ int rgbid_loopfeat_tables(int8_t* pattern, int8_t* rotated, double* bounds) {
   return RGBID_OK;
 }
 
+int rgbid_loopfeat_resize_table(int src, int dst, int32_t* x0, int32_t* w1) {
+  if (src < 1 || dst < 1 || !x0 || !w1) return RGBID_E_INVALID;
+  const double ratio = (double)src / (double)dst;
+  for (int d = 0; d < dst; ++d) {
+    const double fx = ((double)d + 0.5) * ratio - 0.5;
+    const double fl = std::floor(fx);
+    int i = (int)fl, w = (int)std::floor((fx - fl) * 2048.0 + 0.5);
+    if (i < 0) { i = 0; w = 0; }
+    if (i >= src - 1) { i = src - 1; w = 0; }
+    x0[d] = i; w1[d] = w;
+  }
+  return RGBID_OK;
+}
+
+int rgbid_loopfeat_plan_levels(int rows, int cols, int max_keypoints, int levels, float scale, int32_t* existing, int32_t* geometry, float* scale_l) {
+  LfPlan p;
+  const int r = lf_plan(rows, cols, max_keypoints, levels, scale, p);
+  if (r) return r;
+  if (existing) *existing = p.levels;
+  for (int l = 0; l < p.levels; ++l) {
+    if (geometry) {
+      const int v[5] = {p.rows[l], p.cols[l], p.cells_x[l], p.cells_y[l], p.per_cell[l]};
+      for (int i = 0; i < 5; ++i) geometry[5 * l + i] = v[i];
+    }
+    if (scale_l) scale_l[l] = p.s[l];
+  }
+  return RGBID_OK;
+}
+
 int rgbid_loopfeat_create(rgbid_loopfeat** out, rgbid_ctx* ctx, int rows, int cols, int max_keypoints) {
+  return rgbid_loopfeat_create_levels(out, ctx, rows, cols, max_keypoints, 1, 1.2f);
+}
+
+int rgbid_loopfeat_create_levels(rgbid_loopfeat** out, rgbid_ctx* ctx, int rows, int cols, int max_keypoints, int levels, float scale) {
   if (!out) return RGBID_E_INVALID;
   *out = nullptr;
-  if (!ctx || rows < 2 * BORDER + 1 || cols < 2 * BORDER + 1 || rows > 8192 || cols > 8192) return RGBID_E_INVALID;
-  const int cells_x = (cols + CELL - 1) / CELL, cells_y = (rows + CELL - 1) / CELL, cells = cells_x * cells_y;
-  if (max_keypoints < cells || max_keypoints > RGBID_LOOPFEAT_MAX_KEYPOINTS) return RGBID_E_INVALID;
+  LfPlan p;
+  if (!ctx || lf_plan(rows, cols, max_keypoints, levels, scale, p)) return RGBID_E_INVALID;
   (void)hipSetDevice(ctx->device);
   rgbid_loopfeat* f = new (std::nothrow) rgbid_loopfeat;
   if (!f) return RGBID_E_NOMEM;
   f->ctx = ctx;
-  const int per_cell = max_keypoints / cells;
-  f->g = LfGeom{rows, cols, cells_x, cells_y, per_cell < RGBID_LOOPFEAT_CELL_MAX ? per_cell : RGBID_LOOPFEAT_CELL_MAX, max_keypoints};
+  LfGeom& g = f->g;
+  g = LfGeom{rows, cols, p.levels, max_keypoints, 0, 0, 0, 0};
+  int ntab = 0;
+  for (int l = 0; l < p.levels; ++l) {
+    LfLevel& v = f->lv[l];
+    v = LfLevel{p.rows[l], p.cols[l], p.cells_x[l], p.cells_y[l], p.per_cell[l], p.s[l], l ? g.pyr_stride : 0, g.resp_stride, g.cells, g.slots,
+                (p.cols[l] + 15) / 16, f->tiles, f->dblocks};
+    const int px = p.rows[l] * p.cols[l], cells = v.cells_x * v.cells_y;
+    if (l) g.pyr_stride += (px + 3) / 4 * 4;   // each image starts on a word and ends before the next one
+    g.resp_stride += px; g.cells += cells; g.slots += cells * v.per_cell;
+    f->tiles += v.tiles_x * ((v.rows + 15) / 16);
+    f->dblocks += (cells * v.per_cell + 3) / 4;
+    f->tab_off[l][0] = ntab; f->tab_off[l][1] = ntab + (l ? v.cols : 0);
+    if (l) ntab += v.cols + v.rows;
+  }
   int8_t rot[RGBID_LOOPFEAT_DIRECTIONS * RGBID_LOOPFEAT_TESTS * 4];
   double bounds[32];
   rgbid_loopfeat_tables(nullptr, rot, bounds);
-  int r = lf_alloc((void**)&f->rotated, sizeof(rot));
+  int2* tabs = ntab ? new (std::nothrow) int2[ntab] : nullptr;
+  int32_t* tmp = ntab ? new (std::nothrow) int32_t[2 * 8192] : nullptr;
+  int r = (ntab && (!tabs || !tmp)) ? RGBID_E_NOMEM : RGBID_OK;
+  for (int l = 1; l < p.levels && !r; ++l)
+    for (int axis = 0; axis < 2; ++axis) {
+      const int src = axis ? p.rows[l - 1] : p.cols[l - 1], dst = axis ? p.rows[l] : p.cols[l];
+      rgbid_loopfeat_resize_table(src, dst, tmp, tmp + 8192);
+      for (int d = 0; d < dst; ++d) tabs[f->tab_off[l][axis] + d] = make_int2(tmp[d], tmp[8192 + d]);
+    }
+  if (!r) r = lf_alloc((void**)&f->rotated, sizeof(rot));
   if (!r) r = lf_alloc((void**)&f->bounds, sizeof(bounds));
+  if (!r) r = lf_alloc((void**)&f->levels_dev, sizeof(LfLevel) * MAXL);
+  if (!r && ntab) r = lf_alloc((void**)&f->tabs, sizeof(int2) * (size_t)ntab);
   if (!r) {   // pageable sources: the copies have left the host buffers when the calls return
     hipError_t e = hipMemcpy(f->rotated, rot, sizeof(rot), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(f->bounds, bounds, sizeof(bounds), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(f->levels_dev, f->lv, sizeof(LfLevel) * MAXL, hipMemcpyHostToDevice);
+    if (e == hipSuccess && ntab) e = hipMemcpy(f->tabs, tabs, sizeof(int2) * (size_t)ntab, hipMemcpyHostToDevice);
     if (e != hipSuccess) { (void)hipGetLastError(); r = (int)e; }
   }
+  delete[] tabs;
+  delete[] tmp;
   if (r) { rgbid_loopfeat_destroy(f); return r; }
   *out = f;
   return RGBID_OK;
@@ -562,7 +765,8 @@ int rgbid_loopfeat_destroy(rgbid_loopfeat* f) {
   if (!f) return RGBID_OK;
   (void)hipSetDevice(f->ctx->device);
   if (f->ctx->stream) (void)hipStreamSynchronize(f->ctx->stream);
-  for (void* p : {(void*)f->resp, (void*)f->staged, (void*)f->cell_counts, (void*)f->rotated, (void*)f->bounds})
+  for (void* p : {(void*)f->resp, (void*)f->staged, (void*)f->cell_counts, (void*)f->pyr, (void*)f->rotated, (void*)f->bounds, (void*)f->levels_dev,
+                  (void*)f->tabs})
     if (p) (void)hipFree(p);
   for (hipEvent_t e : f->ev) if (e) (void)hipEventDestroy(e);
   (void)hipGetLastError();
@@ -571,49 +775,81 @@ int rgbid_loopfeat_destroy(rgbid_loopfeat* f) {
 }
 
 int rgbid_loopfeat_layout(const rgbid_loopfeat* f, int* cells_x, int* cells_y, int* per_cell) {
-  if (!f) return RGBID_E_INVALID;
-  if (cells_x) *cells_x = f->g.cells_x;
-  if (cells_y) *cells_y = f->g.cells_y;
-  if (per_cell) *per_cell = f->g.per_cell;
+  return rgbid_loopfeat_level_layout(f, 0, nullptr, nullptr, cells_x, cells_y, per_cell, nullptr);
+}
+
+int rgbid_loopfeat_level_layout(const rgbid_loopfeat* f, int level, int* rows_l, int* cols_l, int* cells_x, int* cells_y, int* per_cell,
+                                float* scale_l) {
+  if (!f || level < 0 || level >= f->g.levels) return RGBID_E_INVALID;
+  const LfLevel& v = f->lv[level];
+  if (rows_l) *rows_l = v.rows;
+  if (cols_l) *cols_l = v.cols;
+  if (cells_x) *cells_x = v.cells_x;
+  if (cells_y) *cells_y = v.cells_y;
+  if (per_cell) *per_cell = v.per_cell;
+  if (scale_l) *scale_l = v.s;
+  return RGBID_OK;
+}
+
+int rgbid_loopfeat_pyramid(rgbid_loopfeat* f, const uint8_t* grey_dev, int n, int level, uint8_t* out_dev) {
+  if (!f || n < 0 || n > 65535 || level < 0 || level >= f->g.levels) return RGBID_E_INVALID;
+  if (n == 0) return RGBID_OK;
+  if (!grey_dev || !out_dev) return RGBID_E_INVALID;
+  (void)hipSetDevice(f->ctx->device);
+  hipStream_t s = f->ctx->stream;
+  const LfGeom& g = f->g;
+  if (level == 0) {
+    RGBID_HIPC(hipMemcpyAsync(out_dev, grey_dev, (size_t)n * g.rows * g.cols, hipMemcpyDeviceToDevice, s));
+    return RGBID_OK;
+  }
+  const int r = lf_reserve(f, n);
+  if (r) return r;
+  lf_build_pyramid(f, grey_dev, n, level);
+  RGBID_HIPC(hipGetLastError());
+  const size_t px = (size_t)f->lv[level].rows * f->lv[level].cols;
+  RGBID_HIPC(hipMemcpy2DAsync(out_dev, px, f->pyr + f->lv[level].img_off, (size_t)g.pyr_stride, px, (size_t)n, hipMemcpyDeviceToDevice, s));
   return RGBID_OK;
 }
 
 int rgbid_loopfeat_extract(rgbid_loopfeat* f, const uint8_t* grey_dev, const float* invdepth_dev, int n, const float K[4],
                            rgbid_loopfeat_kp* kps_dev, int32_t* counts_dev) {
+  return rgbid_loopfeat_extract_levels(f, grey_dev, invdepth_dev, n, K, kps_dev, counts_dev, nullptr);
+}
+
+int rgbid_loopfeat_extract_levels(rgbid_loopfeat* f, const uint8_t* grey_dev, const float* invdepth_dev, int n, const float K[4],
+                                  rgbid_loopfeat_kp* kps_dev, int32_t* counts_dev, rgbid_loopfeat_aux* aux_dev) {
   if (!f || n < 0 || n > 65535 || !K) return RGBID_E_INVALID;
   if (n == 0) return RGBID_OK;
-  if (!grey_dev || !invdepth_dev || !kps_dev || !counts_dev || (((uintptr_t)kps_dev) & 7)) return RGBID_E_INVALID;
+  if (!grey_dev || !invdepth_dev || !kps_dev || !counts_dev || (((uintptr_t)kps_dev) & 7) || (((uintptr_t)aux_dev) & 3)) return RGBID_E_INVALID;
   for (int i = 0; i < 4; ++i) if (!std::isfinite(K[i])) return RGBID_E_INVALID;
   if (K[0] == 0.f || K[1] == 0.f) return RGBID_E_INVALID;
   (void)hipSetDevice(f->ctx->device);
   hipStream_t s = f->ctx->stream;
   const LfGeom g = f->g;
-  const int cells = g.cells_x * g.cells_y;
-  if (n > f->cap_kf) {
-    RGBID_HIPC(hipStreamSynchronize(s));
-    for (void* p : {(void*)f->resp, (void*)f->staged, (void*)f->cell_counts}) if (p) (void)hipFree(p);
-    f->resp = nullptr; f->staged = nullptr; f->cell_counts = nullptr; f->cap_kf = 0;
-    int r = lf_alloc((void**)&f->resp, sizeof(float) * (size_t)n * g.rows * g.cols);
-    if (!r) r = lf_alloc((void**)&f->staged, sizeof(LfStaged) * (size_t)n * cells * g.per_cell);
-    if (!r) r = lf_alloc((void**)&f->cell_counts, sizeof(int) * (size_t)n * cells);
-    if (r) return r;
-    f->cap_kf = n;
-  }
+  const int r = lf_reserve(f, n);
+  if (r) return r;
   LfKinv Ki;
   rgbid_cloud_kinv(K, Ki.m);
   const float scale = 1.f / (4 * 7 * 255.f);
   const float scale4 = ((scale * scale) * scale) * scale;
-  f->timed[0] = false;
+  f->timed[0] = false; f->timed[3] = false;
+  if (g.levels > 1) {
+    f->mark(8);
+    lf_build_pyramid(f, grey_dev, n, g.levels - 1);
+    f->mark(9);
+  }
   f->mark(0);
   RGBID_HIPC(hipMemsetAsync(kps_dev, 0, sizeof(rgbid_loopfeat_kp) * (size_t)n * g.max_kp, s));
-  hipLaunchKernelGGL(k_lf_response, dim3((g.cols + 15) / 16, (g.rows + 15) / 16, n), dim3(LT), 0, s, grey_dev, g, scale4, f->resp);
+  if (aux_dev) RGBID_HIPC(hipMemsetAsync(aux_dev, 0, sizeof(rgbid_loopfeat_aux) * (size_t)n * g.max_kp, s));
+  hipLaunchKernelGGL(k_lf_response, dim3(f->tiles, n), dim3(LT), 0, s, grey_dev, f->pyr, g, f->levels_dev, scale4, f->resp);
   f->mark(1);
-  hipLaunchKernelGGL(k_lf_select, dim3(cells, n), dim3(LT), 0, s, f->resp, invdepth_dev, g, f->staged, f->cell_counts);
+  hipLaunchKernelGGL(k_lf_select, dim3(g.cells, n), dim3(LT), 0, s, f->resp, invdepth_dev, g, f->levels_dev, f->staged, f->cell_counts);
   f->mark(2);
-  hipLaunchKernelGGL(k_lf_describe, dim3((cells * g.per_cell + 3) / 4, n), dim3(LT), 0, s, grey_dev, invdepth_dev, g, Ki, f->staged,
-                     f->cell_counts, f->rotated, f->bounds, kps_dev, counts_dev);
+  hipLaunchKernelGGL(k_lf_describe, dim3(f->dblocks, n), dim3(LT), 0, s, grey_dev, f->pyr, invdepth_dev, g, f->levels_dev, Ki, f->staged,
+                     f->cell_counts, f->rotated, f->bounds, kps_dev, counts_dev, aux_dev);
   f->mark(3);
   f->timed[0] = f->timing;
+  f->timed[3] = f->timing && g.levels > 1;
   RGBID_HIPC(hipGetLastError());
   return RGBID_OK;
 }
@@ -654,6 +890,17 @@ int rgbid_loopfeat_ransac(rgbid_loopfeat* f, const rgbid_loopfeat_kp* kps_dev, i
   f->mark(7);
   f->timed[2] = f->timing;
   RGBID_HIPC(hipGetLastError());
+  return RGBID_OK;
+}
+
+int rgbid_loopfeat_timing_pyramid(rgbid_loopfeat* f, float* ms) {
+  if (!f || !ms) return RGBID_E_INVALID;
+  (void)hipSetDevice(f->ctx->device);
+  *ms = 0.f;
+  if (f->timed[3]) {
+    RGBID_HIPC(hipEventSynchronize(f->ev[9]));
+    RGBID_HIPC(hipEventElapsedTime(ms, f->ev[8], f->ev[9]));
+  }
   return RGBID_OK;
 }
 

@@ -2,7 +2,7 @@
 2-NN Hamming matching with the ratio test, the appearance proposal, and the 3-point RANSAC over 3-D correspondences that starts the dense
 verifier (LoopCloser::detectLoopClosures / computeRANSACTrafo3D, src/loop_closer.cpp:193-716).
 
-    lf = LoopFeat(ctx, rows, cols)
+    lf = LoopFeat(ctx, rows, cols)                             # levels=8, scale=1.2: features over a scale pyramid
     feats = lf.extract(grey [n, rows, cols] uint8, invdepth [n, rows, cols] float32, K)
     pairs, scores = propose(lf, feats)                         # uses no pose
     res = lf.ransac(feats, pairs, *lf.match(feats, pairs))     # qTc_ini, best iteration, inliers, mask per pair
@@ -20,14 +20,19 @@ from ._lib import check
 KP_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("response", "<f4"), ("direction", "<i4"), ("desc", "u1", (32,)), ("X", "<f8", (3,)),
                      ("cov", "<f8", (6,))])
 assert KP_DTYPE.itemsize == 120
+AUX_DTYPE = np.dtype([("px", "<f4"), ("py", "<f4"), ("lx", "<i2"), ("ly", "<i2"), ("level", "<i4")])
+assert AUX_DTYPE.itemsize == 16
 MATCH_DTYPE = np.dtype([("query", "<i4"), ("train", "<i4"), ("distance", "<i4"), ("second", "<i4")])
 assert MATCH_DTYPE.itemsize == 16
 
 CELL, CELL_MAX, BORDER, DIRECTIONS, TESTS = 32, 64, 16, 32, 256
-MAX_KEYPOINTS, MAX_ITERS = 1536, 4096
+MAX_KEYPOINTS, MAX_ITERS, MAX_LEVELS = 1536, 4096, 8
 EXPORTS = ["rgbid_loopfeat_create", "rgbid_loopfeat_destroy", "rgbid_loopfeat_tables", "rgbid_loopfeat_layout", "rgbid_loopfeat_extract",
-           "rgbid_loopfeat_match", "rgbid_loopfeat_ransac", "rgbid_loopfeat_timing"]
+           "rgbid_loopfeat_match", "rgbid_loopfeat_ransac", "rgbid_loopfeat_timing", "rgbid_loopfeat_create_levels",
+           "rgbid_loopfeat_plan_levels", "rgbid_loopfeat_resize_table", "rgbid_loopfeat_level_layout", "rgbid_loopfeat_extract_levels",
+           "rgbid_loopfeat_pyramid", "rgbid_loopfeat_timing_pyramid"]
 STAGES = ("response", "select", "describe", "match", "ransac")
+LEVELS, SCALE = 8, 1.2         # the reference's FEATURE_EXTRACTOR LEVELS and SCALE; the default here is one level
 
 # the reference's settings (config_data/visodoRGBDconfig.ini, loop_closer.cpp)
 MATCH_RATIO = 0.75             # MATCH_SCORE_RATIO_THRESHOLD
@@ -81,11 +86,67 @@ def layout(rows, cols, max_keypoints):
     return cx, cy, min(max_keypoints // (cx * cy), CELL_MAX)
 
 
-class Features:
-    """records [n, max_keypoints, 120] uint8 and counts [n] int32 on the device"""
+def layout_levels(rows, cols, max_keypoints, levels=1, scale=SCALE):
+    """the levels of include/rgbid_loopfeat.h that exist -> [(rows_l, cols_l, cells_x, cells_y, per_cell, s_l)]; ValueError for what the
+    library refuses (rgbid_loopfeat_plan_levels is the same on the C side)"""
+    f32 = np.float32
+    rows, cols, max_keypoints, levels, scale = int(rows), int(cols), int(max_keypoints), int(levels), f32(scale)
+    if rows < 2 * BORDER + 1 or cols < 2 * BORDER + 1 or rows > 8192 or cols > 8192:
+        raise ValueError(f"rows, cols must be {2 * BORDER + 1} .. 8192, got {rows} x {cols}")
+    if not 1 <= levels <= MAX_LEVELS or not (scale > f32(1.0) and scale <= f32(2.0)):
+        raise ValueError(f"levels must be 1 .. {MAX_LEVELS} and 1 < scale <= 2, got {levels}, {scale}")
+    if not 1 <= max_keypoints <= MAX_KEYPOINTS:
+        raise ValueError(f"max_keypoints must be 1 .. {MAX_KEYPOINTS}, got {max_keypoints}")
+    geo = []
+    for l in range(levels):
+        s = f32(math.pow(float(scale), float(l)))
+        c, r = int((f32(cols) + f32(0.5)) / s), int((f32(rows) + f32(0.5)) / s)
+        if r < 2 * BORDER + 1 or c < 2 * BORDER + 1:
+            break
+        geo.append((r, c, (c + CELL - 1) // CELL, (r + CELL - 1) // CELL, s))
+    sd = float(scale)
+    r = 1.0 / (sd * sd)
+    rL = 1.0
+    for _ in geo:
+        rL *= r
+    out, rl, slots = [], 1.0, 0
+    for rows_l, cols_l, cx, cy, s in geo:
+        n = int(math.floor(float(max_keypoints) * (((1.0 - r) * rl) / (1.0 - rL))))
+        k = min(max(n // (cx * cy), 1), CELL_MAX)
+        out.append((rows_l, cols_l, cx, cy, k, float(s)))
+        slots += cx * cy * k
+        rl *= r
+    if slots > max_keypoints:
+        raise ValueError(f"{len(out)} levels of {rows} x {cols} need {slots} keypoint slots (one per cell at least), max_keypoints is {max_keypoints}")
+    return out
 
-    def __init__(self, kps, counts):
-        self.kps, self.counts = kps, counts
+
+def plan_levels(rows, cols, max_keypoints, levels=1, scale=SCALE):
+    """rgbid_loopfeat_plan_levels: the library's own answer to layout_levels, the same tuples; RgbidError for its refusals.  Needs no device."""
+    L = _lib.lib()
+    L.rgbid_loopfeat_plan_levels.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+    n = C.c_int32(0)
+    geo = np.zeros((MAX_LEVELS, 5), np.int32); s = np.zeros(MAX_LEVELS, np.float32)
+    check(L.rgbid_loopfeat_plan_levels(int(rows), int(cols), int(max_keypoints), int(levels), C.c_float(float(scale)), C.byref(n),
+                                       geo.ctypes.data_as(C.c_void_p), s.ctypes.data_as(C.c_void_p)))
+    return [tuple(int(v) for v in geo[l]) + (float(s[l]),) for l in range(n.value)]
+
+
+def resize_table(src, dst):
+    """rgbid_loopfeat_resize_table -> (x0 int32 [dst], w1 int32 [dst]) of one axis.  Needs no device."""
+    L = _lib.lib()
+    L.rgbid_loopfeat_resize_table.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    x0 = np.zeros(max(int(dst), 0), np.int32); w1 = np.zeros(max(int(dst), 0), np.int32)
+    check(L.rgbid_loopfeat_resize_table(int(src), int(dst), x0.ctypes.data_as(C.c_void_p), w1.ctypes.data_as(C.c_void_p)))
+    return x0, w1
+
+
+class Features:
+    """records [n, max_keypoints, 120] uint8 and counts [n] int32 on the device; aux [n, max_keypoints, 16] uint8 (level, level pixel and
+    float position of each record) when the extraction was asked for it, else None"""
+
+    def __init__(self, kps, counts, aux=None):
+        self.kps, self.counts, self.aux = kps, counts, aux
 
     def __len__(self):
         return int(self.kps.shape[0])
@@ -94,23 +155,39 @@ class Features:
         """-> (structured KP_DTYPE [n, max_keypoints], counts [n])"""
         return self.kps.cpu().numpy().view(KP_DTYPE).reshape(self.kps.shape[0], self.kps.shape[1]), self.counts.cpu().numpy()
 
+    def numpy_aux(self):
+        """-> structured AUX_DTYPE [n, max_keypoints]"""
+        if self.aux is None:
+            raise ValueError("these features were extracted without aux records (extract(..., aux=True))")
+        return self.aux.cpu().numpy().view(AUX_DTYPE).reshape(self.aux.shape[0], self.aux.shape[1])
+
 
 class LoopFeat:
-    """Feature extractor, matcher and RANSAC for keyframes of rows x cols pixels, on the context's stream."""
+    """Feature extractor, matcher and RANSAC for keyframes of rows x cols pixels, on the context's stream.  levels > 1: features over a
+    pyramid of that many images at `scale` between neighbours (self.levels lists those that exist), so that a revisit at another distance
+    still matches; levels = 1 is the single-level extractor."""
 
-    def __init__(self, ctx, rows, cols, max_keypoints=1000):
+    def __init__(self, ctx, rows, cols, max_keypoints=1000, levels=1, scale=SCALE):
         self.ctx, self.rows, self.cols, self.max_keypoints = ctx, int(rows), int(cols), int(max_keypoints)
-        self.cells_x, self.cells_y, self.per_cell = layout(rows, cols, max_keypoints)
+        if int(levels) == 1:
+            self.cells_x, self.cells_y, self.per_cell = layout(rows, cols, max_keypoints)
+        self.levels = layout_levels(rows, cols, max_keypoints, levels, scale)
+        _, _, self.cells_x, self.cells_y, self.per_cell, _ = self.levels[0]
+        self.scale = float(np.float32(scale))
         self.L = L = _lib.lib()
         vp, ci = C.c_void_p, C.c_int
-        L.rgbid_loopfeat_create.argtypes = [vp, vp, ci, ci, ci]
+        L.rgbid_loopfeat_create_levels.argtypes = [vp, vp, ci, ci, ci, ci, C.c_float]
         L.rgbid_loopfeat_destroy.argtypes = [vp]
-        L.rgbid_loopfeat_extract.argtypes = [vp, vp, vp, ci, vp, vp, vp]
+        L.rgbid_loopfeat_extract_levels.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp]
+        L.rgbid_loopfeat_pyramid.argtypes = [vp, vp, ci, ci, vp]
+        L.rgbid_loopfeat_level_layout.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp]
+        L.rgbid_loopfeat_timing_pyramid.argtypes = [vp, vp]
         L.rgbid_loopfeat_match.argtypes = [vp, vp, vp, ci, vp, ci, C.c_float, vp, vp]
         L.rgbid_loopfeat_ransac.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, ci, C.c_double, vp, vp, vp]
         L.rgbid_loopfeat_timing.argtypes = [vp, ci, vp]
         self._h = C.c_void_p()
-        check(L.rgbid_loopfeat_create(C.byref(self._h), ctx._h, self.rows, self.cols, self.max_keypoints))
+        check(L.rgbid_loopfeat_create_levels(C.byref(self._h), ctx._h, self.rows, self.cols, self.max_keypoints, int(levels),
+                                             C.c_float(self.scale)))
         ctx._dependents.add(self)
         self.dev = f"cuda:{ctx.device}"
 
@@ -137,8 +214,35 @@ class LoopFeat:
         check(self.L.rgbid_loopfeat_timing(self._h, int(enable), ms))
         return dict(zip(STAGES, ms[:]))
 
-    def extract(self, grey, invdepth, K):
-        """grey [n, rows, cols] uint8 and invdepth [n, rows, cols] float32 (numpy or tensors), K = (fx, fy, cx, cy) -> Features.  Synchronises."""
+    def timing_pyramid(self):
+        """the device ms the last timed extract spent on its pyramid (0.0 with one level)"""
+        ms = C.c_float(0.0)
+        check(self.L.rgbid_loopfeat_timing_pyramid(self._h, C.byref(ms)))
+        return float(ms.value)
+
+    def level_layout(self, level):
+        """rgbid_loopfeat_level_layout -> (rows_l, cols_l, cells_x, cells_y, per_cell, s_l) as the library holds it"""
+        v = [C.c_int(0) for _ in range(5)]
+        s = C.c_float(0.0)
+        check(self.L.rgbid_loopfeat_level_layout(self._h, int(level), *[C.byref(x) for x in v], C.byref(s)))
+        return tuple(x.value for x in v) + (float(s.value),)
+
+    def pyramid(self, grey, level):
+        """level `level` of the pyramid of grey [n, rows, cols] uint8 -> [n, rows_l, cols_l] uint8 on the device.  Synchronises."""
+        g = self._dev(grey, torch.uint8)
+        assert g.dim() == 3 and tuple(g.shape[1:]) == (self.rows, self.cols), g.shape
+        if not 0 <= int(level) < len(self.levels):
+            raise ValueError(f"level {level} does not exist (levels 0 .. {len(self.levels) - 1})")
+        n = int(g.shape[0])
+        out = torch.zeros((n, self.levels[level][0], self.levels[level][1]), dtype=torch.uint8, device=self.dev)
+        self.ctx.wait_torch_stream()
+        check(self.L.rgbid_loopfeat_pyramid(self._h, g.data_ptr() if n else None, n, int(level), out.data_ptr() if n else None))
+        self.ctx.sync()
+        return out
+
+    def extract(self, grey, invdepth, K, aux=False):
+        """grey [n, rows, cols] uint8 and invdepth [n, rows, cols] float32 (numpy or tensors), K = (fx, fy, cx, cy) -> Features (with the
+        16-byte aux records when aux is set).  Synchronises."""
         g, w = self._dev(grey, torch.uint8), self._dev(invdepth, torch.float32)
         assert g.dim() == 3 and tuple(g.shape[1:]) == (self.rows, self.cols) and g.shape == w.shape, (g.shape, w.shape)
         n = int(g.shape[0])
@@ -146,10 +250,12 @@ class LoopFeat:
         counts = torch.zeros((n,), dtype=torch.int32, device=self.dev)
         Kc = (C.c_float * 4)(*[float(v) for v in K])
         self.ctx.wait_torch_stream()
-        check(self.L.rgbid_loopfeat_extract(self._h, g.data_ptr() if n else None, w.data_ptr() if n else None, n, Kc,
-                                            kps.data_ptr() if n else None, counts.data_ptr() if n else None))
+        ax = torch.empty((n, self.max_keypoints, 16), dtype=torch.uint8, device=self.dev) if aux else None
+        check(self.L.rgbid_loopfeat_extract_levels(self._h, g.data_ptr() if n else None, w.data_ptr() if n else None, n, Kc,
+                                                   kps.data_ptr() if n else None, counts.data_ptr() if n else None,
+                                                   ax.data_ptr() if (aux and n) else None))
         self.ctx.sync()
-        return Features(kps, counts)
+        return Features(kps, counts, ax)
 
     def _pairs(self, pairs):
         p = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
@@ -274,17 +380,17 @@ def gate(kq, kc, matches, mask, rows, cols, min_inliers=MIN_INLIERS, min_hull=MI
 
 
 def appearance_loops(ctx, keyframes, K, grey=None, max_keypoints=1000, min_separation=3, score_threshold=SCORE_THRESHOLD, per_query=(2, 2),
-                     batch=64):
+                     batch=64, levels=1, scale=SCALE):
     """features of all exported keyframes, `propose`, RANSAC and its gates.  keyframes: [dict(frame, depthinv, colors)] in export order.
     -> (pairs [(q, c)] that passed, guesses [(R, t)] = qTc_ini of each, report [dict(query, candidate, score, matches, inliers, hull_query,
-    hull_candidate, ransac_ok)] over every proposed pair)"""
+    hull_candidate, ransac_ok)] over every proposed pair).  levels, scale: the feature pyramid (LoopFeat); the reference runs 8 levels at 1.2."""
     from .posegraph import grey_from_colors
     if len(keyframes) < 2:
         return [], [], []
     rows, cols = keyframes[0]["depthinv"].shape
     if grey is None:
         grey = [grey_from_colors(k["colors"]) for k in keyframes]
-    lf = LoopFeat(ctx, rows, cols, max_keypoints)
+    lf = LoopFeat(ctx, rows, cols, max_keypoints, levels, scale)
     try:
         parts = [lf.extract(np.stack(grey[s:s + batch]), np.stack([k["depthinv"] for k in keyframes[s:s + batch]]), K)
                  for s in range(0, len(keyframes), batch)]   # records do not depend on the batch

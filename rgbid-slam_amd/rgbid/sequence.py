@@ -29,7 +29,8 @@ def track_chunked(ctx, depth, rgb, n_chunks, K, group=None, comm=None, cloud=Non
     when every keyframe-level component is anchored, else single level (a chunk's keyframe chain ends at its last export, so chunked runs
     without seam-crossing loops run single level).  The returned trajectory (and the cloud) are then the optimised ones; what ran is in
     track_chunked.last_optimise (mode, status, chi2, loops).  It needs the whole run on one rank.  loop_options: keyword arguments of
-    rgbid.posegraph.loop_constraints (radius, angle, gate, min_separation)."""
+    rgbid.posegraph.loop_constraints (radius, angle, gate, min_separation) and, with loops = "appearance", of rgbid.loopfeat.appearance_loops
+    (max_keypoints, score_threshold, per_query, and levels / scale of the feature pyramid: one level by default, the reference runs 8 at 1.2)."""
     if cloud not in (None, "novel", "all"):
         raise ValueError(f"cloud must be None, 'novel' or 'all', not {cloud!r}")
     if optimise not in (None, "auto", "multilevel", "single"):

@@ -12,7 +12,11 @@ warm-up; one JSON line per case with the microseconds per stage and a byte / ope
     ransac, P pairs of m matches, I iterations: I m votes of 2 errors, about 230 FP64 operations per error; 144 m bytes staged per pass of
       256 hypotheses; peak taken as 78.6 TFLOP/s FP64 vector
 
-    python tools/loopfeat_bench.py [--keyframes 64 256] [--pairs 64 1024] [--reps 5]
+    with --levels N --scale S (a feature pyramid): the pyramid as a stage of its own (1.7 B per destination pixel: 4 taps of which about
+      1.44 source bytes are new, 1 written, levels 1 .. L - 1 hold about 2.1 x the pixels of level 0 at 1.2), the other feature stages over
+      all levels' pixels, features per keyframe, and the match stage at the keypoint counts the levels really yield
+
+    python tools/loopfeat_bench.py [--keyframes 64 256] [--pairs 64 1024] [--reps 5] [--levels 8 --scale 1.2]
 """
 import argparse
 import json
@@ -41,14 +45,17 @@ def textured(r, rows, cols):
 
 
 def median_ms(lf, fn, stages, reps, warmup):
+    """-> ({stage: median ms}, {stage: (min, max) ms}); the stage "pyramid" comes from the library's own call"""
     out = {s: [] for s in stages}
     for k in range(warmup + reps):
         fn()
         ms = lf.timing(True)
+        if "pyramid" in out:
+            ms["pyramid"] = lf.timing_pyramid()
         if k >= warmup:
             for s in stages:
                 out[s].append(ms[s])
-    return {s: float(np.median(v)) for s, v in out.items()}
+    return {s: float(np.median(v)) for s, v in out.items()}, {s: (float(min(v)), float(max(v))) for s, v in out.items()}
 
 
 def main():
@@ -60,6 +67,8 @@ def main():
     ap.add_argument("--rows", type=int, default=480)
     ap.add_argument("--cols", type=int, default=640)
     ap.add_argument("--max-keypoints", type=int, default=1000)
+    ap.add_argument("--levels", type=int, default=1, help="pyramid levels of the feature extractor (1 .. 8)")
+    ap.add_argument("--scale", type=float, default=1.2, help="scale between neighbouring levels")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a HIP device (there is no CPU path)"
     from rgbid import device
@@ -68,7 +77,9 @@ def main():
     K = (525.0 * cols / 640, 525.0 * rows / 480, cols / 2 - 0.5, rows / 2 - 0.5)
     r = np.random.default_rng(0)
     ctx = device.Context(0)
-    lf = LF.LoopFeat(ctx, rows, cols, mk)
+    lf = LF.LoopFeat(ctx, rows, cols, mk, args.levels, args.scale)
+    px_all = sum(l[0] * l[1] for l in lf.levels)           # pixels of all levels
+    stages = (("pyramid",) if len(lf.levels) > 1 else ()) + ("response", "select", "describe")
     lf.timing(True)
     base = [textured(r, rows, cols) for _ in range(8)]
     for n in args.keyframes:
@@ -76,16 +87,20 @@ def main():
         grey = torch.roll(grey, shifts=3, dims=2) if n % 2 else grey
         w = torch.full((n, rows, cols), 0.8, dtype=torch.float32, device="cuda")
         holder = {}
-        ms = median_ms(lf, lambda: holder.__setitem__("f", lf.extract(grey, w, K)), ("response", "select", "describe"), args.reps, args.warmup)
+        ms, spread = median_ms(lf, lambda: holder.__setitem__("f", lf.extract(grey, w, K)), stages, args.reps, args.warmup)
         feats = holder["f"]
         kp = float(feats.counts.float().mean())
-        px = rows * cols
-        model = dict(response_bytes=n * px * (2.25 + 4), select_bytes=n * px * 8, describe_bytes=n * kp * (1089 + 120))
-        print(json.dumps(dict(case="features", keyframes=n, rows=rows, cols=cols, keypoints_mean=kp,
-                              us={k: 1e3 * v for k, v in ms.items()}, us_per_keyframe=1e3 * sum(ms.values()) / n,
+        px = px_all
+        model = dict(pyramid_bytes=n * (px_all - rows * cols) * 1.7, response_bytes=n * px * (2.25 + 4), select_bytes=n * px * 8,
+                     describe_bytes=n * kp * (1089 + 120))
+        print(json.dumps(dict(case="features", keyframes=n, rows=rows, cols=cols, levels=len(lf.levels), scale=args.scale,
+                              pixels_over_level0=px_all / (rows * cols), keypoints_mean=kp,
+                              us={k: 1e3 * v for k, v in ms.items()}, us_min_max={k: [1e3 * a, 1e3 * b] for k, (a, b) in spread.items()},
+                              us_per_keyframe=1e3 * sum(ms.values()) / n,
+                              us_per_keyframe_by_stage={k: 1e3 * v / n for k, v in ms.items()},
                               frac_of_8TBps={s: model[s + "_bytes"] / (ms[s] * 1e-3) / PEAK_BPS for s in ms})))
         pairs = LF.all_pairs(n, 3)
-        ms = median_ms(lf, lambda: lf.match(feats, pairs, lists=False), ("match",), args.reps, args.warmup)
+        ms, _ = median_ms(lf, lambda: lf.match(feats, pairs, lists=False), ("match",), args.reps, args.warmup)
         ops = len(pairs) * 12.0 * kp * kp
         print(json.dumps(dict(case="match_all_pairs", keyframes=n, pairs=len(pairs), keypoints_mean=kp, us=1e3 * ms["match"],
                               int_ops=ops, frac_of_int_peak=ops / (ms["match"] * 1e-3) / INT_OPS, bytes=len(pairs) * 64.0 * kp)))
@@ -94,7 +109,7 @@ def main():
     for P in args.pairs:
         pairs = [(int(q), int(c)) for q, c in zip(r.integers(1, n, P), r.integers(0, n, P))]
         m, mc = lf.match(feats, pairs)
-        ms = median_ms(lf, lambda: lf.ransac(feats, pairs, m, mc), ("ransac",), args.reps, args.warmup)
+        ms, _ = median_ms(lf, lambda: lf.ransac(feats, pairs, m, mc), ("ransac",), args.reps, args.warmup)
         mm = float(mc.float().mean())
         flops = P * iters * mm * 2 * 230.0
         print(json.dumps(dict(case="ransac", pairs=P, iterations=iters, matches_mean=mm, us=1e3 * ms["ransac"], fp64_flops=flops,

@@ -44,6 +44,10 @@ def main():
     ap.add_argument("--loops", default=None, choices=["auto", "appearance"],
                     help="with --optimise: add loop constraints from the dense keyframe verifier; auto: candidates by distance on the trajectory, "
                          "appearance: by binary features, Hamming matching and RANSAC (DESIGN.md section 13)")
+    ap.add_argument("--loop-levels", type=int, default=1, metavar="N",
+                    help="with --loops appearance: extract the features over a pyramid of N levels (1 .. 8; the reference uses 8), so that a "
+                         "revisit at another distance still matches")
+    ap.add_argument("--loop-scale", type=float, default=1.2, metavar="S", help="with --loop-levels: the scale between neighbouring levels (1 < S <= 2)")
     ap.add_argument("--K", type=float, nargs=4, default=[525.0, 525.0, 319.5, 239.5], help="fx fy cx cy (tools/evaluation.cpp:64-67)")
     args = ap.parse_args()
     if args.voxel is not None and not args.cloud:
@@ -85,7 +89,11 @@ def main():
             sys.stderr.write(f"[track_dataset] WARNING: C-ABI RCCL communicator failed ({e}); gathering through torch.distributed\n")
     if args.loops and not args.optimise:
         ap.error("--loops needs --optimise")
+    if (args.loop_levels != 1 or args.loop_scale != 1.2) and args.loops != "appearance":
+        ap.error("--loop-levels / --loop-scale need --loops appearance")
     opt = dict(optimise=args.optimise, loops=args.loops) if args.optimise else {}
+    if args.loops == "appearance" and (args.loop_levels != 1 or args.loop_scale != 1.2):
+        opt["loop_options"] = dict(levels=args.loop_levels, scale=args.loop_scale)
     if args.cloud:
         R, t, ranges, pc = sequence.track_chunked(ctx, depth, rgb, args.chunks, tuple(args.K), comm=comm, use_graph=0,
                                                   cloud="all" if args.cloud_all else "novel", **opt)
