@@ -4,7 +4,7 @@
 // returning, which is the contract of the reference's bridge (cudaStreamSynchronize after every launch).
 // There is NO CPU fallback: without a HIP device every entry point returns an error.
 #include "../../include/rgbid.h"
-#include "ctx.h"
+#include "hip_host.h"
 #include "kernels.h"
 #include "guard_band.h"
 
@@ -13,14 +13,6 @@
 #include <new>
 
 using namespace rgbid;
-
-// a failing HIP call is reported through the return value; the runtime's sticky "last error" is cleared so that the caller's
-// other HIP users (e.g. a framework sharing the process) do not trip over it later
-#define RGBID_HIP(expr)                                             \
-  do {                                                              \
-    hipError_t e_ = (expr);                                         \
-    if (e_ != hipSuccess) { (void)hipGetLastError(); return (int)e_; } \
-  } while (0)
 
 extern "C" {
 
@@ -83,13 +75,13 @@ int rgbid_ctx_create(rgbid_ctx** out, int device, void* stream) {
   if (stream) c->stream = (hipStream_t)stream;
   else {
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { delete c; return (int)e; }
+    if (e != hipSuccess) { delete c; return hip_status(e); }
   }
-  hipError_t e = hipEventCreate(&c->ev0);
-  if (e == hipSuccess) e = hipEventCreate(&c->ev1);
-  if (e == hipSuccess) e = hipMalloc(&c->small_dev, ctx_small_bytes);
-  if (e == hipSuccess) e = hipHostMalloc(&c->small_host, ctx_small_bytes, hipHostMallocDefault);
-  if (e != hipSuccess) { rgbid_ctx_destroy(c); return (int)e; }
+  int r = hip_status(hipEventCreate(&c->ev0));
+  if (!r) r = hip_status(hipEventCreate(&c->ev1));
+  if (!r) r = hip_alloc(&c->small_dev, ctx_small_bytes);
+  if (!r) r = hip_alloc_host(&c->small_host, ctx_small_bytes);
+  if (r) { rgbid_ctx_destroy(c); return r; }
   *out = c;
   return RGBID_OK;
 }
@@ -239,10 +231,7 @@ int rgbid_mem_info(size_t* f, size_t* t) { if (!f || !t) return RGBID_E_INVALID;
 int rgbid_malloc(void** p, size_t bytes) {
   if (!p) return RGBID_E_INVALID;
   *p = nullptr;
-  if (bytes == 0) return RGBID_OK;
-  hipError_t e = hipMalloc(p, bytes);
-  if (e == hipErrorOutOfMemory) return RGBID_E_NOMEM;
-  return (int)e;
+  return bytes ? hip_alloc(p, bytes) : RGBID_OK;
 }
 int rgbid_malloc_pitch(void** p, size_t* step, size_t width_bytes, size_t rows) {
   if (!p || !step) return RGBID_E_INVALID;
@@ -254,10 +243,7 @@ int rgbid_free(void* p) { if (p) RGBID_HIP(hipFree(p)); return RGBID_OK; }
 int rgbid_malloc_host(void** p, size_t bytes) {
   if (!p) return RGBID_E_INVALID;
   *p = nullptr;
-  if (bytes == 0) return RGBID_OK;
-  hipError_t e = hipHostMalloc(p, bytes, hipHostMallocDefault);
-  if (e != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return e == hipErrorOutOfMemory ? RGBID_E_NOMEM : (int)e; }
-  return RGBID_OK;
+  return bytes ? hip_alloc_host(p, bytes) : RGBID_OK;
 }
 int rgbid_free_host(void* p) { if (p) RGBID_HIP(hipHostFree(p)); return RGBID_OK; }
 
@@ -302,16 +288,13 @@ struct Timed {  // cudaTimer (device.hpp:83-106) with hipEvents on the context's
   float* ms;
   Timed(rgbid_ctx* c_, float* ms_) : c(c_), ms(ms_) { if (ms) hipEventRecord(c->ev0, c->stream); }
   int finish() {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
+    RGBID_HIP(hipGetLastError());
     if (ms) {
       hipEventRecord(c->ev1, c->stream);
-      e = hipEventSynchronize(c->ev1);
-      if (e != hipSuccess) return (int)e;
+      RGBID_HIP(hipEventSynchronize(c->ev1));
       hipEventElapsedTime(ms, c->ev0, c->ev1);
     } else if (!c->async) {
-      e = hipStreamSynchronize(c->stream);
-      if (e != hipSuccess) return (int)e;
+      RGBID_HIP(hipStreamSynchronize(c->stream));
     }
     return RGBID_OK;
   }
@@ -326,10 +309,8 @@ inline WarpParams make_wp(const float R[9], const float t[3]) {
 
 // blocking read-back of a few bytes from the context's small device scratch through pinned memory
 int fetch_small(rgbid_ctx* c, size_t dev_off, size_t bytes) {
-  hipError_t e = hipMemcpyAsync((char*)c->small_host + dev_off, (char*)c->small_dev + dev_off, bytes, hipMemcpyDeviceToHost, c->stream);
-  if (e != hipSuccess) return (int)e;
-  e = hipStreamSynchronize(c->stream);
-  return (int)e;
+  RGBID_HIP(hipMemcpyAsync((char*)c->small_host + dev_off, (char*)c->small_dev + dev_off, bytes, hipMemcpyDeviceToHost, c->stream));
+  return hip_status(hipStreamSynchronize(c->stream));
 }
 
 }  // namespace
@@ -339,8 +320,7 @@ int rgbid::ctx_reserve_partials(rgbid_ctx* c, size_t n_doubles) {
   hipStreamSynchronize(c->stream);
   if (c->partials) hipFree(c->partials);
   c->partials = nullptr; c->partials_cap = 0;
-  hipError_t e = hipMalloc((void**)&c->partials, n_doubles * sizeof(double));
-  if (e != hipSuccess) return e == hipErrorOutOfMemory ? RGBID_E_NOMEM : (int)e;
+  if (int r = hip_alloc((void**)&c->partials, n_doubles * sizeof(double))) return r;
   c->partials_cap = n_doubles;
   return RGBID_OK;
 }
@@ -352,14 +332,13 @@ int rgbid::ctx_reserve_lane(rgbid_ctx* c, size_t bytes) {
   if (c->lane_host) hipHostFree(c->lane_host);
   c->lane_dev = c->lane_host = nullptr; c->lane_cap = 0;
   bytes = (bytes + 4095) & ~(size_t)4095;
-  hipError_t e = hipMalloc(&c->lane_dev, bytes);
-  if (e == hipSuccess) e = hipHostMalloc(&c->lane_host, bytes, hipHostMallocDefault);
-  if (e == hipSuccess && !c->lane_ev) e = hipEventCreateWithFlags(&c->lane_ev, hipEventDisableTiming);
+  int r = hip_alloc(&c->lane_dev, bytes);
+  if (!r) r = hip_alloc_host(&c->lane_host, bytes);
+  if (!r && !c->lane_ev) r = hip_status(hipEventCreateWithFlags(&c->lane_ev, hipEventDisableTiming));
   c->lane_ev_pending = false;
-  if (e != hipSuccess) {
+  if (r) {
     if (c->lane_dev) { hipFree(c->lane_dev); c->lane_dev = nullptr; }
-    (void)hipGetLastError();
-    return e == hipErrorOutOfMemory ? RGBID_E_NOMEM : (int)e;
+    return r;
   }
   c->lane_cap = bytes;
   return RGBID_OK;

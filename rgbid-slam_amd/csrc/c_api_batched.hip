@@ -3,7 +3,7 @@
 // staging copy lets an asynchronous context issue the next call without overwriting parameters still in flight), the SAME launchers
 // (kernels.h) the engine calls -- nothing here has an implementation of its own, and nothing falls back to another numerics class or to a CPU.
 #include "../../include/rgbid_batched.h"
-#include "ctx.h"
+#include "hip_host.h"
 #include "kernels.h"
 
 #include <cstring>
@@ -12,12 +12,6 @@
 using namespace rgbid;
 
 namespace {
-
-#define RGBID_HIPB(expr)                                               \
-  do {                                                                 \
-    hipError_t e_ = (expr);                                            \
-    if (e_ != hipSuccess) { (void)hipGetLastError(); return (int)e_; } \
-  } while (0)
 
 const LaneMask ALL{nullptr, 0};
 
@@ -43,17 +37,10 @@ struct Call {
   Call(rgbid_ctx* c_, float* ms_) : c(c_), ms(ms_) { if (ms) hipEventRecord(c->ev0, c->stream); }
   // results: bytes of the lane scratch (from offset 0 of `from`) the caller reads on the host afterwards
   int finish(const void* from = nullptr, size_t result_bytes = 0, size_t host_off = 0) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
+    RGBID_HIP(hipGetLastError());
     if (ms) hipEventRecord(c->ev1, c->stream);
-    if (result_bytes) {
-      e = hipMemcpyAsync((char*)c->lane_host + host_off, from, result_bytes, hipMemcpyDeviceToHost, c->stream);
-      if (e != hipSuccess) { (void)hipGetLastError(); return (int)e; }
-    }
-    if (result_bytes || ms || !c->async) {
-      e = hipStreamSynchronize(c->stream);
-      if (e != hipSuccess) { (void)hipGetLastError(); return (int)e; }
-    }
+    if (result_bytes) RGBID_HIP(hipMemcpyAsync((char*)c->lane_host + host_off, from, result_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (result_bytes || ms || !c->async) RGBID_HIP(hipStreamSynchronize(c->stream));
     if (ms) hipEventElapsedTime(ms, c->ev0, c->ev1);
     return RGBID_OK;
   }
@@ -63,11 +50,11 @@ inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // the pinned staging area may be rewritten once the previous call's H2D out of it has run (the kernels behind it need not have)
 int staging_free(rgbid_ctx* c) {
-  if (c->lane_ev_pending) { RGBID_HIPB(hipEventSynchronize(c->lane_ev)); c->lane_ev_pending = false; }
+  if (c->lane_ev_pending) { RGBID_HIP(hipEventSynchronize(c->lane_ev)); c->lane_ev_pending = false; }
   return RGBID_OK;
 }
 int staging_sent(rgbid_ctx* c) {
-  RGBID_HIPB(hipEventRecord(c->lane_ev, c->stream));
+  RGBID_HIP(hipEventRecord(c->lane_ev, c->stream));
   c->lane_ev_pending = true;
   return RGBID_OK;
 }
@@ -79,7 +66,7 @@ int stage_warps(rgbid_ctx* c, int lanes, const float* R, const float* t, size_t 
     for (int i = 0; i < 9; ++i) h[l].R[i] = R[(size_t)l * 9 + i];
     for (int i = 0; i < 3; ++i) h[l].t[i] = t[(size_t)l * 3 + i];
   }
-  RGBID_HIPB(hipMemcpyAsync((char*)c->lane_dev + off, h, sizeof(WarpParams) * lanes, hipMemcpyHostToDevice, c->stream));
+  RGBID_HIP(hipMemcpyAsync((char*)c->lane_dev + off, h, sizeof(WarpParams) * lanes, hipMemcpyHostToDevice, c->stream));
   return RGBID_OK;
 }
 
@@ -88,7 +75,7 @@ int stage_sys(rgbid_ctx* c, int lanes, rgbid_intr k, const rgbid_sys_params* p, 
   for (int l = 0; l < lanes; ++l)
     h[l] = SysParams{k.fx, k.fy, k.cx, k.cy, p[l].sigma_depthinv, p[l].sigma_int, p[l].bias_depthinv, p[l].bias_int, p[l].nu_depthinv, p[l].nu_int,
                      p[l].mestimator, p[l].weighting, p[l].student_nu ? 1 : 0, p[l].nu_int_from_max ? 1 : 0};
-  RGBID_HIPB(hipMemcpyAsync((char*)c->lane_dev + off, h, sizeof(SysParams) * lanes, hipMemcpyHostToDevice, c->stream));
+  RGBID_HIP(hipMemcpyAsync((char*)c->lane_dev + off, h, sizeof(SysParams) * lanes, hipMemcpyHostToDevice, c->stream));
   return RGBID_OK;
 }
 
@@ -250,7 +237,7 @@ int rgbid_sigma_pair_batched(rgbid_ctx* c, int lanes, const float* res_dev, size
   int e = ctx_reserve_lane(c, sizeof(SysParams) * lanes);
   if (e) return e;
   SysParams* sp = reinterpret_cast<SysParams*>(c->lane_dev);
-  RGBID_HIPB(hipMemsetAsync(sp, 0, sizeof(SysParams) * lanes, c->stream));
+  RGBID_HIP(hipMemsetAsync(sp, 0, sizeof(SysParams) * lanes, c->stream));
   Call call(c, ms);
   launch_sigma_pair_arrays(c->stream, lanes, res_dev, res_lane_stride, n, sp, mestimator, ALL);
   e = call.finish(sp, sizeof(SysParams) * lanes, 0);
@@ -302,7 +289,7 @@ int rgbid_visibility_pair_batched(rgbid_ctx* c, int lanes, const rgbid_imgb* a, 
   if ((e = stage_warps(c, lanes, R_ba, t_ba, off_ba))) return e;
   if ((e = staging_sent(c))) return e;
   unsigned int* cnt = reinterpret_cast<unsigned int*>((char*)c->lane_dev + off_cnt);   // [2][lanes][2]: a->b block, then b->a block
-  RGBID_HIPB(hipMemsetAsync(cnt, 0, sizeof(unsigned int) * 4 * lanes, c->stream));
+  RGBID_HIP(hipMemsetAsync(cnt, 0, sizeof(unsigned int) * 4 * lanes, c->stream));
   Call call(c, ms);
   launch_visibility_pair(c->stream, lanes, BB(a, lanes), BB(b, lanes), reinterpret_cast<const WarpParams*>((char*)c->lane_dev + off_ab),
                          reinterpret_cast<const WarpParams*>((char*)c->lane_dev + off_ba), cnt, cnt + 2 * lanes, ALL, numerics == RGBID_NUMERICS_FAST);

@@ -19,6 +19,10 @@
 #endif
 #endif
 
+// The per-lane scalar kernels hold 6x6 / 3x3 double matrices in registers: one wave per SIMD may take the whole register file (the default budget of 128
+// VGPRs spilled 660 - 1 250 bytes per thread to scratch, and dependent scratch round trips were most of these kernels' run time)
+#define RGBID_SCALAR_KERNEL __attribute__((amdgpu_waves_per_eu(1, 1)))
+
 namespace rgbid {
 
 struct ImgB {

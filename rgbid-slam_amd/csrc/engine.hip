@@ -8,7 +8,7 @@
 // control flow (lost tracking, keyframe switches, fuse-vs-reset) is expressed as per-lane flag arrays that
 // predicate whole workgroups (LaneMask).
 #include "../../include/rgbid_engine.h"
-#include "ctx.h"
+#include "hip_host.h"
 #include "kernels.h"
 #include "../../include/rgbid/se3.h"
 #include "engine_device.h"
@@ -20,10 +20,6 @@
 #include <cstring>
 #include <new>
 #include <vector>
-
-// The per-lane scalar kernels hold 6x6 / 3x3 double matrices in registers: one wave per SIMD may take the whole register file (the default budget of 128
-// VGPRs spilled 660 - 1 250 bytes per thread to scratch, and dependent scratch round trips were most of these kernels' run time)
-#define RGBID_SCALAR_KERNEL __attribute__((amdgpu_waves_per_eu(1, 1)))
 
 #pragma clang fp contract(off)   // the per-lane scalar kernels below (double-precision tracker logic): no FMA contraction, as se3.h / engine_device.h
 
@@ -536,8 +532,7 @@ struct rgbid_engine {
   rgbid_ctx* ctx = nullptr;
   rgbid_engine_config cfg{};
   int B = 0, L = 0;
-  std::vector<void*> allocs;
-  size_t bytes = 0;
+  Buffers buf;
   // images
   ImgB in_depth, in_rgb;      // pitched staging copies of the inputs (graph replay needs fixed addresses)
   ImgB cur_depth, cur_rgb;    // what this step reads: the staging copies, or dense views of the caller's buffers (eager mode)
@@ -588,14 +583,8 @@ struct rgbid_engine {
 namespace {
 
 int alloc_dev(rgbid_engine* e, void** p, size_t bytes, bool zero = true) {
-  hipError_t err = hipMalloc(p, bytes);
-  if (err != hipSuccess) return err == hipErrorOutOfMemory ? RGBID_E_NOMEM : (int)err;
-  e->allocs.push_back(*p);
-  e->bytes += bytes;
-  if (zero) {
-    err = hipMemsetAsync(*p, 0, bytes, e->ctx->stream);
-    if (err != hipSuccess) return (int)err;
-  }
+  if (int r = e->buf.alloc(p, bytes)) return r;
+  if (zero) RGBID_HIP(hipMemsetAsync(*p, 0, bytes, e->ctx->stream));
   return RGBID_OK;
 }
 
@@ -978,8 +967,7 @@ int enqueue_step(rgbid_engine* e, hipStream_t s, bool first) {
   }
   hipLaunchKernelGGL(k_step_end, dim3(gb), dim3(tb), 0, s, e->state, e->rec_cur, f.kf_slot, B);
   e->launches++;
-  hipError_t err = hipGetLastError();
-  return err == hipSuccess ? RGBID_OK : (int)err;
+  return hip_status(hipGetLastError());
 }
 
 }  // namespace
@@ -1112,10 +1100,10 @@ int rgbid_engine_create(rgbid_engine** out, rgbid_ctx* ctx, const rgbid_engine_c
     e->kf_block_bytes = 20 * (size_t)rows * cols;   // u8 mask + 3 u8 colours + f32 inverse depth + 3 f32 normals per pixel
     r = alloc_dev(e, (void**)&e->kf_hdr, sizeof(rgbid_keyframe_header) * (size_t)cfg->keyframe_capacity * B);
     if (!r) r = alloc_dev(e, (void**)&e->kf_blocks, e->kf_block_bytes * cfg->keyframe_capacity * B, /*zero=*/false);
-    if (!r && hipHostMalloc((void**)&e->kf_staging, sizeof(rgbid_keyframe_header) + e->kf_block_bytes, hipHostMallocDefault) != hipSuccess) r = RGBID_E_NOMEM;
-    if (!r && hipHostMalloc((void**)&e->kf_counts_host, sizeof(int) * B, hipHostMallocDefault) != hipSuccess) r = RGBID_E_NOMEM;
+    if (!r) r = e->buf.alloc_host(&e->kf_staging, sizeof(rgbid_keyframe_header) + e->kf_block_bytes);
+    if (!r) r = e->buf.alloc_host(&e->kf_counts_host, sizeof(int) * B);
   }
-  if (!r) { hipError_t he = hipStreamSynchronize(ctx->stream); if (he != hipSuccess) r = (int)he; }
+  if (!r) r = hip_status(hipStreamSynchronize(ctx->stream));
   if (r) { rgbid_engine_destroy(e); return r; }
   if (getenv("RGBID_ENGINE_DEBUG_ALLOC")) {   // diagnostics: where the level-0 maps of the dominant kernel landed (placement sensitivity of the 1280x960 case)
     const ImgB* m[] = {&e->iD_kf[0], &e->I_kf[0], &e->gxD[0], &e->gyD[0], &e->gxI[0], &e->gyI[0], &e->iD_curr[0], &e->I_curr[0]};
@@ -1133,22 +1121,17 @@ int rgbid_engine_destroy(rgbid_engine* e) {
   hipStreamSynchronize(e->ctx->stream);
   if (e->graph_first) hipGraphExecDestroy(e->graph_first);
   if (e->graph_next) hipGraphExecDestroy(e->graph_next);
-  for (void* p : e->allocs) hipFree(p);
-  if (e->kf_staging) hipHostFree(e->kf_staging);
-  if (e->kf_counts_host) hipHostFree(e->kf_counts_host);
   for (hipEvent_t ev : e->prof_ev) hipEventDestroy(ev);
-  delete e;
+  delete e;   // its Buffers free the maps and the pinned staging
   return RGBID_OK;
 }
 
 int rgbid_engine_reset(rgbid_engine* e) {
   if (!e) return RGBID_E_INVALID;
   hipSetDevice(e->ctx->device);
-  hipError_t he = hipMemsetAsync(e->state, 0, sizeof(LaneState) * e->B, e->ctx->stream);  // global_time = 0 -> first-frame path
-  if (he != hipSuccess) return (int)he;
+  RGBID_HIP(hipMemsetAsync(e->state, 0, sizeof(LaneState) * e->B, e->ctx->stream));  // global_time = 0 -> first-frame path
   // warped_weight_curr_ is never initialised by the reference (uninitialised device memory); the engine defines it as 0
-  he = hipMemsetAsync(e->warped_w.base, 0, e->warped_w.lane_stride * e->B, e->ctx->stream);
-  if (he != hipSuccess) return (int)he;
+  RGBID_HIP(hipMemsetAsync(e->warped_w.base, 0, e->warped_w.lane_stride * e->B, e->ctx->stream));
   e->steps = 0;
   return RGBID_OK;
 }
@@ -1158,9 +1141,8 @@ int rgbid_engine_set_active(rgbid_engine* e, const int* active_host) {
   hipSetDevice(e->ctx->device);
   std::vector<int> m(e->B, 1);
   if (active_host) for (int i = 0; i < e->B; ++i) m[i] = active_host[i] ? 1 : 0;
-  hipError_t he = hipMemcpyAsync(e->active_dev, m.data(), sizeof(int) * e->B, hipMemcpyHostToDevice, e->ctx->stream);
-  if (he == hipSuccess) he = hipStreamSynchronize(e->ctx->stream);   // m is a temporary
-  return he == hipSuccess ? RGBID_OK : (int)he;
+  RGBID_HIP(hipMemcpyAsync(e->active_dev, m.data(), sizeof(int) * e->B, hipMemcpyHostToDevice, e->ctx->stream));
+  return hip_status(hipStreamSynchronize(e->ctx->stream));   // m is a temporary
 }
 
 int rgbid_engine_reset_lane(rgbid_engine* e, int lane) {
@@ -1169,13 +1151,10 @@ int rgbid_engine_reset_lane(rgbid_engine* e, int lane) {
   hipSetDevice(e->ctx->device);
   // the lane's next frame takes the first-frame path of k_step_begin (global_time == 0) inside the ordinary step: its Gauss-Newton, covisibility
   // and fusion kernels are predicated off by the lane flags and the keyframe-creation kernels on, exactly as in the first step after reset()
-  hipError_t he = hipMemsetAsync(&e->state[lane], 0, sizeof(LaneState), e->ctx->stream);
-  if (he != hipSuccess) return (int)he;
-  he = hipMemsetAsync((char*)e->warped_w.base + (size_t)lane * e->warped_w.lane_stride, 0, e->warped_w.lane_stride, e->ctx->stream);
-  if (he != hipSuccess) return (int)he;
+  RGBID_HIP(hipMemsetAsync(&e->state[lane], 0, sizeof(LaneState), e->ctx->stream));
+  RGBID_HIP(hipMemsetAsync((char*)e->warped_w.base + (size_t)lane * e->warped_w.lane_stride, 0, e->warped_w.lane_stride, e->ctx->stream));
   // the lane's staged record goes with its state: while the lane sits steps out before its new first frame, its records read all-zero
-  he = hipMemsetAsync(&e->rec_cur[lane], 0, sizeof(rgbid_pose_record), e->ctx->stream);
-  return he == hipSuccess ? RGBID_OK : (int)he;
+  return hip_status(hipMemsetAsync(&e->rec_cur[lane], 0, sizeof(rgbid_pose_record), e->ctx->stream));
 }
 
 int rgbid_engine_step(rgbid_engine* e, const void* depth_dev, const void* rgb_dev) {
@@ -1188,7 +1167,7 @@ int rgbid_engine_set_delta_t(rgbid_engine* e, float delta_t) {
   if (!e || !(delta_t > 0.f) || !(delta_t < INFINITY)) return RGBID_E_INVALID;   // 1 / delta_t scales the velocity of the constant-velocity prediction: 0, negative, inf or NaN would lose the lane
   hipSetDevice(e->ctx->device);
   // the kernels read the value through a device pointer (StepCfg::delta_t): captured graphs stay valid; ordered on the context's stream
-  if (hipError_t he = hipMemsetD32Async((hipDeviceptr_t)e->delta_t_dev, __builtin_bit_cast(int, delta_t), 1, e->ctx->stream); he != hipSuccess) return (int)he;
+  RGBID_HIP(hipMemsetD32Async((hipDeviceptr_t)e->delta_t_dev, __builtin_bit_cast(int, delta_t), 1, e->ctx->stream));
   e->cfg.delta_t = delta_t;
   return RGBID_OK;
 }
@@ -1217,7 +1196,7 @@ int rgbid_engine_step_strided(rgbid_engine* e, const void* depth_dev, size_t dep
         he = hipMemcpy2DAsync((char*)e->in_rgb.base + (size_t)l * e->in_rgb.lane_stride, e->in_rgb.pitch, (const char*)rgb_dev + (size_t)l * rgb_lane_stride, rgb_step,
                               (size_t)c.cols * 3, nrows, hipMemcpyDeviceToDevice, s);
     }
-    if (he != hipSuccess) return (int)he;
+    RGBID_HIP(he);
     e->cur_depth = e->in_depth; e->cur_rgb = e->in_rgb;
   } else {
     e->cur_depth = ImgB{const_cast<void*>(depth_dev), depth_step, depth_lane_stride, c.rows, c.cols};
@@ -1232,30 +1211,27 @@ int rgbid_engine_step_strided(rgbid_engine* e, const void* depth_dev, size_t dep
     bool& ready = first ? e->graph_ready_first : e->graph_ready_next;
     if (!ready) {
       hipGraph_t g = nullptr;
-      he = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
-      if (he != hipSuccess) return (int)he;
+      RGBID_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
       r = enqueue_step(e, s, first);
       he = hipStreamEndCapture(s, &g);
       if (r || he != hipSuccess) {
         if (g) hipGraphDestroy(g);
-        return r ? r : (int)he;
+        return r ? r : hip_status(he);
       }
       he = hipGraphInstantiate(&gx, g, nullptr, nullptr, 0);
       hipGraphDestroy(g);
-      if (he != hipSuccess) return (int)he;
+      RGBID_HIP(he);
       ready = true;
     }
-    he = hipGraphLaunch(gx, s);
-    if (he != hipSuccess) return (int)he;
+    RGBID_HIP(hipGraphLaunch(gx, s));
   } else {
     r = enqueue_step(e, s, first);
     if (r) return r;
   }
   int slot = e->steps % c.record_capacity;
-  he = hipMemcpyAsync(e->records + (size_t)slot * e->B, e->rec_cur, sizeof(rgbid_pose_record) * e->B, hipMemcpyDeviceToDevice, s);
-  if (he != hipSuccess) return (int)he;
+  RGBID_HIP(hipMemcpyAsync(e->records + (size_t)slot * e->B, e->rec_cur, sizeof(rgbid_pose_record) * e->B, hipMemcpyDeviceToDevice, s));
   e->steps++;
-  if (!e->ctx->async) { he = hipStreamSynchronize(s); if (he != hipSuccess) return (int)he; }
+  if (!e->ctx->async) RGBID_HIP(hipStreamSynchronize(s));
   return RGBID_OK;
 }
 
@@ -1265,11 +1241,9 @@ int rgbid_engine_read_records(rgbid_engine* e, int first_step, int n_steps, rgbi
   if (!e || !out || n_steps < 0 || first_step < 0 || first_step + n_steps > e->steps || e->steps - first_step > e->cfg.record_capacity) return RGBID_E_INVALID;
   for (int k = 0; k < n_steps; ++k) {
     int slot = (first_step + k) % e->cfg.record_capacity;
-    hipError_t he = hipMemcpyAsync(out + (size_t)k * e->B, e->records + (size_t)slot * e->B, sizeof(rgbid_pose_record) * e->B, hipMemcpyDeviceToHost, e->ctx->stream);
-    if (he != hipSuccess) return (int)he;
+    RGBID_HIP(hipMemcpyAsync(out + (size_t)k * e->B, e->records + (size_t)slot * e->B, sizeof(rgbid_pose_record) * e->B, hipMemcpyDeviceToHost, e->ctx->stream));
   }
-  hipError_t he = hipStreamSynchronize(e->ctx->stream);
-  return he == hipSuccess ? RGBID_OK : (int)he;
+  return hip_status(hipStreamSynchronize(e->ctx->stream));
 }
 
 int rgbid_engine_pack_gather_records(rgbid_engine* e, int first_step, int n_steps, rgbid_gather_record* out_dev) {
@@ -1279,9 +1253,9 @@ int rgbid_engine_pack_gather_records(rgbid_engine* e, int first_step, int n_step
   hipSetDevice(e->ctx->device);
   const int n = e->B * n_steps;
   hipLaunchKernelGGL(k_pack_gather, dim3(div_up(n, 128)), dim3(128), 0, e->ctx->stream, e->records, e->cfg.record_capacity, e->B, first_step, n_steps, out_dev);
-  hipError_t he = hipGetLastError();
-  if (he == hipSuccess && !e->ctx->async) he = hipStreamSynchronize(e->ctx->stream);
-  return he == hipSuccess ? RGBID_OK : (int)he;
+  RGBID_HIP(hipGetLastError());
+  if (!e->ctx->async) RGBID_HIP(hipStreamSynchronize(e->ctx->stream));
+  return RGBID_OK;
 }
 
 int rgbid_engine_records_dev(rgbid_engine* e, void** ptr, int* capacity) {
@@ -1295,10 +1269,9 @@ int rgbid_engine_keyframe_counts(rgbid_engine* e, int* counts) {
   if (!e || !counts) return RGBID_E_INVALID;
   if (!e->kf_hdr) { for (int i = 0; i < e->B; ++i) counts[i] = 0; return RGBID_OK; }
   hipSetDevice(e->ctx->device);
-  hipError_t he = hipMemcpy2DAsync(e->kf_counts_host, sizeof(int), &e->state[0].kf_exported, sizeof(LaneState), sizeof(int), e->B,
-                                   hipMemcpyDeviceToHost, e->ctx->stream);
-  if (he == hipSuccess) he = hipStreamSynchronize(e->ctx->stream);
-  if (he != hipSuccess) return (int)he;
+  RGBID_HIP(hipMemcpy2DAsync(e->kf_counts_host, sizeof(int), &e->state[0].kf_exported, sizeof(LaneState), sizeof(int), e->B, hipMemcpyDeviceToHost,
+                             e->ctx->stream));
+  RGBID_HIP(hipStreamSynchronize(e->ctx->stream));
   memcpy(counts, e->kf_counts_host, sizeof(int) * e->B);
   return RGBID_OK;
 }
@@ -1311,19 +1284,14 @@ int rgbid_engine_read_keyframe(rgbid_engine* e, int lane, int seq, rgbid_keyfram
   hipStream_t s = e->ctx->stream;
   rgbid_keyframe_header* h = reinterpret_cast<rgbid_keyframe_header*>(e->kf_staging);
   const bool images = overlap_mask || colors || depthinv || normals;
-  hipError_t he = hipMemcpyAsync(h, e->kf_hdr + (size_t)lane * cap + slot, sizeof(*h), hipMemcpyDeviceToHost, s);
-  if (he == hipSuccess && images)
-    he = hipMemcpyAsync(e->kf_staging + sizeof(*h), e->kf_blocks + ((size_t)lane * cap + slot) * e->kf_block_bytes, e->kf_block_bytes,
-                        hipMemcpyDeviceToHost, s);
-  if (he == hipSuccess) he = hipStreamSynchronize(s);
-  if (he != hipSuccess) return (int)he;
-  int count = 0;
-  {
-    he = hipMemcpyAsync(e->kf_counts_host, &e->state[lane].kf_exported, sizeof(int), hipMemcpyDeviceToHost, s);
-    if (he == hipSuccess) he = hipStreamSynchronize(s);
-    if (he != hipSuccess) return (int)he;
-    count = e->kf_counts_host[0];
-  }
+  RGBID_HIP(hipMemcpyAsync(h, e->kf_hdr + (size_t)lane * cap + slot, sizeof(*h), hipMemcpyDeviceToHost, s));
+  if (images)
+    RGBID_HIP(hipMemcpyAsync(e->kf_staging + sizeof(*h), e->kf_blocks + ((size_t)lane * cap + slot) * e->kf_block_bytes, e->kf_block_bytes,
+                             hipMemcpyDeviceToHost, s));
+  RGBID_HIP(hipStreamSynchronize(s));
+  RGBID_HIP(hipMemcpyAsync(e->kf_counts_host, &e->state[lane].kf_exported, sizeof(int), hipMemcpyDeviceToHost, s));
+  RGBID_HIP(hipStreamSynchronize(s));
+  const int count = e->kf_counts_host[0];
   if (seq >= count || seq < count - cap || h->seq != seq) return RGBID_E_INVALID;  // not exported yet / already overwritten
   if (header) *header = *h;
   const size_t N = (size_t)e->cfg.rows * e->cfg.cols;
@@ -1388,8 +1356,7 @@ int rgbid_engine_profile_begin(rgbid_engine* e, int max_launches) {
   while ((int)e->prof_ev.size() < 2 * max_launches) {
     hipEvent_t ev;
     // no system-scope fence around the timed kernel: the events only order against work on this stream
-    hipError_t he = hipEventCreate(&ev);
-    if (he != hipSuccess) return (int)he;
+    RGBID_HIP(hipEventCreate(&ev));
     e->prof_ev.push_back(ev);
   }
   e->prof_used = 0;
@@ -1399,13 +1366,11 @@ int rgbid_engine_profile_begin(rgbid_engine* e, int max_launches) {
 
 int rgbid_engine_profile_end(rgbid_engine* e, double* total_ms, int* n_launches, double* bytes_per_launch) {
   if (!e || !total_ms || !n_launches) return RGBID_E_INVALID;
-  hipError_t he = hipStreamSynchronize(e->ctx->stream);
-  if (he != hipSuccess) return (int)he;
+  RGBID_HIP(hipStreamSynchronize(e->ctx->stream));
   double tot = 0.0;
   for (int i = 0; i + 1 < e->prof_used; i += 2) {
     float ms = 0.f;
-    he = hipEventElapsedTime(&ms, e->prof_ev[i], e->prof_ev[i + 1]);
-    if (he != hipSuccess) return (int)he;
+    RGBID_HIP(hipEventElapsedTime(&ms, e->prof_ev[i], e->prof_ev[i + 1]));
     tot += ms;
   }
   *total_ms = tot;
@@ -1416,7 +1381,7 @@ int rgbid_engine_profile_end(rgbid_engine* e, double* total_ms, int* n_launches,
   return RGBID_OK;
 }
 
-int rgbid_engine_bytes(const rgbid_engine* e, size_t* bytes) { if (!e || !bytes) return RGBID_E_INVALID; *bytes = e->bytes; return RGBID_OK; }
+int rgbid_engine_bytes(const rgbid_engine* e, size_t* bytes) { if (!e || !bytes) return RGBID_E_INVALID; *bytes = e->buf.bytes(); return RGBID_OK; }
 int rgbid_engine_launches_per_step(const rgbid_engine* e) { return e ? e->launches : 0; }
 int rgbid_engine_step_bytes(const rgbid_engine* e, double out[4]) {
   if (!e || !out) return RGBID_E_INVALID;

@@ -12,7 +12,7 @@
 // The counting and emitting kernels walk a flat (keyframe, tile) index, grid-strided with the grid capped at CLOUD_MAX_GRID blocks.
 #include "../../include/rgbid_cloud.h"
 #include "common.h"
-#include "ctx.h"
+#include "hip_host.h"
 
 #include <cstring>
 #include <new>
@@ -259,18 +259,10 @@ struct rgbid_cloud {
   unsigned long long* kf_off_host = nullptr;   // pinned
   CloudGeom geom = {};                         // of the last plan (geom.n = 0: none)
   unsigned long long total = 0;
+  Buffers buf;
 };
 
 namespace {
-
-// a failed allocation is reported through the return value and the runtime's sticky last error is cleared (c_api.hip rgbid_malloc_host)
-int cloud_alloc(void** p, size_t bytes, bool host) {
-  hipError_t e = host ? hipHostMalloc(p, bytes, hipHostMallocDefault) : hipMalloc(p, bytes);
-  if (e == hipSuccess) return RGBID_OK;
-  (void)hipGetLastError();
-  *p = nullptr;
-  return e == hipErrorOutOfMemory ? RGBID_E_NOMEM : (int)e;
-}
 
 // Eigen's compute_inverse<3x3> (Eigen/src/LU/InverseImpl.h) of K = [fx 0 cx; 0 fy cy; 0 0 1] in double: cofactors of column 0,
 // det = their dot product with column 0 (in index order), invdet = 1 / det, Kinv(i, j) = cofactor(j, i) * invdet
@@ -288,12 +280,6 @@ void kinv_eigen(const float K[4], double Kinv[9]) {
 }
 
 int grid_of(int items) { return items < CLOUD_MAX_GRID ? items : CLOUD_MAX_GRID; }
-
-#define RGBID_HIPC(expr)                                               \
-  do {                                                                 \
-    hipError_t e_ = (expr);                                            \
-    if (e_ != hipSuccess) { (void)hipGetLastError(); return (int)e_; } \
-  } while (0)
 
 }  // namespace
 
@@ -315,12 +301,12 @@ int rgbid_cloud_create(rgbid_cloud** out, rgbid_ctx* ctx, int rows, int cols, in
   c->ctx = ctx; c->rows = rows; c->cols = cols; c->cap = max_keyframes;
   c->tiles = (rows * cols + TILE - 1) / TILE;
   const size_t cap = (size_t)max_keyframes;
-  int r = cloud_alloc((void**)&c->src_dev, sizeof(rgbid_cloud_src) * cap, false);
-  if (!r) r = cloud_alloc((void**)&c->src_host, sizeof(rgbid_cloud_src) * cap, true);
-  if (!r) r = cloud_alloc((void**)&c->tile_off, sizeof(unsigned) * cap * c->tiles, false);
-  if (!r) r = cloud_alloc((void**)&c->kf_total, sizeof(unsigned) * cap, false);
-  if (!r) r = cloud_alloc((void**)&c->kf_off, sizeof(unsigned long long) * (cap + 1), false);
-  if (!r) r = cloud_alloc((void**)&c->kf_off_host, sizeof(unsigned long long) * (cap + 1), true);
+  int r = c->buf.alloc(&c->src_dev, sizeof(rgbid_cloud_src) * cap);
+  if (!r) r = c->buf.alloc_host(&c->src_host, sizeof(rgbid_cloud_src) * cap);
+  if (!r) r = c->buf.alloc(&c->tile_off, sizeof(unsigned) * cap * c->tiles);
+  if (!r) r = c->buf.alloc(&c->kf_total, sizeof(unsigned) * cap);
+  if (!r) r = c->buf.alloc(&c->kf_off, sizeof(unsigned long long) * (cap + 1));
+  if (!r) r = c->buf.alloc_host(&c->kf_off_host, sizeof(unsigned long long) * (cap + 1));
   if (r) { rgbid_cloud_destroy(c); return r; }
   *out = c;
   return RGBID_OK;
@@ -330,10 +316,7 @@ int rgbid_cloud_destroy(rgbid_cloud* c) {
   if (!c) return RGBID_OK;
   (void)hipSetDevice(c->ctx->device);
   if (c->ctx->stream) (void)hipStreamSynchronize(c->ctx->stream);   // an emit may still read the tables
-  for (void* p : {(void*)c->src_dev, (void*)c->tile_off, (void*)c->kf_total, (void*)c->kf_off}) if (p) (void)hipFree(p);
-  for (void* p : {(void*)c->src_host, (void*)c->kf_off_host}) if (p) (void)hipHostFree(p);
-  (void)hipGetLastError();
-  delete c;
+  delete c;   // its Buffers free the tables
   return RGBID_OK;
 }
 
@@ -346,18 +329,18 @@ int rgbid_cloud_plan(rgbid_cloud* c, int n, const rgbid_cloud_src* src, const fl
   c->geom.n = 0; c->total = 0;
   offsets[0] = 0;
   if (n == 0) return RGBID_OK;
-  RGBID_HIPC(hipStreamSynchronize(s));   // the previous plan's upload and emit have read the staging area and the tables
+  RGBID_HIP(hipStreamSynchronize(s));   // the previous plan's upload and emit have read the staging area and the tables
   CloudGeom g;
   kinv_eigen(K, g.kinv);
   g.N = c->rows * c->cols; g.cols = c->cols; g.tiles = c->tiles; g.n = n; g.mode = mode;
   memcpy(c->src_host, src, sizeof(rgbid_cloud_src) * n);
-  RGBID_HIPC(hipMemcpyAsync(c->src_dev, c->src_host, sizeof(rgbid_cloud_src) * n, hipMemcpyHostToDevice, s));
+  RGBID_HIP(hipMemcpyAsync(c->src_dev, c->src_host, sizeof(rgbid_cloud_src) * n, hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_cloud_count, dim3(grid_of(n * g.tiles)), dim3(CT), 0, s, c->src_dev, g, c->tile_off);
   hipLaunchKernelGGL(k_cloud_scan_tiles, dim3(n), dim3(CT), 0, s, c->tile_off, c->kf_total, g.tiles);
   hipLaunchKernelGGL(k_cloud_scan_kfs, dim3(1), dim3(CT), 0, s, c->kf_total, c->kf_off, n);
-  RGBID_HIPC(hipGetLastError());
-  RGBID_HIPC(hipMemcpyAsync(c->kf_off_host, c->kf_off, sizeof(unsigned long long) * (n + 1), hipMemcpyDeviceToHost, s));
-  RGBID_HIPC(hipStreamSynchronize(s));
+  RGBID_HIP(hipGetLastError());
+  RGBID_HIP(hipMemcpyAsync(c->kf_off_host, c->kf_off, sizeof(unsigned long long) * (n + 1), hipMemcpyDeviceToHost, s));
+  RGBID_HIP(hipStreamSynchronize(s));
   memcpy(offsets, c->kf_off_host, sizeof(unsigned long long) * (n + 1));
   c->geom = g;
   c->total = offsets[n];
@@ -371,7 +354,7 @@ int rgbid_cloud_emit(rgbid_cloud* c, rgbid_cloud_point* out_dev, unsigned long l
   (void)hipSetDevice(c->ctx->device);
   hipLaunchKernelGGL(k_cloud_emit, dim3(grid_of(c->geom.n * c->geom.tiles)), dim3(CT), 0, c->ctx->stream, c->src_dev, c->geom, c->tile_off, c->kf_off,
                      reinterpret_cast<uint4*>(out_dev));
-  RGBID_HIPC(hipGetLastError());
+  RGBID_HIP(hipGetLastError());
   return RGBID_OK;
 }
 

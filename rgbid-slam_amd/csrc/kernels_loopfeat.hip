@@ -19,7 +19,7 @@
 #include "../../include/rgbid_loopfeat.h"
 #include "../../include/rgbid_cloud.h"
 #include "common.h"
-#include "ctx.h"
+#include "hip_host.h"
 
 #include <cmath>
 #include <cstddef>
@@ -533,20 +533,6 @@ __global__ __launch_bounds__(LT) void k_lf_ransac(const rgbid_loopfeat_kp* __res
 }
 
 // ---- host ----
-int lf_alloc(void** p, size_t bytes) {
-  hipError_t e = hipMalloc(p, bytes);
-  if (e == hipSuccess) return RGBID_OK;
-  (void)hipGetLastError();
-  *p = nullptr;
-  return e == hipErrorOutOfMemory ? RGBID_E_NOMEM : (int)e;
-}
-
-#define RGBID_HIPC(expr)                                               \
-  do {                                                                 \
-    hipError_t e_ = (expr);                                            \
-    if (e_ != hipSuccess) { (void)hipGetLastError(); return (int)e_; } \
-  } while (0)
-
 // the project's own test pattern: xorshift32 from 0x9E3779B9; a coordinate is (next % 27) - 13; a test is (x1, y1, x2, y2) with both points
 // inside the disc of radius 13 and different from each other; the first 256 accepted tests, in order
 void lf_pattern(int8_t* pattern) {
@@ -611,10 +597,10 @@ struct rgbid_loopfeat {
   double* bounds = nullptr;
   LfLevel* levels_dev = nullptr;
   int2* tabs = nullptr;
-  bool timing = false;
-  hipEvent_t ev[10] = {};   // 0-3 extract, 4-5 match, 6-7 ransac, 8-9 pyramid
+  Buffers tables, scratch;  // what create made; what lf_reserve makes for cap_kf keyframes
+  StageTimer<10> timer;     // 0-3 extract, 4-5 match, 6-7 ransac, 8-9 pyramid
   bool timed[4] = {false, false, false, false};
-  void mark(int i) { if (timing) (void)hipEventRecord(ev[i], ctx->stream); }
+  void mark(int i) { timer.mark(i, ctx->stream); }
 };
 
 namespace {
@@ -622,14 +608,14 @@ namespace {
 // scratch for n keyframes
 int lf_reserve(rgbid_loopfeat* f, int n) {
   if (n <= f->cap_kf) return RGBID_OK;
-  RGBID_HIPC(hipStreamSynchronize(f->ctx->stream));
-  for (void* p : {(void*)f->resp, (void*)f->staged, (void*)f->cell_counts, (void*)f->pyr}) if (p) (void)hipFree(p);
+  RGBID_HIP(hipStreamSynchronize(f->ctx->stream));
+  f->scratch.release();
   f->resp = nullptr; f->staged = nullptr; f->cell_counts = nullptr; f->pyr = nullptr; f->cap_kf = 0;
   const LfGeom& g = f->g;
-  int r = lf_alloc((void**)&f->resp, sizeof(float) * (size_t)n * g.resp_stride);
-  if (!r) r = lf_alloc((void**)&f->staged, sizeof(LfStaged) * (size_t)n * g.slots);
-  if (!r) r = lf_alloc((void**)&f->cell_counts, sizeof(int) * (size_t)n * g.cells);
-  if (!r && g.pyr_stride) r = lf_alloc((void**)&f->pyr, (size_t)n * g.pyr_stride);
+  int r = f->scratch.alloc(&f->resp, sizeof(float) * (size_t)n * g.resp_stride);
+  if (!r) r = f->scratch.alloc(&f->staged, sizeof(LfStaged) * (size_t)n * g.slots);
+  if (!r) r = f->scratch.alloc(&f->cell_counts, sizeof(int) * (size_t)n * g.cells);
+  if (!r && g.pyr_stride) r = f->scratch.alloc(&f->pyr, (size_t)n * g.pyr_stride);
   if (r) return r;
   f->cap_kf = n;
   return RGBID_OK;
@@ -743,16 +729,16 @@ int rgbid_loopfeat_create_levels(rgbid_loopfeat** out, rgbid_ctx* ctx, int rows,
       rgbid_loopfeat_resize_table(src, dst, tmp, tmp + 8192);
       for (int d = 0; d < dst; ++d) tabs[f->tab_off[l][axis] + d] = make_int2(tmp[d], tmp[8192 + d]);
     }
-  if (!r) r = lf_alloc((void**)&f->rotated, sizeof(rot));
-  if (!r) r = lf_alloc((void**)&f->bounds, sizeof(bounds));
-  if (!r) r = lf_alloc((void**)&f->levels_dev, sizeof(LfLevel) * MAXL);
-  if (!r && ntab) r = lf_alloc((void**)&f->tabs, sizeof(int2) * (size_t)ntab);
+  if (!r) r = f->tables.alloc(&f->rotated, sizeof(rot));
+  if (!r) r = f->tables.alloc(&f->bounds, sizeof(bounds));
+  if (!r) r = f->tables.alloc(&f->levels_dev, sizeof(LfLevel) * MAXL);
+  if (!r && ntab) r = f->tables.alloc(&f->tabs, sizeof(int2) * (size_t)ntab);
   if (!r) {   // pageable sources: the copies have left the host buffers when the calls return
     hipError_t e = hipMemcpy(f->rotated, rot, sizeof(rot), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(f->bounds, bounds, sizeof(bounds), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(f->levels_dev, f->lv, sizeof(LfLevel) * MAXL, hipMemcpyHostToDevice);
     if (e == hipSuccess && ntab) e = hipMemcpy(f->tabs, tabs, sizeof(int2) * (size_t)ntab, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipGetLastError(); r = (int)e; }
+    r = hip_status(e);
   }
   delete[] tabs;
   delete[] tmp;
@@ -765,12 +751,7 @@ int rgbid_loopfeat_destroy(rgbid_loopfeat* f) {
   if (!f) return RGBID_OK;
   (void)hipSetDevice(f->ctx->device);
   if (f->ctx->stream) (void)hipStreamSynchronize(f->ctx->stream);
-  for (void* p : {(void*)f->resp, (void*)f->staged, (void*)f->cell_counts, (void*)f->pyr, (void*)f->rotated, (void*)f->bounds, (void*)f->levels_dev,
-                  (void*)f->tabs})
-    if (p) (void)hipFree(p);
-  for (hipEvent_t e : f->ev) if (e) (void)hipEventDestroy(e);
-  (void)hipGetLastError();
-  delete f;
+  delete f;   // its Buffers free tables and scratch, its StageTimer the events
   return RGBID_OK;
 }
 
@@ -799,15 +780,15 @@ int rgbid_loopfeat_pyramid(rgbid_loopfeat* f, const uint8_t* grey_dev, int n, in
   hipStream_t s = f->ctx->stream;
   const LfGeom& g = f->g;
   if (level == 0) {
-    RGBID_HIPC(hipMemcpyAsync(out_dev, grey_dev, (size_t)n * g.rows * g.cols, hipMemcpyDeviceToDevice, s));
+    RGBID_HIP(hipMemcpyAsync(out_dev, grey_dev, (size_t)n * g.rows * g.cols, hipMemcpyDeviceToDevice, s));
     return RGBID_OK;
   }
   const int r = lf_reserve(f, n);
   if (r) return r;
   lf_build_pyramid(f, grey_dev, n, level);
-  RGBID_HIPC(hipGetLastError());
+  RGBID_HIP(hipGetLastError());
   const size_t px = (size_t)f->lv[level].rows * f->lv[level].cols;
-  RGBID_HIPC(hipMemcpy2DAsync(out_dev, px, f->pyr + f->lv[level].img_off, (size_t)g.pyr_stride, px, (size_t)n, hipMemcpyDeviceToDevice, s));
+  RGBID_HIP(hipMemcpy2DAsync(out_dev, px, f->pyr + f->lv[level].img_off, (size_t)g.pyr_stride, px, (size_t)n, hipMemcpyDeviceToDevice, s));
   return RGBID_OK;
 }
 
@@ -839,8 +820,8 @@ int rgbid_loopfeat_extract_levels(rgbid_loopfeat* f, const uint8_t* grey_dev, co
     f->mark(9);
   }
   f->mark(0);
-  RGBID_HIPC(hipMemsetAsync(kps_dev, 0, sizeof(rgbid_loopfeat_kp) * (size_t)n * g.max_kp, s));
-  if (aux_dev) RGBID_HIPC(hipMemsetAsync(aux_dev, 0, sizeof(rgbid_loopfeat_aux) * (size_t)n * g.max_kp, s));
+  RGBID_HIP(hipMemsetAsync(kps_dev, 0, sizeof(rgbid_loopfeat_kp) * (size_t)n * g.max_kp, s));
+  if (aux_dev) RGBID_HIP(hipMemsetAsync(aux_dev, 0, sizeof(rgbid_loopfeat_aux) * (size_t)n * g.max_kp, s));
   hipLaunchKernelGGL(k_lf_response, dim3(f->tiles, n), dim3(LT), 0, s, grey_dev, f->pyr, g, f->levels_dev, scale4, f->resp);
   f->mark(1);
   hipLaunchKernelGGL(k_lf_select, dim3(g.cells, n), dim3(LT), 0, s, f->resp, invdepth_dev, g, f->levels_dev, f->staged, f->cell_counts);
@@ -848,9 +829,9 @@ int rgbid_loopfeat_extract_levels(rgbid_loopfeat* f, const uint8_t* grey_dev, co
   hipLaunchKernelGGL(k_lf_describe, dim3(f->dblocks, n), dim3(LT), 0, s, grey_dev, f->pyr, invdepth_dev, g, f->levels_dev, Ki, f->staged,
                      f->cell_counts, f->rotated, f->bounds, kps_dev, counts_dev, aux_dev);
   f->mark(3);
-  f->timed[0] = f->timing;
-  f->timed[3] = f->timing && g.levels > 1;
-  RGBID_HIPC(hipGetLastError());
+  f->timed[0] = f->timer.on;
+  f->timed[3] = f->timer.on && g.levels > 1;
+  RGBID_HIP(hipGetLastError());
   return RGBID_OK;
 }
 
@@ -867,8 +848,8 @@ int rgbid_loopfeat_match(rgbid_loopfeat* f, const rgbid_loopfeat_kp* kps_dev, co
   hipLaunchKernelGGL(k_lf_match, dim3(n_pairs), dim3(LT), sizeof(unsigned long long) * 4 * (size_t)f->g.max_kp, s, kps_dev, counts_dev, n_kf,
                      f->g.max_kp, pairs_dev, ratio, matches_dev, match_counts_dev);
   f->mark(5);
-  f->timed[1] = f->timing;
-  RGBID_HIPC(hipGetLastError());
+  f->timed[1] = f->timer.on;
+  RGBID_HIP(hipGetLastError());
   return RGBID_OK;
 }
 
@@ -888,8 +869,8 @@ int rgbid_loopfeat_ransac(rgbid_loopfeat* f, const rgbid_loopfeat_kp* kps_dev, i
   hipLaunchKernelGGL(k_lf_ransac, dim3(n_pairs), dim3(LT), 0, s, kps_dev, n_kf, f->g.max_kp, pairs_dev, matches_dev, match_counts_dev, u_dev,
                      iters, threshold, pose_dev, result_dev, mask_dev);
   f->mark(7);
-  f->timed[2] = f->timing;
-  RGBID_HIPC(hipGetLastError());
+  f->timed[2] = f->timer.on;
+  RGBID_HIP(hipGetLastError());
   return RGBID_OK;
 }
 
@@ -898,8 +879,8 @@ int rgbid_loopfeat_timing_pyramid(rgbid_loopfeat* f, float* ms) {
   (void)hipSetDevice(f->ctx->device);
   *ms = 0.f;
   if (f->timed[3]) {
-    RGBID_HIPC(hipEventSynchronize(f->ev[9]));
-    RGBID_HIPC(hipEventElapsedTime(ms, f->ev[8], f->ev[9]));
+    RGBID_HIP(hipEventSynchronize(f->timer.ev[9]));
+    RGBID_HIP(f->timer.elapsed(8, 9, ms));
   }
   return RGBID_OK;
 }
@@ -912,14 +893,11 @@ int rgbid_loopfeat_timing(rgbid_loopfeat* f, int enable, float ms[5]) {
     const int a[5] = {0, 1, 2, 4, 6}, grp[5] = {0, 0, 0, 1, 2};
     for (int i = 0; i < 5; ++i)
       if (f->timed[grp[i]]) {
-        RGBID_HIPC(hipEventSynchronize(f->ev[a[i] + 1]));
-        RGBID_HIPC(hipEventElapsedTime(&ms[i], f->ev[a[i]], f->ev[a[i] + 1]));
+        RGBID_HIP(hipEventSynchronize(f->timer.ev[a[i] + 1]));
+        RGBID_HIP(f->timer.elapsed(a[i], a[i] + 1, &ms[i]));
       }
   }
-  if (enable && !f->ev[0])
-    for (hipEvent_t& e : f->ev) RGBID_HIPC(hipEventCreate(&e));
-  f->timing = enable != 0;
-  return RGBID_OK;
+  return f->timer.enable(enable != 0);
 }
 
 }  // extern "C"

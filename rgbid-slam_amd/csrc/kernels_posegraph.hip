@@ -21,7 +21,7 @@
 // its poses stay at the last completed iteration.
 #include "../../include/rgbid_posegraph.h"
 #include "common.h"
-#include "ctx.h"
+#include "hip_host.h"
 #include "../../include/rgbid/so3r3.h"
 
 #include <algorithm>
@@ -595,12 +595,6 @@ __global__ void __launch_bounds__(PG_RT) k_pg_chi2_sum(const int2* __restrict__ 
 
 int pg_grid(long long items, int threads) { return (int)((items + threads - 1) / threads); }
 
-#define PG_HIPC(expr)                                                  \
-  do {                                                                 \
-    hipError_t e_ = (expr);                                            \
-    if (e_ != hipSuccess) { (void)hipGetLastError(); return (int)e_; } \
-  } while (0)
-
 // ---- host: the structure of one stage of all graphs ----
 struct Stage {
   std::vector<int> lin_edge;            // active edges (global ids), graph by graph in edge order
@@ -928,9 +922,8 @@ int rgbid_pg_optimise(rgbid_pg* p, int ng, const rgbid_pg_graph* graphs, double*
   (void)hipSetDevice(p->ctx->device);
   hipStream_t s = p->ctx->stream;
   if (off > p->ws_cap) {
-    if (p->ws) { PG_HIPC(hipStreamSynchronize(s)); (void)hipFree(p->ws); p->ws = nullptr; p->ws_cap = 0; }
-    hipError_t e = hipMalloc(&p->ws, off);
-    if (e != hipSuccess) { (void)hipGetLastError(); p->ws = nullptr; return e == hipErrorOutOfMemory ? RGBID_E_NOMEM : (int)e; }
+    if (p->ws) { RGBID_HIP(hipStreamSynchronize(s)); (void)hipFree(p->ws); p->ws = nullptr; p->ws_cap = 0; }
+    if (int r = hip_alloc(&p->ws, off)) return r;
     p->ws_cap = off;
   }
   char* w = (char*)p->ws;
@@ -946,9 +939,9 @@ int rgbid_pg_optimise(rgbid_pg* p, int ng, const rgbid_pg_graph* graphs, double*
       if (!p->span[q] && hipEventCreate(&p->span[q]) != hipSuccess) { (void)hipGetLastError(); p->span[q] = nullptr; }
     if (p->span[0]) (void)hipEventRecord(p->span[0], s);
   }
-  PG_HIPC(hipMemcpyAsync(d_poses, poses, sizeof(double) * 12 * V, hipMemcpyHostToDevice, s));
-  PG_HIPC(hipMemcpyAsync(d_edges, ed.data(), sizeof(PgEdgeDev) * ed.size(), hipMemcpyHostToDevice, s));
-  PG_HIPC(hipMemsetAsync(d_failed, 0, sizeof(int) * ng, s));
+  RGBID_HIP(hipMemcpyAsync(d_poses, poses, sizeof(double) * 12 * V, hipMemcpyHostToDevice, s));
+  RGBID_HIP(hipMemcpyAsync(d_edges, ed.data(), sizeof(PgEdgeDev) * ed.size(), hipMemcpyHostToDevice, s));
+  RGBID_HIP(hipMemsetAsync(d_failed, 0, sizeof(int) * ng, s));
   // ---- timing ----
   p->launches = 0;
   for (double& m : p->ms) m = 0;
@@ -968,15 +961,15 @@ int rgbid_pg_optimise(rgbid_pg* p, int ng, const rgbid_pg_graph* graphs, double*
   };
   // chi2 before: over the first stage's active edges; after: over the last stage's (g2o's activeChi2 of the level it initialised).  The
   // tables are pageable uploads, ordered on the stream before the launches that read them.
-  PG_HIPC(hipMemsetAsync(d_chiout, 0, sizeof(double) * 2 * ng, s));
+  RGBID_HIP(hipMemsetAsync(d_chiout, 0, sizeof(double) * 2 * ng, s));
   auto chi_pass = [&](int which, const Stage& st) -> int {
     const int n = (int)st.lin_edge.size();
     if (n == 0) return RGBID_OK;
-    PG_HIPC(hipMemcpyAsync(d_chiidx, st.lin_edge.data(), sizeof(int) * n, hipMemcpyHostToDevice, s));
-    PG_HIPC(hipMemcpyAsync(d_rng, st.chi_rng.data(), sizeof(int2) * ng, hipMemcpyHostToDevice, s));
+    RGBID_HIP(hipMemcpyAsync(d_chiidx, st.lin_edge.data(), sizeof(int) * n, hipMemcpyHostToDevice, s));
+    RGBID_HIP(hipMemcpyAsync(d_rng, st.chi_rng.data(), sizeof(int2) * ng, hipMemcpyHostToDevice, s));
     timed(5, [&] { hipLaunchKernelGGL(k_pg_chi2_edges, dim3(pg_grid(n, PG_T)), dim3(PG_T), 0, s, d_edges, d_chiidx, n, d_poses, d_chi); });
     timed(5, [&] { hipLaunchKernelGGL(k_pg_chi2_sum, dim3(ng), dim3(PG_RT), 0, s, d_rng, d_chi, d_chiout, which); });
-    return hipStreamSynchronize(s) == hipSuccess ? RGBID_OK : (int)hipGetLastError();   // the next upload reuses the tables
+    return hip_status(hipStreamSynchronize(s));   // the next upload reuses the tables
   };
   { const int r = chi_pass(0, stages.front()); if (r) return r; }
   p->reduced_flops = p->lin_bytes = p->seg_bytes = 0;
@@ -998,17 +991,17 @@ int rgbid_pg_optimise(rgbid_pg* p, int ng, const rgbid_pg_graph* graphs, double*
     PgEnvC* d_ec = (PgEnvC*)(w + o_ec);
     double *d_renv = (double*)(w + o_renv), *d_env = (double*)(w + o_env);
     auto up = [&](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess; };
-    PG_HIPC(up(d_linedge, st.lin_edge.data(), sizeof(int) * st.lin_edge.size()));
-    PG_HIPC(up(d_fr, st.fr.data(), sizeof(PgFree) * st.fr.size()));
-    PG_HIPC(up(d_inc, st.inc.data(), sizeof(PgInc) * st.inc.size()));
-    PG_HIPC(up(d_sepidx, st.sep_idx.data(), sizeof(int) * st.sep_idx.size()));
-    PG_HIPC(up(d_seg, st.seg.data(), sizeof(PgSeg) * st.seg.size()));
-    PG_HIPC(up(d_gst, st.gst.data(), sizeof(PgGraphStage) * st.gst.size()));
-    PG_HIPC(up(d_sep, st.sep_slot.data(), sizeof(int) * st.sep_slot.size()));
-    PG_HIPC(up(d_sse, st.sse.data(), sizeof(PgSse) * st.sse.size()));
-    PG_HIPC(up(d_eg, st.eg.data(), sizeof(PgEnvGraph) * st.eg.size()));
-    PG_HIPC(up(d_erow, st.erow.data(), sizeof(PgEnvRow) * st.erow.size()));
-    PG_HIPC(up(d_ec, st.ec.data(), sizeof(PgEnvC) * st.ec.size()));
+    RGBID_HIP(up(d_linedge, st.lin_edge.data(), sizeof(int) * st.lin_edge.size()));
+    RGBID_HIP(up(d_fr, st.fr.data(), sizeof(PgFree) * st.fr.size()));
+    RGBID_HIP(up(d_inc, st.inc.data(), sizeof(PgInc) * st.inc.size()));
+    RGBID_HIP(up(d_sepidx, st.sep_idx.data(), sizeof(int) * st.sep_idx.size()));
+    RGBID_HIP(up(d_seg, st.seg.data(), sizeof(PgSeg) * st.seg.size()));
+    RGBID_HIP(up(d_gst, st.gst.data(), sizeof(PgGraphStage) * st.gst.size()));
+    RGBID_HIP(up(d_sep, st.sep_slot.data(), sizeof(int) * st.sep_slot.size()));
+    RGBID_HIP(up(d_sse, st.sse.data(), sizeof(PgSse) * st.sse.size()));
+    RGBID_HIP(up(d_eg, st.eg.data(), sizeof(PgEnvGraph) * st.eg.size()));
+    RGBID_HIP(up(d_erow, st.erow.data(), sizeof(PgEnvRow) * st.erow.size()));
+    RGBID_HIP(up(d_ec, st.ec.data(), sizeof(PgEnvC) * st.ec.size()));
     // the stage uploads read pageable host vectors: they complete before the call returns, and the vectors outlive it
     const int nl = (int)st.lin_edge.size(), nf = (int)st.fr.size(), nsg = (int)st.seg.size(), ngs = (int)st.gst.size();
     const int neg_ = (int)st.eg.size(), ner = (int)st.erow.size();
@@ -1030,18 +1023,18 @@ int rgbid_pg_optimise(rgbid_pg* p, int ng, const rgbid_pg_graph* graphs, double*
       if (nsg) timed(4, [&] { hipLaunchKernelGGL(k_pg_backsub, dim3(pg_grid(nsg, PG_T)), dim3(PG_T), 0, s, d_seg, nsg, d_segv, d_failed, d_delta); });
       timed(4, [&] { hipLaunchKernelGGL(k_pg_update, dim3(pg_grid(nf, PG_T)), dim3(PG_T), 0, s, d_fr, nf, d_delta, d_failed, d_poses); });
     }
-    PG_HIPC(hipGetLastError());
-    PG_HIPC(hipStreamSynchronize(s));   // the next stage's uploads overwrite this stage's tables
+    RGBID_HIP(hipGetLastError());
+    RGBID_HIP(hipStreamSynchronize(s));   // the next stage's uploads overwrite this stage's tables
   }
   { const int r = chi_pass(1, stages.back()); if (r) return r; }
-  PG_HIPC(hipGetLastError());
-  PG_HIPC(hipMemcpyAsync(poses, d_poses, sizeof(double) * 12 * V, hipMemcpyDeviceToHost, s));
+  RGBID_HIP(hipGetLastError());
+  RGBID_HIP(hipMemcpyAsync(poses, d_poses, sizeof(double) * 12 * V, hipMemcpyDeviceToHost, s));
   std::vector<int> fl(ng);
   std::vector<double> co(2 * ng, 0.0);
-  PG_HIPC(hipMemcpyAsync(fl.data(), d_failed, sizeof(int) * ng, hipMemcpyDeviceToHost, s));
-  PG_HIPC(hipMemcpyAsync(co.data(), d_chiout, sizeof(double) * 2 * ng, hipMemcpyDeviceToHost, s));
+  RGBID_HIP(hipMemcpyAsync(fl.data(), d_failed, sizeof(int) * ng, hipMemcpyDeviceToHost, s));
+  RGBID_HIP(hipMemcpyAsync(co.data(), d_chiout, sizeof(double) * 2 * ng, hipMemcpyDeviceToHost, s));
   if (p->timing && p->span[1]) (void)hipEventRecord(p->span[1], s);
-  PG_HIPC(hipStreamSynchronize(s));
+  RGBID_HIP(hipStreamSynchronize(s));
   p->ms[6] = 0;
   if (p->timing && p->span[0] && p->span[1]) {
     float t = 0;

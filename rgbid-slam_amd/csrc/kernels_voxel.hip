@@ -14,7 +14,7 @@
 // Keys are 32-bit when the largest key + 1 < 2^32 (a 1 cm room map), 64-bit otherwise.
 #include "../../include/rgbid_voxel.h"
 #include "common.h"
-#include "ctx.h"
+#include "hip_host.h"
 
 #include <cmath>
 #include <cstddef>
@@ -400,29 +400,15 @@ struct rgbid_voxel {
   const unsigned* vend = nullptr;
   unsigned long long voxels = 0;
   // stage timing (rgbid_voxel_timing): box [0, 1], keys [2, 3], sort [3, 4], runs [4, 5], emit [6, 7]
-  bool timing = false, plan_timed = false, emit_timed = false;
-  hipEvent_t ev[8] = {};
-  void mark(int i) { if (timing) (void)hipEventRecord(ev[i], ctx->stream); }
+  bool plan_timed = false, emit_timed = false;
+  Buffers buf;
+  StageTimer<8> timer;
+  void mark(int i) { timer.mark(i, ctx->stream); }
 };
 
 namespace {
 
-// a failed allocation is reported through the return value and the runtime's sticky last error is cleared (kernels_cloud.hip)
-int vox_alloc(void** p, size_t bytes, bool host) {
-  hipError_t e = host ? hipHostMalloc(p, bytes, hipHostMallocDefault) : hipMalloc(p, bytes);
-  if (e == hipSuccess) return RGBID_OK;
-  (void)hipGetLastError();
-  *p = nullptr;
-  return e == hipErrorOutOfMemory ? RGBID_E_NOMEM : (int)e;
-}
-
 unsigned grid_of(unsigned long long items) { return items < VOX_MAX_GRID ? (unsigned)(items ? items : 1) : VOX_MAX_GRID; }
-
-#define RGBID_HIPC(expr)                                               \
-  do {                                                                 \
-    hipError_t e_ = (expr);                                            \
-    if (e_ != hipSuccess) { (void)hipGetLastError(); return (int)e_; } \
-  } while (0)
 
 int bitlen(unsigned long long x) { return x ? 64 - __builtin_clzll(x) : 0; }
 
@@ -492,7 +478,7 @@ int sort_and_runs(rgbid_voxel* v, const float4* in, unsigned n, unsigned finite,
   }
   v->mark(5);
   v->sidx = v->idx[p];
-  RGBID_HIPC(hipGetLastError());
+  RGBID_HIP(hipGetLastError());
   return RGBID_OK;
 }
 
@@ -512,15 +498,15 @@ int rgbid_voxel_create(rgbid_voxel** out, rgbid_ctx* ctx, unsigned long long max
   v->run_tiles = (unsigned)((max_points + RUN_TILE - 1) / RUN_TILE);
   const size_t cap = (size_t)max_points;
   int r = RGBID_OK;
-  for (int i = 0; i < 2 && !r; ++i) r = vox_alloc((void**)&v->keys[i], sizeof(unsigned long long) * cap, false);
-  for (int i = 0; i < 2 && !r; ++i) r = vox_alloc((void**)&v->idx[i], sizeof(unsigned) * (cap + 1), false);
-  if (!r) r = vox_alloc((void**)&v->hist, sizeof(unsigned) * RADIX * (size_t)v->sort_tiles, false);
-  if (!r) r = vox_alloc((void**)&v->dtotal, sizeof(unsigned) * RADIX, false);
-  if (!r) r = vox_alloc((void**)&v->box_part, sizeof(float) * 6 * VOX_MAX_GRID, false);
-  if (!r) r = vox_alloc((void**)&v->box_cnt, sizeof(unsigned) * VOX_MAX_GRID, false);
-  if (!r) r = vox_alloc((void**)&v->bc, sizeof(unsigned) * v->run_tiles, false);
-  if (!r) r = vox_alloc((void**)&v->slots, sizeof(unsigned) * SLOTS, false);
-  if (!r) r = vox_alloc((void**)&v->slots_host, sizeof(unsigned) * SLOTS, true);
+  for (int i = 0; i < 2 && !r; ++i) r = v->buf.alloc(&v->keys[i], sizeof(unsigned long long) * cap);
+  for (int i = 0; i < 2 && !r; ++i) r = v->buf.alloc(&v->idx[i], sizeof(unsigned) * (cap + 1));
+  if (!r) r = v->buf.alloc(&v->hist, sizeof(unsigned) * RADIX * (size_t)v->sort_tiles);
+  if (!r) r = v->buf.alloc(&v->dtotal, sizeof(unsigned) * RADIX);
+  if (!r) r = v->buf.alloc(&v->box_part, sizeof(float) * 6 * VOX_MAX_GRID);
+  if (!r) r = v->buf.alloc(&v->box_cnt, sizeof(unsigned) * VOX_MAX_GRID);
+  if (!r) r = v->buf.alloc(&v->bc, sizeof(unsigned) * v->run_tiles);
+  if (!r) r = v->buf.alloc(&v->slots, sizeof(unsigned) * SLOTS);
+  if (!r) r = v->buf.alloc_host(&v->slots_host, sizeof(unsigned) * SLOTS);
   if (r) { rgbid_voxel_destroy(v); return r; }
   *out = v;
   return RGBID_OK;
@@ -530,13 +516,7 @@ int rgbid_voxel_destroy(rgbid_voxel* v) {
   if (!v) return RGBID_OK;
   (void)hipSetDevice(v->ctx->device);
   if (v->ctx->stream) (void)hipStreamSynchronize(v->ctx->stream);   // an emit may still read the tables
-  for (void* p : {(void*)v->keys[0], (void*)v->keys[1], (void*)v->idx[0], (void*)v->idx[1], (void*)v->hist, (void*)v->dtotal,
-                  (void*)v->box_part, (void*)v->box_cnt, (void*)v->bc, (void*)v->slots})
-    if (p) (void)hipFree(p);
-  if (v->slots_host) (void)hipHostFree(v->slots_host);
-  for (hipEvent_t e : v->ev) if (e) (void)hipEventDestroy(e);
-  (void)hipGetLastError();
-  delete v;
+  delete v;   // its Buffers free the tables, its StageTimer the events
   return RGBID_OK;
 }
 
@@ -551,7 +531,7 @@ int rgbid_voxel_plan(rgbid_voxel* v, const rgbid_cloud_point* in_dev, unsigned l
   if (n == 0) return RGBID_OK;
   (void)hipSetDevice(v->ctx->device);
   hipStream_t s = v->ctx->stream;
-  RGBID_HIPC(hipStreamSynchronize(s));   // the previous emit has read the tables
+  RGBID_HIP(hipStreamSynchronize(s));   // the previous emit has read the tables
   const float4* in = reinterpret_cast<const float4*>(in_dev);
   const unsigned nu = (unsigned)n;
   const unsigned nb = grid_of((n + VT - 1) / VT);
@@ -560,9 +540,9 @@ int rgbid_voxel_plan(rgbid_voxel* v, const rgbid_cloud_point* in_dev, unsigned l
   hipLaunchKernelGGL(k_vox_box, dim3(nb), dim3(VT), 0, s, in, nu, v->box_part, v->box_cnt);
   hipLaunchKernelGGL(k_vox_box_final, dim3(1), dim3(64), 0, s, v->box_part, v->box_cnt, (int)nb, v->slots);
   v->mark(1);
-  RGBID_HIPC(hipGetLastError());
-  RGBID_HIPC(hipMemcpyAsync(v->slots_host, v->slots, sizeof(unsigned) * SLOTS, hipMemcpyDeviceToHost, s));
-  RGBID_HIPC(hipStreamSynchronize(s));
+  RGBID_HIP(hipGetLastError());
+  RGBID_HIP(hipMemcpyAsync(v->slots_host, v->slots, sizeof(unsigned) * SLOTS, hipMemcpyDeviceToHost, s));
+  RGBID_HIP(hipStreamSynchronize(s));
   const unsigned finite = v->slots_host[SLOT_FINITE];
   if (stats) stats[0] = finite;
   if (finite == 0) return RGBID_OK;
@@ -577,15 +557,15 @@ int rgbid_voxel_plan(rgbid_voxel* v, const rgbid_cloud_point* in_dev, unsigned l
   const int e = g.sentinel < (1ull << 32) ? sort_and_runs<unsigned>(v, in, nu, finite, g, min_points)
                                           : sort_and_runs<unsigned long long>(v, in, nu, finite, g, min_points);
   if (e) return e;
-  RGBID_HIPC(hipMemcpyAsync(v->slots_host, v->slots, sizeof(unsigned) * SLOTS, hipMemcpyDeviceToHost, s));
-  RGBID_HIPC(hipStreamSynchronize(s));
+  RGBID_HIP(hipMemcpyAsync(v->slots_host, v->slots, sizeof(unsigned) * SLOTS, hipMemcpyDeviceToHost, s));
+  RGBID_HIP(hipStreamSynchronize(s));
   const unsigned runs = v->slots_host[SLOT_RUNS];
   const unsigned vox = min_points > 1 ? v->slots_host[SLOT_VOXELS] : runs;
   if (stats) { stats[1] = runs; stats[2] = vox; }
   *voxels = vox;
   v->voxels = vox;
   v->in = in_dev;
-  v->plan_timed = v->timing;
+  v->plan_timed = v->timer.on;
   return RGBID_OK;
 }
 
@@ -599,8 +579,8 @@ int rgbid_voxel_emit(rgbid_voxel* v, rgbid_voxel_point* out_dev, unsigned long l
   hipLaunchKernelGGL(k_vox_emit, dim3((nv + VT - 1) / VT), dim3(VT), 0, v->ctx->stream, reinterpret_cast<const uint4*>(v->in), v->sidx, v->vbeg,
                      v->vend, nv, reinterpret_cast<uint4*>(out_dev));
   v->mark(7);
-  RGBID_HIPC(hipGetLastError());
-  v->emit_timed = v->timing;
+  RGBID_HIP(hipGetLastError());
+  v->emit_timed = v->timer.on;
   return RGBID_OK;
 }
 
@@ -611,13 +591,10 @@ int rgbid_voxel_timing(rgbid_voxel* v, int enable, float ms[5]) {
     static const int pair[5][2] = {{0, 1}, {2, 3}, {3, 4}, {4, 5}, {6, 7}};
     for (int k = 0; k < 5; ++k) {
       ms[k] = 0.f;
-      if ((k < 4 && v->plan_timed) || (k == 4 && v->emit_timed)) RGBID_HIPC(hipEventElapsedTime(&ms[k], v->ev[pair[k][0]], v->ev[pair[k][1]]));
+      if ((k < 4 && v->plan_timed) || (k == 4 && v->emit_timed)) RGBID_HIP(v->timer.elapsed(pair[k][0], pair[k][1], &ms[k]));
     }
   }
-  if (enable && !v->ev[0])
-    for (int i = 0; i < 8; ++i) RGBID_HIPC(hipEventCreate(&v->ev[i]));
-  v->timing = enable != 0;
-  return RGBID_OK;
+  return v->timer.enable(enable != 0);
 }
 
 }  // extern "C"

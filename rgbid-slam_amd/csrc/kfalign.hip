@@ -10,17 +10,12 @@
 // What is NOT computed: the intensity channel's residual lattice and its nu -- the reference estimates nu_intensity and then passes nu_depthinv for both
 // channels (:300-308), so that work has no consumer (two launches per iteration).
 #include "../../include/rgbid_kfalign.h"
-#include "ctx.h"
+#include "hip_host.h"
 #include "kernels.h"
 #include "../../include/rgbid/se3.h"
 
 #include <cstring>
 #include <new>
-#include <vector>
-
-// The per-lane scalar kernels hold 6x6 / 3x3 double matrices in registers: one wave per SIMD may take the whole register file (the default budget of 128
-// VGPRs spilled 660 - 1 250 bytes per thread to scratch, and dependent scratch round trips were most of these kernels' run time)
-#define RGBID_SCALAR_KERNEL __attribute__((amdgpu_waves_per_eu(1, 1)))
 
 #pragma clang fp contract(off)   // the per-pair scalar kernels below: operation by operation, as the host loop of KeyframeAlign (g++, no contraction)
 
@@ -141,8 +136,7 @@ __global__ __launch_bounds__(64) RGBID_SCALAR_KERNEL void k_kfa_finish(const Kfa
 struct rgbid_kfalign {
   rgbid_ctx* ctx = nullptr;
   int rows = 0, cols = 0, cap = 0;
-  std::vector<void*> allocs;
-  size_t bytes = 0;
+  Buffers buf;
   ImgB iD_ini[KFA_LEVELS], I_ini[KFA_LEVELS], iD_end[KFA_LEVELS], I_end[KFA_LEVELS], W1[KFA_LEVELS], I1[KFA_LEVELS];
   ImgB gxD[KFA_LEVELS], gyD[KFA_LEVELS], gxI[KFA_LEVELS], gyI[KFA_LEVELS];
   unsigned char *grey_a = nullptr, *grey_b = nullptr;   // dense staging of the two grey images
@@ -157,18 +151,10 @@ struct rgbid_kfalign {
 
 namespace {
 
-int kfa_alloc(rgbid_kfalign* a, void** p, size_t bytes) {
-  hipError_t err = hipMalloc(p, bytes);
-  if (err != hipSuccess) return err == hipErrorOutOfMemory ? RGBID_E_NOMEM : (int)err;
-  a->allocs.push_back(*p);
-  a->bytes += bytes;
-  return RGBID_OK;
-}
 int kfa_img(rgbid_kfalign* a, ImgB* im, int rows, int cols) {
   const size_t pitch = ((size_t)cols * 4 + 255) & ~(size_t)255, lane_stride = pitch * rows;
   void* p = nullptr;
-  int r = kfa_alloc(a, &p, lane_stride * a->cap);
-  if (r) return r;
+  if (int r = a->buf.alloc(&p, lane_stride * a->cap)) return r;
   *im = ImgB{p, pitch, lane_stride, rows, cols};
   return RGBID_OK;
 }
@@ -204,18 +190,18 @@ int rgbid_kfalign_create(rgbid_kfalign** out, rgbid_ctx* ctx, int rows, int cols
     }
   }
   const size_t N = (size_t)rows * cols, B = (size_t)max_pairs;
-  if (!r) r = kfa_alloc(a, (void**)&a->grey_a, N * B);
-  if (!r) r = kfa_alloc(a, (void**)&a->grey_b, N * B);
-  if (!r) r = kfa_alloc(a, (void**)&a->res, sizeof(float) * a->res_cap * B);
-  if (!r) r = kfa_alloc(a, (void**)&a->partials, sizeof(double) * SYS_TERMS * (size_t)a->nblk_cap * B);
-  if (!r) r = kfa_alloc(a, (void**)&a->state, sizeof(KfaState) * B);
-  if (!r) r = kfa_alloc(a, (void**)&a->wp, sizeof(WarpParams) * B);
-  if (!r) r = kfa_alloc(a, (void**)&a->sp, sizeof(SysParams) * B);
-  if (!r) r = kfa_alloc(a, (void**)&a->io, sizeof(SigmaIO) * B);
-  if (!r) r = kfa_alloc(a, (void**)&a->R_dev, sizeof(double) * 9 * B);
-  if (!r) r = kfa_alloc(a, (void**)&a->t_dev, sizeof(double) * 3 * B);
-  if (!r) r = kfa_alloc(a, (void**)&a->cov_dev, sizeof(double) * 36 * B);
-  if (!r) r = kfa_alloc(a, (void**)&a->K_dev, sizeof(float) * 4 * B);
+  if (!r) r = a->buf.alloc(&a->grey_a, N * B);
+  if (!r) r = a->buf.alloc(&a->grey_b, N * B);
+  if (!r) r = a->buf.alloc(&a->res, sizeof(float) * a->res_cap * B);
+  if (!r) r = a->buf.alloc(&a->partials, sizeof(double) * SYS_TERMS * (size_t)a->nblk_cap * B);
+  if (!r) r = a->buf.alloc(&a->state, sizeof(KfaState) * B);
+  if (!r) r = a->buf.alloc(&a->wp, sizeof(WarpParams) * B);
+  if (!r) r = a->buf.alloc(&a->sp, sizeof(SysParams) * B);
+  if (!r) r = a->buf.alloc(&a->io, sizeof(SigmaIO) * B);
+  if (!r) r = a->buf.alloc(&a->R_dev, sizeof(double) * 9 * B);
+  if (!r) r = a->buf.alloc(&a->t_dev, sizeof(double) * 3 * B);
+  if (!r) r = a->buf.alloc(&a->cov_dev, sizeof(double) * 36 * B);
+  if (!r) r = a->buf.alloc(&a->K_dev, sizeof(float) * 4 * B);
   if (r) { rgbid_kfalign_destroy(a); return r; }
   *out = a;
   return RGBID_OK;
@@ -225,8 +211,7 @@ int rgbid_kfalign_destroy(rgbid_kfalign* a) {
   if (!a) return RGBID_OK;
   hipSetDevice(a->ctx->device);
   hipStreamSynchronize(a->ctx->stream);
-  for (void* p : a->allocs) hipFree(p);
-  delete a;
+  delete a;   // its Buffers free the maps
   return RGBID_OK;
 }
 
@@ -240,10 +225,9 @@ int rgbid_kfalign_batched(rgbid_kfalign* a, int pairs, const float* iD_ini_dev, 
   a->launches = 0;
   for (int l = 0; l < KFA_LEVELS; ++l)   // the normal equations' launch plan of THIS pair count must fit the partials buffer (sized at creation)
     if (system_blocks_per_lane(rows >> l, cols >> l, B) > a->nblk_cap) return RGBID_E_INVALID;
-#define KFA_HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return (int)e_; } while (0)
-  KFA_HIP(hipMemcpyAsync(a->R_dev, R, sizeof(double) * 9 * B, hipMemcpyHostToDevice, s));
-  KFA_HIP(hipMemcpyAsync(a->t_dev, t, sizeof(double) * 3 * B, hipMemcpyHostToDevice, s));
-  KFA_HIP(hipMemcpyAsync(a->K_dev, K, sizeof(float) * 4 * B, hipMemcpyHostToDevice, s));
+  RGBID_HIP(hipMemcpyAsync(a->R_dev, R, sizeof(double) * 9 * B, hipMemcpyHostToDevice, s));
+  RGBID_HIP(hipMemcpyAsync(a->t_dev, t, sizeof(double) * 3 * B, hipMemcpyHostToDevice, s));
+  RGBID_HIP(hipMemcpyAsync(a->K_dev, K, sizeof(float) * 4 * B, hipMemcpyHostToDevice, s));
   // level 0: the inverse-depth maps into the aligner's pitched buffers, the grey images converted to float (:120-129)
   launch_copy_bytes(s, B, dense_view(iD_ini_dev, rows, cols, 4), a->iD_ini[0], 4, ALL);
   launch_copy_bytes(s, B, dense_view(iD_end_dev, rows, cols, 4), a->iD_end[0], 4, ALL);
@@ -285,11 +269,11 @@ int rgbid_kfalign_batched(rgbid_kfalign* a, int pairs, const float* iD_ini_dev, 
   }
   hipLaunchKernelGGL(k_kfa_finish, dim3(gb), dim3(tb), 0, s, a->state, a->R_dev, a->t_dev, a->cov_dev, B);
   a->launches += 1;
-  KFA_HIP(hipGetLastError());
-  KFA_HIP(hipMemcpyAsync(R, a->R_dev, sizeof(double) * 9 * B, hipMemcpyDeviceToHost, s));
-  KFA_HIP(hipMemcpyAsync(t, a->t_dev, sizeof(double) * 3 * B, hipMemcpyDeviceToHost, s));
-  KFA_HIP(hipMemcpyAsync(cov, a->cov_dev, sizeof(double) * 36 * B, hipMemcpyDeviceToHost, s));
-  KFA_HIP(hipStreamSynchronize(s));
+  RGBID_HIP(hipGetLastError());
+  RGBID_HIP(hipMemcpyAsync(R, a->R_dev, sizeof(double) * 9 * B, hipMemcpyDeviceToHost, s));
+  RGBID_HIP(hipMemcpyAsync(t, a->t_dev, sizeof(double) * 3 * B, hipMemcpyDeviceToHost, s));
+  RGBID_HIP(hipMemcpyAsync(cov, a->cov_dev, sizeof(double) * 36 * B, hipMemcpyDeviceToHost, s));
+  RGBID_HIP(hipStreamSynchronize(s));
   return RGBID_OK;
 }
 
@@ -300,19 +284,18 @@ int rgbid_kfalign_batched_host(rgbid_kfalign* a, int pairs, const float* iD_ini,
   hipStream_t s = a->ctx->stream;
   const size_t N = (size_t)a->rows * a->cols;
   if (!a->dense_a) {   // only this entry point needs dense device staging of the inverse-depth maps
-    int r = kfa_alloc(a, (void**)&a->dense_a, sizeof(float) * N * a->cap);
-    if (!r) r = kfa_alloc(a, (void**)&a->dense_b, sizeof(float) * N * a->cap);
+    int r = a->buf.alloc(&a->dense_a, sizeof(float) * N * a->cap);
+    if (!r) r = a->buf.alloc(&a->dense_b, sizeof(float) * N * a->cap);
     if (r) return r;
   }
-  KFA_HIP(hipMemcpyAsync(a->dense_a, iD_ini, sizeof(float) * N * pairs, hipMemcpyHostToDevice, s));
-  KFA_HIP(hipMemcpyAsync(a->dense_b, iD_end, sizeof(float) * N * pairs, hipMemcpyHostToDevice, s));
-  KFA_HIP(hipMemcpyAsync(a->grey_a, grey_ini, N * pairs, hipMemcpyHostToDevice, s));
-  KFA_HIP(hipMemcpyAsync(a->grey_b, grey_end, N * pairs, hipMemcpyHostToDevice, s));
+  RGBID_HIP(hipMemcpyAsync(a->dense_a, iD_ini, sizeof(float) * N * pairs, hipMemcpyHostToDevice, s));
+  RGBID_HIP(hipMemcpyAsync(a->dense_b, iD_end, sizeof(float) * N * pairs, hipMemcpyHostToDevice, s));
+  RGBID_HIP(hipMemcpyAsync(a->grey_a, grey_ini, N * pairs, hipMemcpyHostToDevice, s));
+  RGBID_HIP(hipMemcpyAsync(a->grey_b, grey_end, N * pairs, hipMemcpyHostToDevice, s));
   return rgbid_kfalign_batched(a, pairs, a->dense_a, a->grey_a, a->dense_b, a->grey_b, K, R, t, cov);
-#undef KFA_HIP
 }
 
 int rgbid_kfalign_launches(const rgbid_kfalign* a) { return a ? a->launches : 0; }
-int rgbid_kfalign_bytes(const rgbid_kfalign* a, size_t* bytes) { if (!a || !bytes) return RGBID_E_INVALID; *bytes = a->bytes; return RGBID_OK; }
+int rgbid_kfalign_bytes(const rgbid_kfalign* a, size_t* bytes) { if (!a || !bytes) return RGBID_E_INVALID; *bytes = a->buf.bytes(); return RGBID_OK; }
 
 }  // extern "C"

@@ -56,6 +56,32 @@ def check(err):
         raise RgbidError(f"rgbid error {err}: {lib().rgbid_error_string(err).decode()}")
 
 
+class CtxHandle:
+    """A C-ABI handle created on a device.Context: it uses the context's device and stream, so it is destroyed before the context is
+    (Context.close() closes its dependents first) and never after it."""
+    _destroy = None   # name of the C destroy function
+
+    def __init__(self, ctx):
+        self.ctx, self.L, self._h = ctx, lib(), C.c_void_p()
+
+    def _created(self, err):
+        check(err)
+        self.ctx._dependents.add(self)
+
+    def close(self):
+        if self._h:
+            if self.ctx._h:   # a context that is already gone took its stream with it
+                getattr(self.L, self._destroy)(self._h)
+            self._h = None
+            self.ctx._dependents.discard(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # every symbol include/rgbid.h declares (checked by the CPU test-suite against the built library)
 EXPORTS = [
     "rgbid_version", "rgbid_error_string", "rgbid_device_count", "rgbid_get_device_prop", "rgbid_set_device", "rgbid_ctx_create", "rgbid_ctx_destroy",

@@ -49,27 +49,14 @@ def as_numpy(points):
     return np.ascontiguousarray(a).view(POINT_DTYPE).reshape(-1)
 
 
-class Cloud:
+class Cloud(_lib.CtxHandle):
     """Point-cloud builder for keyframes of rows x cols pixels, up to max_keyframes per build, on the context's stream."""
+    _destroy = "rgbid_cloud_destroy"
 
     def __init__(self, ctx, rows, cols, max_keyframes):
-        self.ctx, self.rows, self.cols, self.max_keyframes = ctx, int(rows), int(cols), int(max_keyframes)
-        self.L = _lib.lib()
-        self._h = C.c_void_p()
-        check(self.L.rgbid_cloud_create(C.byref(self._h), ctx._h, self.rows, self.cols, self.max_keyframes))
-        ctx._dependents.add(self)
-
-    def close(self):
-        if self._h:
-            if self.ctx._h:
-                self.L.rgbid_cloud_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__(ctx)
+        self.rows, self.cols, self.max_keyframes = int(rows), int(cols), int(max_keyframes)
+        self._created(self.L.rgbid_cloud_create(C.byref(self._h), ctx._h, self.rows, self.cols, self.max_keyframes))
 
     def plan(self, sources, K, mode="novel"):
         """count pass: -> offsets (uint64 [n + 1]; offsets[n] = number of points).  Synchronises."""

@@ -63,18 +63,17 @@ def default_config(**kw):
     return c
 
 
-class Engine:
+class Engine(_lib.CtxHandle):
+    _destroy = "rgbid_engine_destroy"
+
     def __init__(self, ctx: Context, cfg: EngineConfig = None, **kw):
-        self.ctx = ctx
+        super().__init__(ctx)
         self.cfg = cfg if cfg is not None else default_config(**kw)
-        self.L = _lib.lib()
         self.L.rgbid_engine_config_size.restype = C.c_size_t
         if self.L.rgbid_engine_config_size() != C.sizeof(EngineConfig):
             raise _lib.RgbidError(f"rgbid_engine_config: the library has {self.L.rgbid_engine_config_size()} bytes, this binding {C.sizeof(EngineConfig)} (rebuild / update rgbid/engine.py)")
-        self._h = C.c_void_p()
-        check(self.L.rgbid_engine_create(C.byref(self._h), ctx._h, C.byref(self.cfg)))
         self._inflight = []
-        ctx._dependents.add(self)
+        self._created(self.L.rgbid_engine_create(C.byref(self._h), ctx._h, C.byref(self.cfg)))
         assert RECORD_DTYPE.itemsize == 4 * 8 + 8 * (9 + 3 + 9 + 3 + 36 + 9 + 3 + 36), RECORD_DTYPE.itemsize
 
     @property
@@ -82,17 +81,8 @@ class Engine:
         return self.cfg.lanes
 
     def close(self):
-        if self._h:
-            if self.ctx._h:   # a context that is already gone took its stream with it; its close() destroys the engines first
-                self.L.rgbid_engine_destroy(self._h)
-            self._h = None
-            self._inflight = []
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
+        self._inflight = []
 
     def reset(self):
         check(self.L.rgbid_engine_reset(self._h))

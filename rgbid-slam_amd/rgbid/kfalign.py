@@ -10,25 +10,13 @@ from ._lib import check
 from .device import Context
 
 
-class KfAlign:
+class KfAlign(_lib.CtxHandle):
+    _destroy = "rgbid_kfalign_destroy"
+
     def __init__(self, ctx: Context, rows, cols, max_pairs):
-        self.ctx, self.rows, self.cols, self.cap = ctx, int(rows), int(cols), int(max_pairs)
-        self.L = _lib.lib()
-        self._h = C.c_void_p()
-        check(self.L.rgbid_kfalign_create(C.byref(self._h), ctx._h, self.rows, self.cols, self.cap))
-        ctx._dependents.add(self)
-
-    def close(self):
-        if self._h:
-            self.L.rgbid_kfalign_destroy(self._h)
-            self._h = None
-            self.ctx._dependents.discard(self)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__(ctx)
+        self.rows, self.cols, self.cap = int(rows), int(cols), int(max_pairs)
+        self._created(self.L.rgbid_kfalign_create(C.byref(self._h), ctx._h, self.rows, self.cols, self.cap))
 
     def align(self, iD_ini, grey_ini, iD_end, grey_end, K, R0=None, t0=None):
         """iD_*: float32 [pairs, rows, cols], grey_*: uint8 [pairs, rows, cols] -- CUDA tensors (device entry point) or numpy arrays (host entry point);

@@ -162,19 +162,21 @@ class Features:
         return self.aux.cpu().numpy().view(AUX_DTYPE).reshape(self.aux.shape[0], self.aux.shape[1])
 
 
-class LoopFeat:
+class LoopFeat(_lib.CtxHandle):
     """Feature extractor, matcher and RANSAC for keyframes of rows x cols pixels, on the context's stream.  levels > 1: features over a
     pyramid of that many images at `scale` between neighbours (self.levels lists those that exist), so that a revisit at another distance
     still matches; levels = 1 is the single-level extractor."""
+    _destroy = "rgbid_loopfeat_destroy"
 
     def __init__(self, ctx, rows, cols, max_keypoints=1000, levels=1, scale=SCALE):
-        self.ctx, self.rows, self.cols, self.max_keypoints = ctx, int(rows), int(cols), int(max_keypoints)
+        super().__init__(ctx)
+        self.rows, self.cols, self.max_keypoints = int(rows), int(cols), int(max_keypoints)
         if int(levels) == 1:
             self.cells_x, self.cells_y, self.per_cell = layout(rows, cols, max_keypoints)
         self.levels = layout_levels(rows, cols, max_keypoints, levels, scale)
         _, _, self.cells_x, self.cells_y, self.per_cell, _ = self.levels[0]
         self.scale = float(np.float32(scale))
-        self.L = L = _lib.lib()
+        L = self.L
         vp, ci = C.c_void_p, C.c_int
         L.rgbid_loopfeat_create_levels.argtypes = [vp, vp, ci, ci, ci, ci, C.c_float]
         L.rgbid_loopfeat_destroy.argtypes = [vp]
@@ -185,24 +187,9 @@ class LoopFeat:
         L.rgbid_loopfeat_match.argtypes = [vp, vp, vp, ci, vp, ci, C.c_float, vp, vp]
         L.rgbid_loopfeat_ransac.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, ci, C.c_double, vp, vp, vp]
         L.rgbid_loopfeat_timing.argtypes = [vp, ci, vp]
-        self._h = C.c_void_p()
-        check(L.rgbid_loopfeat_create_levels(C.byref(self._h), ctx._h, self.rows, self.cols, self.max_keypoints, int(levels),
-                                             C.c_float(self.scale)))
-        ctx._dependents.add(self)
+        self._created(L.rgbid_loopfeat_create_levels(C.byref(self._h), ctx._h, self.rows, self.cols, self.max_keypoints, int(levels),
+                                                     C.c_float(self.scale)))
         self.dev = f"cuda:{ctx.device}"
-
-    def close(self):
-        if self._h:
-            if self.ctx._h:
-                self.L.rgbid_loopfeat_destroy(self._h)
-            self._h = None
-            self.ctx._dependents.discard(self)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _dev(self, a, dtype):
         t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))

@@ -79,28 +79,14 @@ def choose_mode(graphs):
     return "multilevel" if all(multilevel_anchored(len(p), e) for p, e in graphs) else "single"
 
 
-class PoseGraph:
+class PoseGraph(_lib.CtxHandle):
     """Device pose-graph solver on a context's device and stream."""
 
+    _destroy = "rgbid_pg_destroy"
+
     def __init__(self, ctx):
-        self.ctx = ctx
-        self.L = _lib.lib()
-        self._h = C.c_void_p()
-        check(self.L.rgbid_pg_create(C.byref(self._h), ctx._h))
-        ctx._dependents.add(self)
-
-    def close(self):
-        if self._h:
-            if self.ctx._h:
-                self.L.rgbid_pg_destroy(self._h)
-            self._h = None
-            self.ctx._dependents.discard(self)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__(ctx)
+        self._created(self.L.rgbid_pg_create(C.byref(self._h), ctx._h))
 
     def set_timing(self, on):
         check(self.L.rgbid_pg_set_timing(self._h, int(bool(on))))

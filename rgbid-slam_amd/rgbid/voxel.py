@@ -62,30 +62,17 @@ def _records(points):
     return points
 
 
-class VoxelGrid:
+class VoxelGrid(_lib.CtxHandle):
     """Voxel-grid filter for up to max_points input records per plan, on the context's stream."""
+    _destroy = "rgbid_voxel_destroy"
 
     def __init__(self, ctx, max_points):
-        self.ctx, self.max_points = ctx, int(max_points)
-        self.L = _lib.lib()
+        super().__init__(ctx)
+        self.max_points = int(max_points)
         self.L.rgbid_voxel_create.argtypes = [C.c_void_p, C.c_void_p, C.c_ulonglong]
         self.L.rgbid_voxel_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]
         self.L.rgbid_voxel_emit.argtypes = [C.c_void_p, C.c_void_p, C.c_ulonglong]
-        self._h = C.c_void_p()
-        check(self.L.rgbid_voxel_create(C.byref(self._h), ctx._h, C.c_ulonglong(self.max_points)))
-        ctx._dependents.add(self)
-
-    def close(self):
-        if self._h:
-            if self.ctx._h:
-                self.L.rgbid_voxel_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._created(self.L.rgbid_voxel_create(C.byref(self._h), ctx._h, C.c_ulonglong(self.max_points)))
 
     def plan(self, points, leaf=0.01, min_points=0):
         """grid, sort and count pass over `points` (CUDA uint8 [M, 32] rgbid_cloud_point records) -> Plan.  Synchronises (on the context's

@@ -104,3 +104,22 @@ def test_python_engine_config_matches_the_library():
     L = _lib.lib()
     L.rgbid_engine_config_size.restype = C.c_size_t
     assert L.rgbid_engine_config_size() == C.sizeof(E.EngineConfig)
+
+
+def test_handles_share_one_host_plumbing():
+    """csrc/hip_host.h is the only place that wraps a HIP call into an early return or allocates device / pinned memory, and rgbid/_lib.py
+    (CtxHandle) the only lifetime code of the context-bound wrappers: a new feature file takes both from there instead of bringing a copy"""
+    import glob
+    csrc = os.path.join(ROOT, "rgbid-slam_amd", "csrc")
+    macros, allocs = [], []
+    for path in sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h"))):
+        name = os.path.basename(path)
+        text = open(path).read()
+        macros += [(name, m.group(1)) for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(\w+).*$", text, re.M) if "HIP" in m.group(0)]
+        if name != "hip_host.h":
+            allocs += [(name, m) for m in re.findall(r"\b(hipMalloc|hipHostMalloc|hipMallocPitch|hipMallocAsync|hipMallocManaged)\s*\(", text)]
+    assert macros == [("hip_host.h", "RGBID_HIP")], macros
+    assert not allocs, allocs
+    pkg = os.path.join(ROOT, "rgbid-slam_amd", "rgbid")
+    dels = sorted(f for f in os.listdir(pkg) if f.endswith(".py") and re.search(r"def\s+__del__", open(os.path.join(pkg, f)).read()))
+    assert dels == ["_lib.py", "device.py", "host.py"], dels
