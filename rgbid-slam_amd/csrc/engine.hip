@@ -12,9 +12,11 @@
 #include "kernels.h"
 #include "../../include/rgbid/se3.h"
 #include "engine_device.h"
+#include "step_plan.h"
 #include "sigma_device.h"   // FusedLatticeGetter: the lattice pre-pass that carries the few-lane plan's update prologue
 
 #include <algorithm>
+#include <cassert>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -566,9 +568,8 @@ struct rgbid_engine {
   char* kf_staging = nullptr;               // pinned host: header + block
   int* kf_counts_host = nullptr;            // pinned host [B]
   int steps = 0;
-  int launches = 0;
-  // algorithmic HBM bytes of the launch list, per lane (rgbid_engine_step_bytes): [0] every tracked frame, [1] extra per odometry-keyframe
-  // switch, [2] extra per integration-keyframe switch, [3] extra per frame fused into the integration keyframe
+  GnSchedule sched;                        // the Gauss-Newton iterations of a step (step_plan.h), fixed at creation
+  int launches = 0;                        // the Ledger of the last enqueued step (enqueue_step): launches and algorithmic HBM bytes per lane
   double step_bytes[4] = {0, 0, 0, 0};
   hipGraphExec_t graph_first = nullptr, graph_next = nullptr;
   bool graph_ready_first = false, graph_ready_next = false;
@@ -609,177 +610,178 @@ int alloc_img(rgbid_engine* e, ImgB* im, int rows, int cols, int elem) {
 inline LaneMask M(const int* flag) { return LaneMask{flag, 1}; }
 const LaneMask ALL{nullptr, 0};
 
-StepCfg step_cfg(const rgbid_engine_config& c) {
+StepCfg step_cfg(const rgbid_engine* e) {
+  const rgbid_engine_config& c = e->cfg;
   StepCfg s;
   s.fx = c.fx; s.fy = c.fy; s.cx = c.cx; s.cy = c.cy;
   s.levels = c.levels; s.finest_level = c.finest_level; s.motion_model = c.motion_model;
   s.max_odoKF_count = c.max_odoKF_count; s.max_integrKF_count = c.max_integrKF_count;
-  s.visratio_odo = c.visratio_odo; s.visratio_integr = c.visratio_integr; s.delta_t = nullptr;   // set by enqueue_step (engine's device copy)
+  s.visratio_odo = c.visratio_odo; s.visratio_integr = c.visratio_integr; s.delta_t = e->delta_t_dev;
   s.mestimator = c.mestimator; s.weighting = c.weighting;
-  // first level (coarse to fine) that runs at least one iteration; the covariance pass warps at the finest level
-  s.start_warp_level = c.finest_level;
-  bool any_gn = false;
-  for (int l = c.levels - 1; l >= c.finest_level; --l) if (c.iters[l] > 0) { s.start_warp_level = l; any_gn = true; break; }
-  if (c.warping == RGBID_WARP_FIRST && any_gn) s.start_warp_level = 0;  // warp-first warps the level-0 frame in every GN iteration
+  s.start_warp_level = e->sched.start_warp_level;
+  s.kf_hdr = e->kf_hdr; s.kf_cap = c.keyframe_capacity;
+  s.active = e->active_dev;   // always passed (all ones by default): the captured graphs stay valid when the mask changes
   return s;
 }
 
-// saveCurrentImagesAsOdoKeyframes (visodo.cpp:826-878) for the lanes flagged sw_odo
 inline double npx(const ImgB& im) { return (double)im.rows * im.cols; }
 
-void enqueue_save_odo_kf(rgbid_engine* e, hipStream_t s) {
+// vertex + normal maps of the fused keyframe: one pass (24 B/px written, the map read once) where the rows allow 16-byte accesses, else the reference's three
+// kernels.  Returns the launches made.
+int enqueue_kf_maps(rgbid_engine* e, hipStream_t s, LaneMask m) {
+  const IntrP K0{e->cfg.fx, e->cfg.fy, e->cfg.cx, e->cfg.cy};
+  if (launch_kf_maps(s, e->B, e->iD_integr, e->vmap, e->nmap, K0, m)) return 1;
+  launch_vmap(s, e->B, e->iD_integr, e->vmap, K0, m);
+  launch_gradient(s, e->B, e->iD_integr, e->gxD_integr, e->gyD_integr, m);
+  launch_nmap_gradients(s, e->B, e->iD_integr, e->gxD_integr, e->gyD_integr, e->nmap, K0, m);
+  return 3;
+}
+
+// saveCurrentImagesAsOdoKeyframes (visodo.cpp:826-878) for the lanes flagged sw_odo; everything here is the cost of an odometry-keyframe switch (bucket 1)
+void enqueue_save_odo_kf(rgbid_engine* e, hipStream_t s, Ledger& led) {
   const int B = e->B, L = e->L;
+  const bool filter_grads = e->cfg.image_filtering == RGBID_FILTER_GRADS;
   LaneMask m = M(e->flags.sw_odo);
-  {
-    // algorithmic bytes of a keyframe switch (bucket 1): 2 copies per level (4 B read + 4 B written per pixel; folded into the Sobel pass where possible), the lattice pack, two
-    // bilateral filters (8 B/px), the pyramid of the filtered maps, Sobel (12 B/px) of the filtered and of the unfiltered maps
-    double b = 0.0;
-    for (int i = 0; i < L; ++i) {
-      const double n = npx(e->iD_kf[i]);
-      const bool keep = e->cfg.image_filtering != RGBID_FILTER_GRADS && e->iD_kf[i].cols % 4 == 0;   // Sobel pair + copy in one pass (16 B/px)
-      if (!keep) b += 2 * 8 * n;
-      if (e->lat_res) b += 16.0 * lattice_samples(e->iD_kf[i].rows, e->iD_kf[i].cols, e->cfg.nsamples);
-      b += 2 * 12 * n;                                                            // gradients of the filtered maps
-      if (i) b += 2 * (4 * npx(e->iD_kf_f[i - 1]) + 4 * n);                       // pyrDown of the filtered maps
-      b += (e->cfg.image_filtering == RGBID_FILTER_GRADS) ? 4 * 8 * n : keep ? 2 * 16 * n : 2 * 12 * n;
-    }
-    b += 2 * 8 * npx(e->iD_kf[0]);
-    e->step_bytes[1] = b;
-  }
   // the current frame's pyramids become the keyframe's.  Where the Sobel pair of the unfiltered maps is taken anyway it writes the copy as well (one
-  // read of the map instead of two, one launch instead of two per map and level); the gradients of those levels are done then, not at the end
+  // read of the map instead of two, one launch instead of two per map and level: 16 B/px per map); the gradients of those levels are done then, not at the end
   bool kept[MAXL] = {};
   for (int i = 0; i < L; ++i) {
-    if (e->cfg.image_filtering != RGBID_FILTER_GRADS)
-      kept[i] = launch_gradient_keep2(s, B, e->I_curr[i], e->gxI[i], e->gyI[i], e->I_kf[i], e->iD_curr[i], e->gxD[i], e->gyD[i], e->iD_kf[i], m);
-    if (kept[i]) e->launches += 1;
+    const double n = npx(e->iD_kf[i]);
+    kept[i] = !filter_grads && launch_gradient_keep2(s, B, e->I_curr[i], e->gxI[i], e->gyI[i], e->I_kf[i], e->iD_curr[i], e->gxD[i], e->gyD[i], e->iD_kf[i], m);
+    if (kept[i]) led.add(1, 1, 2 * 16 * n);
     else {
       launch_copy_bytes(s, B, e->iD_curr[i], e->iD_kf[i], 4, m);
       launch_copy_bytes(s, B, e->I_curr[i], e->I_kf[i], 4, m);
-      e->launches += 2;
+      led.add(2, 1, 2 * 8 * n);
     }
   }
   if (e->lat_res) {
+    double ns = 0.0;
+    for (int i = 0; i < L; ++i) ns += lattice_samples(e->iD_kf[i].rows, e->iD_kf[i].cols, e->cfg.nsamples);
     launch_lattice_pack_levels(s, B, L, e->iD_kf, e->I_kf, e->cfg.nsamples, e->lat_kf, 2 * e->lat_cap, m);
-    e->launches += (L + 3) / 4;
+    led.add((L + 3) / 4, 1, 16 * ns);   // one launch per four levels (kernels_sigma.hip)
   }
   launch_bilateral2(s, B, e->iD_kf[0], e->iD_kf_f[0], 2.f * 0.0025f, e->I_kf[0], e->I_kf_f[0], 3.f, m, e->cfg.fast_numerics != 0);
-  launch_gradient2(s, B, e->I_kf_f[0], e->gxI_c[0], e->gyI_c[0], e->iD_kf_f[0], e->gxD_c[0], e->gyD_c[0], m);
-  e->launches += 2;
-  for (int i = 1; i < L; ++i) {
-    launch_pyr_down2(s, B, e->iD_kf_f[i - 1], e->iD_kf_f[i], e->I_kf_f[i - 1], e->I_kf_f[i], m);
+  led.add(1, 1, 2 * 8 * npx(e->iD_kf[0]));
+  for (int i = 0; i < L; ++i) {
+    if (i) {
+      launch_pyr_down2(s, B, e->iD_kf_f[i - 1], e->iD_kf_f[i], e->I_kf_f[i - 1], e->I_kf_f[i], m);
+      led.add(1, 1, 2 * (4 * npx(e->iD_kf_f[i - 1]) + 4 * npx(e->iD_kf_f[i])));
+    }
     launch_gradient2(s, B, e->I_kf_f[i], e->gxI_c[i], e->gyI_c[i], e->iD_kf_f[i], e->gxD_c[i], e->gyD_c[i], m);
-    e->launches += 2;
+    led.add(1, 1, 2 * 12 * npx(e->iD_kf_f[i]));   // Sobel: 12 B/px per map
   }
   for (int i = 0; i < L; ++i) {
-    if (e->cfg.image_filtering == RGBID_FILTER_GRADS) {
+    if (filter_grads) {
       launch_copy_bytes(s, B, e->gxI_c[i], e->gxI[i], 4, m); launch_copy_bytes(s, B, e->gyI_c[i], e->gyI[i], 4, m);
       launch_copy_bytes(s, B, e->gxD_c[i], e->gxD[i], 4, m); launch_copy_bytes(s, B, e->gyD_c[i], e->gyD[i], 4, m);
-      e->launches += 4;
+      led.add(4, 1, 4 * 8 * npx(e->iD_kf[i]));
     } else if (!kept[i]) {
       launch_gradient2(s, B, e->I_kf[i], e->gxI[i], e->gyI[i], e->iD_kf[i], e->gxD[i], e->gyD[i], m);
-      e->launches += 1;
+      led.add(1, 1, 2 * 12 * npx(e->iD_kf[i]));
     }
   }
 }
 
-// the whole step as a launch sequence on stream s
+// the whole step as a launch sequence on stream s.  This function and enqueue_save_odo_kf ARE the step's launch list: every launch states its cost to the
+// step's Ledger where it is enqueued, the Gauss-Newton iterations come from e->sched, and nothing else writes e->launches / e->step_bytes.
 int enqueue_step(rgbid_engine* e, hipStream_t s, bool first) {
   const rgbid_engine_config& c = e->cfg;
   const int B = e->B, L = e->L;
-  StepCfg sc_ = step_cfg(c);
-  sc_.kf_hdr = e->kf_hdr; sc_.kf_cap = c.keyframe_capacity;
-  sc_.delta_t = e->delta_t_dev;
-  sc_.active = e->active_dev;   // always passed (all ones by default): the captured graphs stay valid when the mask changes
-  const StepCfg sc = sc_;
-  const IntrP K0{c.fx, c.fy, c.cx, c.cy};
+  const StepCfg sc = step_cfg(e);
   const int tb = 64, gb = div_up(B, tb);
+  const double N0 = (double)c.rows * c.cols;
+  const size_t res_stride = (size_t)c.rows * c.cols;
+  Flags& f = e->flags;
+  Ledger led;
   // fast numerics per pyramid level, decided ONCE here for every gather kernel of the level (lattice pre-pass, warp pair, fused normal
   // equations; kernels.h gn_fast_supported): levels whose geometry does not allow the 16-byte / paired 8-byte accesses run the exact
   // kernels in BOTH the fused and the unfused path, so the two stay bit-identical to each other
   auto fast_at = [&](int level) {
     return c.fast_numerics != 0 && gn_fast_supported(e->iD_kf[level], e->I_kf[level], e->gxD[level], e->gyD[level], e->gxI[level], e->gyI[level], e->I_curr[level]);
   };
-  e->launches = 0;
-  const bool defer_maps = c.defer_keyframe_maps != 0 && !c.preview;   // the preview shades the maps every frame
-  double* const sb = e->step_bytes;
-  sb[0] = sb[2] = sb[3] = 0.0;
-  const double N0 = (double)c.rows * c.cols;
-  Flags& f = e->flags;
-  // ---- prepareImages (visodo.cpp:760-773)
+  // ---- the pieces the list uses more than once
+  // warp of the current frame's level-l maps onto the keyframe (12 B/px read, 8 written): the fast kernel where the level's class allows it, else the exact one
+  auto warp_pair = [&](int l, LaneMask m) {
+    if (!(fast_at(l) && launch_warp_pair_fast(s, B, e->iD_curr[l], e->I_curr[l], e->iD_kf[l], e->wiD[l], e->wI[l], nullptr, e->wp, c.interp_mode, m)))
+      launch_warp_pair(s, B, e->iD_curr[l], e->I_curr[l], e->iD_kf[l], e->wiD[l], e->wI[l], e->wp, c.interp_mode, m);
+    led.add(1, 0, 20 * npx(e->iD_kf[l]));
+  };
+  // full-lattice residuals of the level-l warped maps and their chi-square (visodo.cpp:1134-1146, 1411-1415)
+  auto chi_lattice = [&](int l, LaneMask m, double bytes) {
+    int n, lr, lc, st;
+    lattice_geometry(e->wI[l].rows, e->wI[l].cols, 9999999, &n, &lr, &lc, &st);
+    launch_error_lattice(s, B, e->wI[l], e->I_kf[l], e->res_I, res_stride, lr, lc, st, m);
+    launch_error_lattice(s, B, e->wiD[l], e->iD_kf[l], e->res_D, res_stride, lr, lc, st, m);
+    launch_chi_square(s, B, e->res_I, e->res_D, res_stride, n, 5.f, 0.0025f, c.mestimator, e->chi_out, m);
+    led.add(3, 0, bytes);
+  };
+  // fused keyframe's vertex / normal maps; fallback_bytes: what the three-kernel path is booked at
+  auto kf_maps = [&](LaneMask m, int bucket, double fallback_bytes) {
+    const int n = enqueue_kf_maps(e, s, m);
+    led.add(n, bucket, n == 1 ? 28 * N0 : fallback_bytes);
+  };
+  // event pair around the next normal-equation kernel while profiling (rgbid_engine_profile_begin): the level-0 launches
+  auto system_events = [&](int level) {
+    if (!(e->prof_on && level == 0 && e->prof_used + 2 <= (int)e->prof_ev.size())) return;
+    set_system_kernel_events(e->prof_ev[e->prof_used], e->prof_ev[e->prof_used + 1]);
+    e->prof_used += 2;
+  };
+  // a per-lane reduce-and-solve kernel in the workgroup size the lane count calls for (scalar_block_threads)
+  auto per_lane = [&](auto* k64, auto* k256, auto... args) {
+    const int nt = scalar_block_threads(B);
+    hipLaunchKernelGGL(nt == 64 ? k64 : k256, dim3(B), dim3(nt), 0, s, args...);
+    led.add(1);
+  };
+  // ---- prepareImages (visodo.cpp:760-773): 2 + 3 B/px read, five fp32 planes written
   const LaneMask fed = M(e->active_dev);   // lanes without a frame this step keep their current-frame pyramids untouched
-  if (c.custom_registration) {
-    // prepareImagesCustomCalibration (visodo.cpp:775-824): the converters write the DISTORTED maps; undistort the intensity (bilinear), correct the depth
-    // sensor's distortion and undistort the inverse depth (point sample), register it onto the colour camera (z-buffer splat + homography)
-    launch_prep_frame(s, B, e->cur_depth, e->cur_rgb, e->iD_dist, e->I_dist, e->r_curr, e->g_curr, e->b_curr, c.factor_depth, fed);
+  const bool custom = c.custom_registration != 0;   // the converters write the DISTORTED maps then
+  launch_prep_frame(s, B, e->cur_depth, e->cur_rgb, custom ? e->iD_dist : e->iD_curr[0], custom ? e->I_dist : e->I_curr[0], e->r_curr, e->g_curr, e->b_curr, c.factor_depth, fed);
+  led.add(1, 0, 25 * N0);
+  if (custom) {
+    // prepareImagesCustomCalibration (visodo.cpp:775-824): undistort the intensity (bilinear), correct the depth sensor's distortion and undistort the
+    // inverse depth (point sample), register it onto the colour camera (z-buffer splat + homography)
     const IntrK kc{c.fx, c.fy, c.cx, c.cy, c.rgb_dist[0], c.rgb_dist[1], c.rgb_dist[2], c.rgb_dist[3], c.rgb_dist[4]};
     const IntrK kd{c.depth_intr.fx, c.depth_intr.fy, c.depth_intr.cx, c.depth_intr.cy, c.depth_intr.k1, c.depth_intr.k2, c.depth_intr.k3, c.depth_intr.k4, c.depth_intr.k5};
     DepthDistP dp;
     dp.c1 = c.depth_dist.c1; dp.c0 = c.depth_dist.c0; dp.xshift = c.depth_dist.xshift; dp.yshift = c.depth_dist.yshift;
     for (int i = 0; i < 9; ++i) { dp.q0[i] = c.depth_dist.q0[i]; dp.q1[i] = c.depth_dist.q1[i]; }
     launch_undistort(s, B, e->I_dist, e->I_curr[0], kc, true, c.interp_mode, fed);
+    led.add(1, 0, 12 * N0);
     launch_depthinv_correction(s, B, e->iD_dist, e->iD_corr, kd, dp, fed);
+    led.add(1, 0, 8 * N0);
     launch_undistort(s, B, e->iD_corr, e->iD_prereg, kd, false, 0, fed);
+    led.add(1, 0, 8 * N0);
     launch_register_depthinv(s, B, e->iD_prereg, e->reg_f, e->reg_i, e->iD_curr[0], c.dRc_proj, c.t_dc_proj, c.cRd_proj, fed);
-    e->launches += 8;
-    sb[0] += (25 + 12 + 8 + 8 + 9 * 4 + 8 + 9 * 8 + 8) * N0;                        // converters, three per-pixel resamplings, canvas clear / splat / conversion (9 N0 texels), homography
-  } else {
-  launch_prep_frame(s, B, e->cur_depth, e->cur_rgb, e->iD_curr[0], e->I_curr[0], e->r_curr, e->g_curr, e->b_curr, c.factor_depth, fed);
-  e->launches += 1;
-  sb[0] += 25 * N0;                                                               // 2 + 3 B/px read, five fp32 planes written
+    led.add(4, 0, (9 * 4 + 8 + 9 * 8 + 8) * N0);   // canvas clear, splat, conversion (the canvases have 9 N0 texels), homography
   }
   for (int i = 1; i < L; ++i) {
     launch_pyr_down2(s, B, e->I_curr[i - 1], e->I_curr[i], e->iD_curr[i - 1], e->iD_curr[i], fed);
-    e->launches += 1;
-    sb[0] += 2 * (4 * npx(e->I_curr[i - 1]) + 4 * npx(e->I_curr[i]));
+    led.add(1, 0, 2 * (4 * npx(e->I_curr[i - 1]) + 4 * npx(e->I_curr[i])));
   }
-  // the Gauss-Newton stages of the step: the levels that iterate, coarse to fine, then the covariance pass
-  int stage_level[MAXL + 1], n_stages = 0;
-  for (int level = L - 1; level >= c.finest_level; --level) if (c.iters[level] > 0) stage_level[n_stages++] = level;
-  const int n_gn_stages = n_stages;
-  stage_level[n_stages++] = c.finest_level;   // covariance pass
-  hipLaunchKernelGGL(k_step_begin, dim3(gb), dim3(tb), 0, s, e->state, f, e->wp, e->sp, sc, B, e->counts, stage_level[0], n_gn_stages == 0 ? 1 : 0);
-  e->launches++;
-  int stage = 0;
+  hipLaunchKernelGGL(k_step_begin, dim3(gb), dim3(tb), 0, s, e->state, f, e->wp, e->sp, sc, B, e->counts, e->sched.start_sys_level, e->sched.start_sys_cov);
+  led.add(1);
   // The first step after reset() is host-known to be every lane's first frame (visodo.cpp:1994-2045): only the
   // keyframe-creation part of the sequence below is enqueued (k_step_begin has set first / sw_odo / sw_int / maps).
-  // ---- estimateVisualOdometry (visodo.cpp:1041-1281), PYR_FIRST
-  const bool chi_stop = c.termination == RGBID_CHI_SQUARED;
-  const LaneMask LV = M(f.lvl);   // the lanes iterating the current level (== f.gn unless chi_stop)
-  // few-lane plan: every update but the frame's last rides in the next iteration's lattice pre-pass (k_lattice_after_update); needs that pre-pass (fused path with
-  // estimated scales; CHI_SQUARED termination runs unfused)
-  const bool prologue_plan = c.fused_gn && c.sigma_estimator == RGBID_SIGMA_PDF && !chi_stop && e->lat_res && B <= update_prologue_max_lanes();
-  struct { bool on; int nblk, sys_level, sys_cov; } pend = {false, 0, -1, 0};
-  int pose_in_alt = 0;   // which of the lane's two pose buffers holds the working pose (0: cur_*)
-  for (int level = L - 1; !first && level >= c.finest_level; --level) {
-    int iters = c.iters[level];
-    if (iters > 0) ++stage;     // stage_level[stage]: what follows this level
-    if (chi_stop && iters > 0) { hipLaunchKernelGGL(k_level_begin, dim3(gb), dim3(tb), 0, s, f, B); e->launches++; }
-    for (int it = 0; it < iters; ++it) {
-      bool last_of_level = (it == iters - 1);
-      // level whose intrinsics project the NEXT warp: same level, the next lower level that iterates, or (after the very last
-      // iteration) the finest level for the covariance pass; warp-first always warps at level 0 inside the GN loop
-      int next_level = level;
-      if (last_of_level) {
-        next_level = c.finest_level;
-        for (int l = level - 1; l >= c.finest_level; --l) if (c.iters[l] > 0) { next_level = l; break; }
-      }
-      bool more_gn = !last_of_level;
-      for (int l = level - 1; l >= c.finest_level && !more_gn; --l) more_gn = c.iters[l] > 0;
-      if (c.warping == RGBID_WARP_FIRST) next_level = more_gn ? 0 : c.finest_level;
-      bool prof = e->prof_on && level == 0 && e->prof_used + 2 <= (int)e->prof_ev.size();
-      int nblk;
-      {
-        // one Gauss-Newton iteration: the 8 maps of unit U1 (32 B/px); unfused additionally the warp pair (12 B/px read, 8 written); the
-        // residual lattice: 36 B/sample fused (packed keyframe side 8, gathers 20, residuals written 8) + 8 read by the sigma / nu kernel,
-        // 16 B/sample read from the stored maps otherwise
-        const double nl = npx(e->iD_kf[level]);
-        const double ns = c.sigma_estimator == RGBID_SIGMA_PDF ? (double)lattice_samples(e->iD_kf[level].rows, e->iD_kf[level].cols, c.nsamples) : 0.0;
-        if (c.fused_gn) sb[0] += 32 * nl + 44 * ns;
-        else sb[0] += (c.warping == RGBID_WARP_FIRST ? 20 * N0 : 20 * nl) + 32 * nl + 16 * ns;
-      }
+  if (!first) {
+    // ---- estimateVisualOdometry (visodo.cpp:1041-1281): the iterations of e->sched, then the covariance pass
+    const bool chi_stop = c.termination == RGBID_CHI_SQUARED, warp_first = c.warping == RGBID_WARP_FIRST, pdf = c.sigma_estimator == RGBID_SIGMA_PDF;
+    const LaneMask LV = M(f.lvl), GN = M(f.gn);   // LV: the lanes iterating the current level (== f.gn unless chi_stop)
+    // few-lane plan: every update but the frame's last rides in the next iteration's lattice pre-pass (k_lattice_after_update); needs that pre-pass (fused path with
+    // estimated scales).  That launch projects the next warp with ITS level, which is the deferred update's next_level only without the WARP_FIRST rule -- and
+    // rgbid_engine_create ("e->cfg.fused_gn = 0") has taken both WARP_FIRST and CHI_SQUARED termination out of the fused path
+    assert(!(c.fused_gn && (warp_first || chi_stop)));
+    const bool prologue_plan = c.fused_gn && pdf && e->lat_res && B <= update_prologue_max_lanes();
+    struct { bool on; int nblk, sys_level, sys_cov; } pend = {false, 0, -1, 0};
+    int pose_in_alt = 0;   // which of the lane's two pose buffers holds the working pose (0: cur_*)
+    int nblk;
+    for (const GnIter& g : e->sched.iters) {
+      const int level = g.level;
+      if (chi_stop && g.it == 0) { hipLaunchKernelGGL(k_level_begin, dim3(gb), dim3(tb), 0, s, f, B); led.add(1); }
+      const double nl = npx(e->iD_kf[level]);
+      const double ns = pdf ? (double)lattice_samples(e->iD_kf[level].rows, e->iD_kf[level].cols, c.nsamples) : 0.0;
       if (c.fused_gn) {
-        if (c.sigma_estimator == RGBID_SIGMA_PDF) {
+        if (pdf) {
           if (pend.on) {
             // few-lane plan: the previous iteration's update rides in this launch (k_lattice_after_update)
             int n_, lr_, lc_, st_;
@@ -794,179 +796,120 @@ int enqueue_step(rgbid_engine* e, hipStream_t s, bool first) {
             launch_sigma_pair_fused(s, B, e->iD_curr[level], e->iD_kf[level], e->I_curr[level], e->I_kf[level], e->wp, c.interp_mode, c.nsamples,
                                     e->sp, c.mestimator, LV, fast_at(level), e->lat_res, 2 * e->lat_cap, e->lat_kf[level], 2 * e->lat_cap);
           }
-          e->launches += 2;
+          led.add(2, 0, 44 * ns);   // residual lattice: 36 B/sample (packed keyframe side 8, gathers 20, residuals written 8) + 8 read by the sigma / nu kernel
         }
-        if (prof) { set_system_kernel_events(e->prof_ev[e->prof_used], e->prof_ev[e->prof_used + 1]); e->prof_used += 2; }
+        system_events(level);
         nblk = launch_gn_fused(s, B, e->iD_kf[level], e->I_kf[level], e->gxD[level], e->gyD[level], e->gxI[level], e->gyI[level],
                                e->iD_curr[level], e->I_curr[level], e->wp, c.interp_mode, e->sp, e->partials, LV, level < 2 ? level : 2, fast_at(level),
                                c.weighting == RGBID_MIN_WEIGHT ? 0 : 1);   // k_set_sys: the Gauss-Newton iterations always estimate nu
         if (nblk < 0) return RGBID_E_INVALID;
       } else {
-        if (c.warping == RGBID_WARP_FIRST) {
+        if (warp_first) {
           // :1078-1105: warp the full-resolution frame, then reduce the WARPED maps down to the working level
           // (k_step_begin / k_solve_update project the pose with the level-0 intrinsics in this mode)
-          if (!(fast_at(0) && launch_warp_pair_fast(s, B, e->iD_curr[0], e->I_curr[0], e->iD_kf[0], e->wiD[0], e->wI[0], nullptr, e->wp, c.interp_mode, LV)))
-            launch_warp_pair(s, B, e->iD_curr[0], e->I_curr[0], e->iD_kf[0], e->wiD[0], e->wI[0], e->wp, c.interp_mode, LV);
-          e->launches += 1;
+          warp_pair(0, LV);
           for (int i = 1; i <= level; ++i) {
             launch_pyr_down(s, B, e->wI[i - 1], e->wI[i], LV);
             launch_pyr_down(s, B, e->wiD[i - 1], e->wiD[i], LV);
-            e->launches += 2;
+            led.add(2);   // (not in the byte model)
           }
         } else {
-          if (!(fast_at(level) && launch_warp_pair_fast(s, B, e->iD_curr[level], e->I_curr[level], e->iD_kf[level], e->wiD[level], e->wI[level], nullptr, e->wp, c.interp_mode, LV)))
-            launch_warp_pair(s, B, e->iD_curr[level], e->I_curr[level], e->iD_kf[level], e->wiD[level], e->wI[level], e->wp, c.interp_mode, LV);
-          e->launches += 1;
+          warp_pair(level, LV);
         }
-        if (chi_stop && it != 0) {
+        if (chi_stop && g.it != 0) {
           // :1134-1164 -- the full-lattice residuals of the LEVEL-0 warped maps (fresh with WARP_FIRST; with PYR_FIRST whatever the last level-0 warp left
-          // there, as in the reference), their chi-square, and the per-lane decision
-          int n, lr, lc, st_;
-          lattice_geometry(e->wI[0].rows, e->wI[0].cols, 9999999, &n, &lr, &lc, &st_);
-          launch_error_lattice(s, B, e->wI[0], e->I_kf[0], e->res_I, (size_t)c.rows * c.cols, lr, lc, st_, LV);
-          launch_error_lattice(s, B, e->wiD[0], e->iD_kf[0], e->res_D, (size_t)c.rows * c.cols, lr, lc, st_, LV);
-          launch_chi_square(s, B, e->res_I, e->res_D, (size_t)c.rows * c.cols, n, 5.f, 0.0025f, c.mestimator, e->chi_out, LV);
-          int after_level = c.finest_level; bool more_below = false;
-          for (int l = level - 1; l >= c.finest_level; --l) if (c.iters[l] > 0) { after_level = l; more_below = true; break; }
-          if (c.warping == RGBID_WARP_FIRST) after_level = more_below ? 0 : c.finest_level;
-          hipLaunchKernelGGL(k_chi_decide, dim3(gb), dim3(tb), 0, s, e->state, f, e->chi_out, e->wp, sc, it, after_level, B);
-          e->launches += 4;
-          sb[0] += 2 * 12 * N0 + 8 * N0;
+          // there, as in the reference), their chi-square (two lattices of 12 B/px, 8 read by the chi-square), and the per-lane decision
+          chi_lattice(0, LV, (2 * 12 + 8) * N0);
+          hipLaunchKernelGGL(k_chi_decide, dim3(gb), dim3(tb), 0, s, e->state, f, e->chi_out, e->wp, sc, g.it, g.after_level, B);
+          led.add(1);
         }
-        if (c.sigma_estimator == RGBID_SIGMA_PDF) {
+        if (pdf) {
           launch_sigma_pair(s, B, e->wiD[level], e->iD_kf[level], e->wI[level], e->I_kf[level], c.nsamples, e->sp, c.mestimator, LV);
-          e->launches++;
+          led.add(1, 0, 16 * ns);   // 16 B/sample read from the stored maps
         }
-        if (prof) { set_system_kernel_events(e->prof_ev[e->prof_used], e->prof_ev[e->prof_used + 1]); e->prof_used += 2; }
+        system_events(level);
         nblk = launch_build_system(s, B, e->iD_kf[level], e->I_kf[level], e->gxD[level], e->gyD[level], e->gxI[level], e->gyI[level],
                                    e->wiD[level], e->wI[level], nullptr, e->sp, e->partials, LV, level < 2 ? level : 2);
       }
-      const int sys_level = last_of_level ? stage_level[stage] : -1, sys_cov = (last_of_level && stage == n_gn_stages) ? 1 : 0;
-      if (prologue_plan && more_gn) {
+      led.add(1, 0, 32 * nl);   // the normal equations: the 8 maps of unit U1
+      if (prologue_plan && g.more_gn) {
         // the update is deferred into the next iteration's lattice launch (same lanes: LV == f.gn here; next_level is that launch's level)
-        pend.on = true; pend.nblk = nblk; pend.sys_level = sys_level; pend.sys_cov = sys_cov;
-        e->launches += 1;
+        pend.on = true; pend.nblk = nblk; pend.sys_level = g.sys_level; pend.sys_cov = g.sys_cov;
         continue;
       }
-      if (scalar_block_threads(B) == 64)
-        hipLaunchKernelGGL(k_solve_update<64>, dim3(B), dim3(64), 0, s, e->partials, nblk, e->state, f, e->wp, sc, next_level, e->sp, sys_level, sys_cov, pose_in_alt);
-      else
-        hipLaunchKernelGGL(k_solve_update<256>, dim3(B), dim3(256), 0, s, e->partials, nblk, e->state, f, e->wp, sc, next_level, e->sp, sys_level, sys_cov, pose_in_alt);
+      per_lane(k_solve_update<64>, k_solve_update<256>, e->partials, nblk, e->state, f, e->wp, sc, g.next_level, e->sp, g.sys_level, g.sys_cov, pose_in_alt);
       pose_in_alt = 0;
-      e->launches += 2;
     }
-  }
-  // ---- covariance pass (visodo.cpp:1283-1409)
-  if (!first) {
-    int fl = c.finest_level;
-    bool prof = e->prof_on && fl == 0 && e->prof_used + 2 <= (int)e->prof_ev.size();
-    bool fuse_cov = c.fused_gn && !c.chi_square_stats;  // the chi-square statistics need W1 / I1 in memory
-    sb[0] += (fuse_cov ? 32 : 52) * npx(e->iD_kf[fl]);
-    int nblk;
-    if (fuse_cov) {
-      if (prof) { set_system_kernel_events(e->prof_ev[e->prof_used], e->prof_ev[e->prof_used + 1]); e->prof_used += 2; }
+    // ---- covariance pass (visodo.cpp:1283-1409)
+    const int fl = c.finest_level;
+    if (c.fused_gn && !c.chi_square_stats) {   // the chi-square statistics need W1 / I1 in memory
+      system_events(fl);
       nblk = launch_gn_fused(s, B, e->iD_kf[fl], e->I_kf[fl], e->gxD_c[fl], e->gyD_c[fl], e->gxI_c[fl], e->gyI_c[fl],
-                             e->iD_curr[fl], e->I_curr[fl], e->wp, c.interp_mode, e->sp, e->partials, M(f.gn), fl < 2 ? fl : 2, fast_at(fl),
+                             e->iD_curr[fl], e->I_curr[fl], e->wp, c.interp_mode, e->sp, e->partials, GN, fl < 2 ? fl : 2, fast_at(fl),
                              c.weighting == RGBID_MIN_WEIGHT ? 0 : 2);   // k_set_sys: the covariance pass is fixed-nu STUDENT
       if (nblk < 0) return RGBID_E_INVALID;
-      e->launches += 1;
     } else {
-      if (!(fast_at(fl) && launch_warp_pair_fast(s, B, e->iD_curr[fl], e->I_curr[fl], e->iD_kf[fl], e->wiD[fl], e->wI[fl], nullptr, e->wp, c.interp_mode, M(f.gn))))
-        launch_warp_pair(s, B, e->iD_curr[fl], e->I_curr[fl], e->iD_kf[fl], e->wiD[fl], e->wI[fl], e->wp, c.interp_mode, M(f.gn));
-      if (prof) { set_system_kernel_events(e->prof_ev[e->prof_used], e->prof_ev[e->prof_used + 1]); e->prof_used += 2; }
+      warp_pair(fl, GN);
+      system_events(fl);
       nblk = launch_build_system(s, B, e->iD_kf[fl], e->I_kf[fl], e->gxD_c[fl], e->gyD_c[fl], e->gxI_c[fl], e->gyI_c[fl],
-                                 e->wiD[fl], e->wI[fl], nullptr, e->sp, e->partials, M(f.gn), fl < 2 ? fl : 2);
-      e->launches += 2;
+                                 e->wiD[fl], e->wI[fl], nullptr, e->sp, e->partials, GN, fl < 2 ? fl : 2);
     }
-    if (c.chi_square_stats) {  // :1411-1415 (results unused by the reference)
-      int n, lr, lc, st;
-      lattice_geometry(e->wI[fl].rows, e->wI[fl].cols, 9999999, &n, &lr, &lc, &st);
-      launch_error_lattice(s, B, e->wI[fl], e->I_kf[fl], e->res_I, (size_t)c.rows * c.cols, lr, lc, st, M(f.gn));
-      launch_error_lattice(s, B, e->wiD[fl], e->iD_kf[fl], e->res_D, (size_t)c.rows * c.cols, lr, lc, st, M(f.gn));
-      launch_chi_square(s, B, e->res_I, e->res_D, (size_t)c.rows * c.cols, n, 5.f, 0.0025f, c.mestimator, e->chi_out, M(f.gn));
-      e->launches += 3;
-    }
-    if (scalar_block_threads(B) == 64)
-      hipLaunchKernelGGL(k_frame_finish<64>, dim3(B), dim3(64), 0, s, e->partials, nblk, e->state, f, e->sp, e->vis_ab, e->vis_ba,
-                         e->ivis_ab, e->ivis_ba, e->rec_cur, sc);
-    else
-      hipLaunchKernelGGL(k_frame_finish<256>, dim3(B), dim3(256), 0, s, e->partials, nblk, e->state, f, e->sp, e->vis_ab, e->vis_ba,
-                         e->ivis_ab, e->ivis_ba, e->rec_cur, sc);
-    e->launches++;
-  }
-  // ---- covisibility with both keyframes (visodo.cpp:2172-2188), 4 ratio evaluations
-  if (!first) {
+    led.add(1, 0, 32 * npx(e->iD_kf[fl]));
+    if (c.chi_square_stats) chi_lattice(fl, GN, 0.0);  // :1411-1415 (results unused by the reference; outside the byte model)
+    per_lane(k_frame_finish<64>, k_frame_finish<256>, e->partials, nblk, e->state, f, e->sp, e->vis_ab, e->vis_ba, e->ivis_ab, e->ivis_ba, e->rec_cur, sc);
+    // ---- covisibility with both keyframes (visodo.cpp:2172-2188), 4 ratio evaluations: both maps read + both gathered, twice
     launch_visibility_pair2(s, B, e->iD_curr[0], e->iD_kf[0], e->vis_ab, e->vis_ba, e->counts + 0 * 2 * B, e->counts + 1 * 2 * B,
                             e->iD_integr_raw, e->ivis_ab, e->ivis_ba, e->counts + 2 * 2 * B, e->counts + 3 * 2 * B, M(f.vis), c.fast_numerics != 0);
+    led.add(1, 0, 2 * 16 * N0);
     hipLaunchKernelGGL(k_decide, dim3(gb), dim3(tb), 0, s, e->state, f, e->counts, e->fuse_wp, sc, B);
-    e->launches += 2;
-    sb[0] += 2 * 16 * N0;                                                         // two covisibility pairs: both maps read + both gathered
+    led.add(1);
   }
   // ---- odometry keyframe switch
-  enqueue_save_odo_kf(e, s);
+  enqueue_save_odo_kf(e, s, led);
+  const bool defer_maps = c.defer_keyframe_maps != 0 && !c.preview;   // the preview shades the maps every frame
   if (!first && e->kf_hdr) {
     // the outgoing keyframe leaves for the back-end (:1631-1652) BEFORE computeOverlapping rewrites the mask and the incoming frame
     // overwrites the maps (:2197-2202): the exported mask is the keyframe's overlap with its predecessor
     const size_t N = (size_t)c.rows * c.cols;
-    if (defer_maps) {   // the exported normals: from the fused map as the previous step left it -- what the per-frame schedule computed at the end of that step
-      if (!launch_kf_maps(s, B, e->iD_integr, e->vmap, e->nmap, K0, M(f.sw_int))) {
-        launch_vmap(s, B, e->iD_integr, e->vmap, K0, M(f.sw_int));
-        launch_gradient(s, B, e->iD_integr, e->gxD_integr, e->gyD_integr, M(f.sw_int));
-        launch_nmap_gradients(s, B, e->iD_integr, e->gxD_integr, e->gyD_integr, e->nmap, K0, M(f.sw_int));
-        e->launches += 2;
-      }
-      e->launches++;
-      sb[2] += 28 * N0;
-    }
+    // the exported normals: from the fused map as the previous step left it -- what the per-frame schedule computed at the end of that step
+    // (booked at the one-pass kernel's 28 B/px on either branch, as this schedule always has been)
+    if (defer_maps) kf_maps(M(f.sw_int), 2, 28 * N0);
     KfSrc ks;
     ks.im[0] = e->overlap_mask; ks.im[1] = e->colors_integr; ks.im[2] = e->iD_integr; ks.im[3] = e->nmap;
     ks.row_bytes[0] = c.cols; ks.row_bytes[1] = 3 * c.cols; ks.row_bytes[2] = 4 * c.cols; ks.row_bytes[3] = 4 * c.cols;
     ks.off[0] = 0; ks.off[1] = N; ks.off[2] = 4 * N; ks.off[3] = 8 * N;
     hipLaunchKernelGGL(k_export_keyframe, dim3(min(c.rows, 8), 4, B), dim3(256), 0, s, ks, e->kf_blocks, e->kf_block_bytes, c.keyframe_capacity,
                        f.kf_slot);
-    e->launches++;
-    sb[2] += 40 * N0;                                                             // 20 B/px of keyframe images read and written
+    led.add(1, 2, 40 * N0);   // 20 B/px of keyframe images read and written
   }
   // ---- integration keyframe: computeOverlapping (:1517-1539) + saveCurrentImagesAsIntegrationKeyframes (:880-893) ...
   if (!first) {
     launch_visibility(s, B, e->iD_curr[0], e->iD_integr_raw, e->overlap_mask, nullptr, e->ivis_ab, e->counts, M(f.overlap));
-    e->launches++;
+    led.add(1);   // (its 9 B/px are booked with the save that follows: a switch runs both)
   }
   hipLaunchKernelGGL(k_save_integr_kf, dim3(std::min(c.rows, 32), B), dim3(256), 0, s, e->iD_curr[0], e->cur_rgb, e->iD_integr, e->iD_integr_raw, e->colors_integr, e->w_integr,
                      e->overlap_mask, f.sw_int, f.first);   // three copies + weight fill; initialiseDeviceMemory2D(overlap_mask, 0) :2021
-  e->launches += 1;
-  sb[2] += (9 + 12 + 6 + 4) * N0;                                                 // overlap mask pass; inverse depth read once and written twice, colours, weight fill
+  led.add(1, 2, (9 + 12 + 6 + 4) * N0);   // overlap mask pass; inverse depth read once and written twice, colours, weight fill
   // ... or integrateImagesIntoKeyframes (:1674-1764)
-  if (!first) {
-    if (launch_fuse_frame(s, B, e->iD_curr[0], e->iD_integr, e->w_integr, e->warped_w, e->fuse_wp, M(f.fuse), c.fast_numerics != 0)) {
-      e->launches -= 1;
-      sb[3] += (c.fast_numerics ? 20 : 24) * N0;                                  // keyframe map + weight read and written, gather (+ the warped-weight buffer in the exact class)
-    } else {
-      sb[3] += 40 * N0;
-      launch_warp_invdepth_weighted(s, B, e->iD_curr[0], e->iD_integr, e->warped_iD_integr, e->warped_w, nullptr, e->fuse_wp, M(f.fuse));
-      launch_integrate_warped(s, B, e->warped_iD_integr, e->warped_w, e->iD_integr, e->w_integr, M(f.fuse));
-    }
-  }
-  if (defer_maps) {
-    e->launches += 2;                                                             // (the two launches counted with the maps: fusion, integration keyframe)
-  } else if (launch_kf_maps(s, B, e->iD_integr, e->vmap, e->nmap, K0, M(f.maps))) {
-    e->launches += 3;
-    sb[0] += 28 * N0;
+  if (first) {
+    led.add(2);   // NOMINAL: the first-frame list has always counted the fusion's two launches although it enqueues none; bench.py reports the steady list
+  } else if (launch_fuse_frame(s, B, e->iD_curr[0], e->iD_integr, e->w_integr, e->warped_w, e->fuse_wp, M(f.fuse), c.fast_numerics != 0)) {
+    led.add(1, 3, (c.fast_numerics ? 20 : 24) * N0);   // keyframe map + weight read and written, gather (+ the warped-weight buffer in the exact class)
   } else {
-    sb[0] += (16 + 12 + 24) * N0;
-    launch_vmap(s, B, e->iD_integr, e->vmap, K0, M(f.maps));
-    launch_gradient(s, B, e->iD_integr, e->gxD_integr, e->gyD_integr, M(f.maps));
-    launch_nmap_gradients(s, B, e->iD_integr, e->gxD_integr, e->gyD_integr, e->nmap, K0, M(f.maps));
-    e->launches += 5;
+    launch_warp_invdepth_weighted(s, B, e->iD_curr[0], e->iD_integr, e->warped_iD_integr, e->warped_w, nullptr, e->fuse_wp, M(f.fuse));
+    launch_integrate_warped(s, B, e->warped_iD_integr, e->warped_w, e->iD_integr, e->w_integr, M(f.fuse));
+    led.add(2, 3, 40 * N0);
   }
+  if (!defer_maps) kf_maps(M(f.maps), 0, (16 + 12 + 24) * N0);
   if (c.preview) {  // getImage :559-580
     hipLaunchKernelGGL(k_set_light, dim3(gb), dim3(tb), 0, s, e->state, e->light, B);
-    e->launches++;
     launch_generate_image(s, B, e->vmap, e->nmap, e->colors_integr, e->preview, nullptr, e->light, ALL);
-    e->launches++;
+    led.add(2);
   }
   hipLaunchKernelGGL(k_step_end, dim3(gb), dim3(tb), 0, s, e->state, e->rec_cur, f.kf_slot, B);
-  e->launches++;
+  led.add(1);
+  e->launches = led.launches;
+  std::copy(led.bytes, led.bytes + 4, e->step_bytes);
   return hip_status(hipGetLastError());
 }
 
@@ -1040,6 +983,7 @@ int rgbid_engine_create(rgbid_engine** out, rgbid_ctx* ctx, const rgbid_engine_c
   e->ctx = ctx; e->cfg = *cfg; e->B = cfg->lanes; e->L = cfg->levels;
   if (cfg->warping == RGBID_WARP_FIRST) e->cfg.fused_gn = 0;   // warp-first pyramids the WARPED maps: they must exist in memory
   if (cfg->termination == RGBID_CHI_SQUARED) e->cfg.fused_gn = 0;   // the chi-square test reads the stored warped maps
+  e->sched = make_gn_schedule(cfg->iters, cfg->levels, cfg->finest_level, cfg->warping == RGBID_WARP_FIRST);
   hipSetDevice(ctx->device);
   const int B = e->B, rows = cfg->rows, cols = cfg->cols;
   e->lane_pad = 0; e->map_skew = 0x1100;   // 4 KiB + 256 B per map (alloc_img; measured: profiles/r06_experiments/placement.md)
@@ -1321,13 +1265,7 @@ int rgbid_engine_keyframe_maps(rgbid_engine* e, int lane, rgbid_img* depthinv, r
   if (!e || lane < 0 || lane >= e->B) return RGBID_E_INVALID;
   if ((vmap || nmap) && e->cfg.defer_keyframe_maps && !e->cfg.preview) {   // deferred schedule: the maps of the fused keyframe as it stands, now
     hipSetDevice(e->ctx->device);
-    const IntrP K0{e->cfg.fx, e->cfg.fy, e->cfg.cx, e->cfg.cy};
-    hipStream_t s = e->ctx->stream;
-    if (!launch_kf_maps(s, e->B, e->iD_integr, e->vmap, e->nmap, K0, ALL)) {
-      launch_vmap(s, e->B, e->iD_integr, e->vmap, K0, ALL);
-      launch_gradient(s, e->B, e->iD_integr, e->gxD_integr, e->gyD_integr, ALL);
-      launch_nmap_gradients(s, e->B, e->iD_integr, e->gxD_integr, e->gyD_integr, e->nmap, K0, ALL);
-    }
+    enqueue_kf_maps(e, e->ctx->stream, ALL);
   }
   if (depthinv) *depthinv = lane_img(e->iD_integr, lane);
   if (weight) *weight = lane_img(e->w_integr, lane);

@@ -1,4 +1,4 @@
-// engine_device.h -- device-side pieces of the batched engine (engine.hip) that the per-lane persistent Gauss-Newton kernel (tools/experiments/persistent_gn_level/kernels_gnlevel.hip: a measured experiment, profiles/r04_experiments/persistent_gn_level.md) shares:
+// engine_device.h -- device-side pieces of the batched engine (engine.hip) that the keyframe aligner (kfalign.hip: reduce_partials, project_inverse_pose) and the per-lane persistent Gauss-Newton kernel (tools/experiments/persistent_gn_level/kernels_gnlevel.hip: a measured experiment, profiles/r04_experiments/persistent_gn_level.md) shares:
 // the per-lane tracker state, the per-step launch predicates, the by-value step configuration, the pose -> warp projection, and the bodies of
 // k_set_sys / k_solve_update as functions of (lane, thread).  Moved here from engine.hip (round 4).
 #pragma once
@@ -56,15 +56,17 @@ struct StepCfg {  // by-value kernel argument with what the scalar kernels need
   const int* active;     // per-lane 0/1: lanes without a new frame this step sit it out (nullptr: every lane is fed)
 };
 
-__device__ inline void set_warp_from_pose(const StepCfg& c, int level, const double* R, const double* t, WarpParams& wp) { RGBID_FP_STRICT
-  // inverse pose, projected with the level's K (visodo.cpp:1066-1067,1108-1114)
+// pose -> the projected inverse transform a warp uses: the inverse pose, projected with the level's K (visodo.cpp:1066-1067,1108-1114; keyframe_align.cpp:208-231).
+// fx .. cy: the level-0 intrinsics (the engine's are per step, the keyframe aligner's per pair)
+__device__ inline void project_inverse_pose(float fx, float fy, float cx, float cy, int level, const double* R, const double* t, WarpParams& wp) { RGBID_FP_STRICT
   double Ri[9], ti[3];
   se3::m3_inv(R, Ri);
   se3::m3_mulv(Ri, t, ti);
   ti[0] = -ti[0]; ti[1] = -ti[1]; ti[2] = -ti[2];
   int div = 1 << level;
-  se3::project_trafo(c.fx / div, c.fy / div, c.cx / div, c.cy / div, Ri, ti, wp.R, wp.t);
+  se3::project_trafo(fx / div, fy / div, cx / div, cy / div, Ri, ti, wp.R, wp.t);
 }
+__device__ inline void set_warp_from_pose(const StepCfg& c, int level, const double* R, const double* t, WarpParams& wp) { project_inverse_pose(c.fx, c.fy, c.cx, c.cy, level, R, t, wp); }
 
 
 // the per-level constants of the lane's SysParams before a level's iterations / the covariance pass (k_set_sys)

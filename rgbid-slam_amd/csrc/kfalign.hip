@@ -13,6 +13,8 @@
 #include "hip_host.h"
 #include "kernels.h"
 #include "../../include/rgbid/se3.h"
+#include "engine_device.h"   // reduce_partials, project_inverse_pose
+#include "step_plan.h"
 
 #include <cstring>
 #include <new>
@@ -38,14 +40,7 @@ __global__ __launch_bounds__(256) void k_kfa_grey(const unsigned char* src, ImgB
 }
 
 // pose of a pair -> the projected inverse transform its next warps use (:208-231), with the pair's intrinsics at `level`
-__device__ void kfa_set_warp(const KfaState& s, int level, WarpParams& wp) {
-  double Ri[9], ti[3];
-  se3::m3_inv(s.R, Ri);
-  se3::m3_mulv(Ri, s.t, ti);
-  ti[0] = -ti[0]; ti[1] = -ti[1]; ti[2] = -ti[2];
-  const int div = 1 << level;
-  se3::project_trafo(s.fx / div, s.fy / div, s.cx / div, s.cy / div, Ri, ti, wp.R, wp.t);
-}
+__device__ void kfa_set_warp(const KfaState& s, int level, WarpParams& wp) { eng::project_inverse_pose(s.fx, s.fy, s.cx, s.cy, level, s.R, s.t, wp); }
 // the start values every iteration gives computeNuStudent (:265) and the constants of its normal equations at `level`
 __device__ void kfa_set_iteration(const KfaState& s, int level, SysParams& p, SigmaIO& io) {
   const int div = 1 << level;
@@ -73,32 +68,14 @@ __global__ void k_kfa_set_nu(const SigmaIO* io, SysParams* sp, int B) {
   if (lane < B) { sp[lane].nu_d = io[lane].nu; sp[lane].nu_i = io[lane].nu; }
 }
 
-// one update of one pair: fixed-order reduction of its partial sums (the order of k_reduce_system, kernels_system.hip), LLT solve, exp-map, pre-multiplied
-// pose update (:312-335), then what the next iteration needs (warp at next_level, start values)
-// NT: 256 threads per pair, or ONE wave per pair once there are more pairs than compute units (the kernel keeps the whole register file per wave: a 256-thread
-// workgroup occupies a compute unit alone while three of its waves idle) -- four slices of the reduction per thread then, the same doubles in the same order
+// one update of one pair: fixed-order reduction of its partial sums (engine_device.h reduce_partials), LLT solve, exp-map, pre-multiplied pose update (:312-335),
+// then what the next iteration needs (warp at next_level, start values).  NT: 256 threads per pair, or ONE wave per pair once there are more pairs than compute units
 template <int NT>
 __global__ __launch_bounds__(NT) RGBID_SCALAR_KERNEL void k_kfa_solve(const double* partials, int nblk, KfaState* st, WarpParams* wp, SysParams* sp, SigmaIO* io, int next_level) {
-  static_assert(NT == 256 || NT == 64, "8 slices of 32 threads, or 2 x 4");
   const int lane = blockIdx.x, tid = threadIdx.x;
   __shared__ double sm[8][32];
   __shared__ double sums[SYS_TERMS];
-  const int k = tid & 31;
-  for (int sl = tid >> 5; sl < 8; sl += NT / 32) {
-    double acc = 0.0;
-    if (k < SYS_TERMS) {
-      const double* p = partials + (size_t)lane * nblk * SYS_TERMS + k;
-      for (int b = sl; b < nblk; b += 8) acc += p[(size_t)b * SYS_TERMS];
-    }
-    sm[sl][k] = acc;
-  }
-  __syncthreads();
-  if (tid < SYS_TERMS) {
-    double r = 0.0;
-    for (int i = 0; i < 8; ++i) r += sm[i][tid];
-    sums[tid] = r;
-  }
-  __syncthreads();
+  eng::reduce_partials<NT>(partials, nblk, lane, tid, sm, sums);
   if (tid != 0) return;
   KfaState& s = st[lane];
   double b[6], x[6];
@@ -222,7 +199,7 @@ int rgbid_kfalign_batched(rgbid_kfalign* a, int pairs, const float* iD_ini_dev, 
   hipStream_t s = a->ctx->stream;
   const int B = pairs, rows = a->rows, cols = a->cols;
   const int tb = 64, gb = div_up(B, tb);
-  a->launches = 0;
+  Ledger led;   // launches only: the aligner keeps no byte model
   for (int l = 0; l < KFA_LEVELS; ++l)   // the normal equations' launch plan of THIS pair count must fit the partials buffer (sized at creation)
     if (system_blocks_per_lane(rows >> l, cols >> l, B) > a->nblk_cap) return RGBID_E_INVALID;
   RGBID_HIP(hipMemcpyAsync(a->R_dev, R, sizeof(double) * 9 * B, hipMemcpyHostToDevice, s));
@@ -233,42 +210,38 @@ int rgbid_kfalign_batched(rgbid_kfalign* a, int pairs, const float* iD_ini_dev, 
   launch_copy_bytes(s, B, dense_view(iD_end_dev, rows, cols, 4), a->iD_end[0], 4, ALL);
   hipLaunchKernelGGL(k_kfa_grey, dim3(div_up(cols, 256), rows, B), dim3(256), 0, s, grey_ini_dev, a->I_ini[0]);
   hipLaunchKernelGGL(k_kfa_grey, dim3(div_up(cols, 256), rows, B), dim3(256), 0, s, grey_end_dev, a->I_end[0]);
-  a->launches += 4;
+  led.add(4);
   for (int l = 1; l < KFA_LEVELS; ++l) {   // :155-162
     launch_pyr_down2(s, B, a->iD_ini[l - 1], a->iD_ini[l], a->iD_end[l - 1], a->iD_end[l], ALL);
     launch_pyr_down2(s, B, a->I_ini[l - 1], a->I_ini[l], a->I_end[l - 1], a->I_end[l], ALL);
-    a->launches += 2;
+    led.add(2);
   }
   for (int l = 0; l < KFA_LEVELS; ++l) {   // :166-174
     launch_gradient2(s, B, a->iD_ini[l], a->gxD[l], a->gyD[l], a->I_ini[l], a->gxI[l], a->gyI[l], ALL);
-    a->launches += 1;
+    led.add(1);
   }
-  // the levels that iterate, coarse to fine
-  int stage_level[KFA_LEVELS], n_stages = 0;
-  for (int l = KFA_LEVELS - 1; l >= 0; --l) if (KFA_ITERS[l] > 0) stage_level[n_stages++] = l;
-  hipLaunchKernelGGL(k_kfa_begin, dim3(gb), dim3(tb), 0, s, a->state, a->R_dev, a->t_dev, a->K_dev, a->wp, a->sp, a->io, n_stages ? stage_level[0] : 0, B);
-  a->launches += 1;
-  for (int st = 0; st < n_stages; ++st) {
-    const int l = stage_level[st];
+  // the levels that iterate, coarse to fine (no covariance stage: after the last iteration nothing is projected)
+  const GnSchedule sched = make_gn_schedule(KFA_ITERS, KFA_LEVELS, 0, false);
+  hipLaunchKernelGGL(k_kfa_begin, dim3(gb), dim3(tb), 0, s, a->state, a->R_dev, a->t_dev, a->K_dev, a->wp, a->sp, a->io, sched.start_warp_level, B);
+  led.add(1);
+  for (const GnIter& g : sched.iters) {
+    const int l = g.level, next_level = g.more_gn ? g.next_level : -1;
     int n, lr, lc, stride;
     lattice_geometry(a->iD_ini[l].rows, a->iD_ini[l].cols, KFA_NSAMPLES, &n, &lr, &lc, &stride);
-    for (int it = 0; it < KFA_ITERS[l]; ++it) {
-      const bool last_of_level = it == KFA_ITERS[l] - 1;
-      const int next_level = !last_of_level ? l : (st + 1 < n_stages ? stage_level[st + 1] : -1);
-      launch_warp_invdepth(s, B, a->iD_end[l], a->iD_ini[l], a->W1[l], nullptr, a->wp, ALL);
-      launch_warp_intensity(s, B, a->I_end[l], a->iD_ini[l], a->I1[l], nullptr, a->wp, a->ctx->interp_mode, ALL);   // sampled on the KEYFRAME inverse depth (:239-242)
-      launch_error_lattice(s, B, a->W1[l], a->iD_ini[l], a->res, a->res_cap, lr, lc, stride, ALL);
-      launch_sigma(s, B, 1, a->res, a->res_cap, n, a->io, RGBID_STUDENT, ALL);                                        // computeNuStudent (:300)
-      hipLaunchKernelGGL(k_kfa_set_nu, dim3(gb), dim3(tb), 0, s, a->io, a->sp, B);
-      const int nblk = launch_build_system(s, B, a->iD_ini[l], a->I_ini[l], a->gxD[l], a->gyD[l], a->gxI[l], a->gyI[l], a->W1[l], a->I1[l], nullptr, a->sp, a->partials, ALL,
-                                           l < 2 ? l : 2);
-      if (B > 256) hipLaunchKernelGGL(k_kfa_solve<64>, dim3(B), dim3(64), 0, s, a->partials, nblk, a->state, a->wp, a->sp, a->io, next_level);
-      else hipLaunchKernelGGL(k_kfa_solve<256>, dim3(B), dim3(256), 0, s, a->partials, nblk, a->state, a->wp, a->sp, a->io, next_level);
-      a->launches += 7;
-    }
+    launch_warp_invdepth(s, B, a->iD_end[l], a->iD_ini[l], a->W1[l], nullptr, a->wp, ALL);
+    launch_warp_intensity(s, B, a->I_end[l], a->iD_ini[l], a->I1[l], nullptr, a->wp, a->ctx->interp_mode, ALL);   // sampled on the KEYFRAME inverse depth (:239-242)
+    launch_error_lattice(s, B, a->W1[l], a->iD_ini[l], a->res, a->res_cap, lr, lc, stride, ALL);
+    launch_sigma(s, B, 1, a->res, a->res_cap, n, a->io, RGBID_STUDENT, ALL);                                        // computeNuStudent (:300)
+    hipLaunchKernelGGL(k_kfa_set_nu, dim3(gb), dim3(tb), 0, s, a->io, a->sp, B);
+    const int nblk = launch_build_system(s, B, a->iD_ini[l], a->I_ini[l], a->gxD[l], a->gyD[l], a->gxI[l], a->gyI[l], a->W1[l], a->I1[l], nullptr, a->sp, a->partials, ALL,
+                                         l < 2 ? l : 2);
+    if (B > 256) hipLaunchKernelGGL(k_kfa_solve<64>, dim3(B), dim3(64), 0, s, a->partials, nblk, a->state, a->wp, a->sp, a->io, next_level);
+    else hipLaunchKernelGGL(k_kfa_solve<256>, dim3(B), dim3(256), 0, s, a->partials, nblk, a->state, a->wp, a->sp, a->io, next_level);
+    led.add(7);
   }
   hipLaunchKernelGGL(k_kfa_finish, dim3(gb), dim3(tb), 0, s, a->state, a->R_dev, a->t_dev, a->cov_dev, B);
-  a->launches += 1;
+  led.add(1);
+  a->launches = led.launches;
   RGBID_HIP(hipGetLastError());
   RGBID_HIP(hipMemcpyAsync(R, a->R_dev, sizeof(double) * 9 * B, hipMemcpyDeviceToHost, s));
   RGBID_HIP(hipMemcpyAsync(t, a->t_dev, sizeof(double) * 3 * B, hipMemcpyDeviceToHost, s));

@@ -510,9 +510,9 @@ def test_engine_records_do_not_depend_on_the_map_placement(ctx):
 
 @pytest.mark.parametrize("lanes,use_graph", [(1, 0), (1, 1), (3, 0), (16, 0)])
 def test_engine_update_prologue_is_bit_identical(ctx, lanes, use_graph):
-    """round 6, few-lane plan: up to 16 lanes the Gauss-Newton update of an iteration runs as the prologue of the next iteration's lattice launch, redundantly in
-    every workgroup (k_lattice_after_update), instead of as a launch of its own: the same doubles in the same order -- records, fused keyframe maps and launch
-    count (17 launches fewer per tracked frame of the shipped schedule) must say so"""
+    """round 6, few-lane plan: with few lanes (by default up to 8; this test sets the limit itself, to 16 or to 0) the Gauss-Newton update of an iteration runs as
+    the prologue of the next iteration's lattice launch, redundantly in every workgroup (k_lattice_after_update), instead of as a launch of its own: the same doubles
+    in the same order -- records, fused keyframe maps and launch count (17 launches fewer per tracked frame of the shipped schedule) must say so"""
     import os
     K = (131.25, 131.25, 79.5, 59.5)
     T = 6
@@ -920,3 +920,19 @@ def test_engine_one_wave_scalar_kernels(ctx):
         for k in range(n_frames):
             assert rot_angle(a["R"][k, l], b["R"][k, l]) < 2e-5 and np.abs(a["t"][k, l] - b["t"][k, l]).max() < 2e-5, (k, l)
     few.close(); many.close()
+
+
+def test_engine_step_ledger_matches_recorded(ctx):
+    """The step's launch count (launches_per_step: what bench.py reports, what the tests above take differences of) and the four buckets of its byte model
+    (step_bytes: the roofline fraction) for every branch of the launch list -- two geometries (every vectorised path / every fallback) x the configurations of
+    tests/golden/make_engine_step_ledger.py, after the first-frame list and after the steady list -- equal what was recorded before the list was rebuilt from one
+    schedule and one ledger.  Exactly: every term of the model is an integer coefficient times an integer pixel or sample count, far below 2^53."""
+    import json
+    from tests.golden import make_engine_step_ledger as M
+    with open(M.LEDGER) as fh:
+        want = json.load(fh)["entries"]
+    got = M.record(ctx)
+    assert sorted(got) == sorted(want)
+    assert len(got) == 2 * 17        # 16 configurations eagerly + the default as a graph, at both geometries
+    bad = {k: (got[k], want[k]) for k in want if got[k] != want[k]}
+    assert not bad, bad
