@@ -322,11 +322,21 @@ def select_candidates(n, counts, min_separation=3, score_threshold=SCORE_THRESHO
     return out, scores
 
 
-def propose(lf, feats, min_separation=3, score_threshold=SCORE_THRESHOLD, per_query=(2, 2), ratio=MATCH_RATIO):
+def propose(lf, feats, min_separation=3, score_threshold=SCORE_THRESHOLD, per_query=(2, 2), ratio=MATCH_RATIO, shortlist=None, shortlist_size=8,
+            details=None):
     """Appearance proposal over the keyframes of `feats` (in order): one matching call over all (q, c) pairs, then select_candidates.
-    It uses no pose.  -> ([(q, c)], {(q, c): normalised score})"""
+    It uses no pose.  shortlist: a rgbid.bow.Vocabulary; the matching call then runs over (q, q - 1) and the shortlist_size candidates the
+    vocabulary ranks best for q instead of over all pairs, and select_candidates sees those counts alone.  details (a dict) receives the
+    shortlist: candidates [n, T], bow_scores [n, T].  -> ([(q, c)], {(q, c): normalised score})"""
     n = len(feats)
-    pairs = all_pairs(n, min_separation)
+    if shortlist is None:
+        pairs = all_pairs(n, min_separation)
+    else:
+        from . import bow as BW
+        cand, sc = shortlist.shortlist(shortlist.transform(feats), min_separation, shortlist_size)
+        if details is not None:
+            details.update(candidates=cand, bow_scores=sc)
+        pairs = BW.shortlist_pairs(cand)
     if not pairs:
         return [], {}
     _, mc = lf.match(feats, pairs, ratio, lists=False)
@@ -367,11 +377,19 @@ def gate(kq, kc, matches, mask, rows, cols, min_inliers=MIN_INLIERS, min_hull=MI
 
 
 def appearance_loops(ctx, keyframes, K, grey=None, max_keypoints=1000, min_separation=3, score_threshold=SCORE_THRESHOLD, per_query=(2, 2),
-                     batch=64, levels=1, scale=SCALE):
+                     batch=64, levels=1, scale=SCALE, proposal="match", vocabulary=None, shortlist_size=8):
     """features of all exported keyframes, `propose`, RANSAC and its gates.  keyframes: [dict(frame, depthinv, colors)] in export order.
     -> (pairs [(q, c)] that passed, guesses [(R, t)] = qTc_ini of each, report [dict(query, candidate, score, matches, inliers, hull_query,
-    hull_candidate, ransac_ok)] over every proposed pair).  levels, scale: the feature pyramid (LoopFeat); the reference runs 8 levels at 1.2."""
+    hull_candidate, ransac_ok)] over every proposed pair).  levels, scale: the feature pyramid (LoopFeat); the reference runs 8 levels at 1.2.
+    proposal: "match" matches every pair; "bow" matches the shortlist_size candidates per keyframe that `vocabulary` ranks best, and the
+    report gains bow_score and bow_rank.  vocabulary: a rgbid.bow.Vocabulary; None: one of the default size trained on these keyframes'
+    features; a path: the .npz of rgbid.bow.load when the file exists, otherwise one trained on these features and saved there."""
+    import os
     from .posegraph import grey_from_colors
+    if proposal not in ("match", "bow"):
+        raise ValueError(f'proposal must be "match" or "bow", got {proposal!r}')
+    if proposal == "match" and vocabulary is not None:
+        raise ValueError('a vocabulary needs proposal="bow"')
     if len(keyframes) < 2:
         return [], [], []
     rows, cols = keyframes[0]["depthinv"].shape
@@ -382,7 +400,27 @@ def appearance_loops(ctx, keyframes, K, grey=None, max_keypoints=1000, min_separ
         parts = [lf.extract(np.stack(grey[s:s + batch]), np.stack([k["depthinv"] for k in keyframes[s:s + batch]]), K)
                  for s in range(0, len(keyframes), batch)]   # records do not depend on the batch
         feats = Features(torch.cat([p.kps for p in parts]), torch.cat([p.counts for p in parts]))
-        pairs, scores = propose(lf, feats, min_separation, score_threshold, per_query)
+        voc, own, details = vocabulary, False, {}
+        if proposal == "bow" and (voc is None or isinstance(voc, (str, os.PathLike))):
+            from . import bow as BW
+            own = True
+            if voc is not None and os.path.exists(voc):
+                voc = BW.load(ctx, voc)
+            else:
+                path, voc = voc, BW.Vocabulary(ctx)
+                try:
+                    voc.train(feats)
+                    if path is not None:
+                        voc.save(path)
+                except Exception:
+                    voc.close()
+                    raise
+        try:
+            pairs, scores = propose(lf, feats, min_separation, score_threshold, per_query, shortlist=voc, shortlist_size=shortlist_size,
+                                    details=details)
+        finally:
+            if own:
+                voc.close()
         if not pairs:
             return [], [], []
         m, mc = lf.match(feats, pairs)
@@ -397,6 +435,9 @@ def appearance_loops(ctx, keyframes, K, grey=None, max_keypoints=1000, min_separ
         ok, inl, hq, hc = gate(kps[q], kps[c], mm, res["mask"][k], rows, cols) if res["best"][k] >= 0 else (False, 0, 0.0, 0.0)
         report.append(dict(query=q, candidate=c, score=scores[(q, c)], matches=int(mch[k]), inliers=inl, hull_query=hq, hull_candidate=hc,
                            ransac_ok=ok))
+        if details:
+            rank = [int(v) for v in details["candidates"][q]].index(c)
+            report[-1].update(bow_score=int(details["bow_scores"][q][rank]) / float(1 << 30), bow_rank=rank)
         if ok:
             good.append((q, c))
             guess.append((res["R"][k].copy(), res["t"][k].copy()))

@@ -48,6 +48,12 @@ def main():
                     help="with --loops appearance: extract the features over a pyramid of N levels (1 .. 8; the reference uses 8), so that a "
                          "revisit at another distance still matches")
     ap.add_argument("--loop-scale", type=float, default=1.2, metavar="S", help="with --loop-levels: the scale between neighbouring levels (1 < S <= 2)")
+    ap.add_argument("--loop-proposal", default=None, choices=["match", "bow"],
+                    help="with --loops appearance: match every keyframe pair (match, the default) or only the candidates a binary vocabulary "
+                         "shortlists per keyframe (bow; DESIGN.md section 14)")
+    ap.add_argument("--loop-vocabulary", default=None, metavar="FILE",
+                    help="with --loop-proposal bow: load the vocabulary from FILE if it exists, otherwise train it on this run and save it there")
+    ap.add_argument("--loop-shortlist", type=int, default=None, metavar="T", help="with --loop-proposal bow: candidates kept per keyframe (default 8)")
     ap.add_argument("--K", type=float, nargs=4, default=[525.0, 525.0, 319.5, 239.5], help="fx fy cx cy (tools/evaluation.cpp:64-67)")
     args = ap.parse_args()
     if args.voxel is not None and not args.cloud:
@@ -91,9 +97,18 @@ def main():
         ap.error("--loops needs --optimise")
     if (args.loop_levels != 1 or args.loop_scale != 1.2) and args.loops != "appearance":
         ap.error("--loop-levels / --loop-scale need --loops appearance")
+    if (args.loop_proposal is not None or args.loop_vocabulary is not None or args.loop_shortlist is not None) and args.loops != "appearance":
+        ap.error("--loop-proposal / --loop-vocabulary / --loop-shortlist need --loops appearance")
+    if (args.loop_vocabulary is not None or args.loop_shortlist is not None) and args.loop_proposal != "bow":
+        ap.error("--loop-vocabulary / --loop-shortlist need --loop-proposal bow")
     opt = dict(optimise=args.optimise, loops=args.loops) if args.optimise else {}
     if args.loops == "appearance" and (args.loop_levels != 1 or args.loop_scale != 1.2):
         opt["loop_options"] = dict(levels=args.loop_levels, scale=args.loop_scale)
+    if args.loop_proposal == "bow":
+        bow_opt = dict(proposal="bow", vocabulary=args.loop_vocabulary)
+        if args.loop_shortlist is not None:
+            bow_opt["shortlist_size"] = args.loop_shortlist
+        opt.setdefault("loop_options", {}).update(bow_opt)
     if args.cloud:
         R, t, ranges, pc = sequence.track_chunked(ctx, depth, rgb, args.chunks, tuple(args.K), comm=comm, use_graph=0,
                                                   cloud="all" if args.cloud_all else "novel", **opt)
@@ -105,7 +120,8 @@ def main():
               f"loops accepted {info['accepted']} of {len(info['loops'])}")
         for a in info.get("appearance", []):
             print(f"  appearance pair {a['query']} <- {a['candidate']}: score {a['score']:.3f}, matches {a['matches']}, inliers {a['inliers']}, "
-                  f"hull {a['hull_query']:.3f} / {a['hull_candidate']:.3f}, ransac {'ok' if a['ransac_ok'] else 'refused'}")
+                  f"hull {a['hull_query']:.3f} / {a['hull_candidate']:.3f}, ransac {'ok' if a['ransac_ok'] else 'refused'}"
+                  + (f", bow score {a['bow_score']:.3f} rank {a['bow_rank']}" if "bow_rank" in a else ""))
     el = time.perf_counter() - t0
     if args.cloud:
         from rgbid import cloud as CL
