@@ -1,0 +1,358 @@
+// voxel_device.h -- what the map filters over rgbid_cloud_point records share (kernels_voxel.hip, kernels_outlier.hip): the box of the
+// finite points, the float32 grid and its cell keys, the stable LSD radix sort of (key, index) pairs and the stable flag compaction.
+// Everything has internal linkage: each including file compiles its own copy of the kernels it launches.
+#pragma once
+#include "../../include/rgbid.h"
+#include "common.h"
+
+#include <cmath>
+#include <cstddef>
+
+namespace rgbid {
+namespace {
+
+constexpr int VT = 256;                      // threads per block
+constexpr int RADIX = 256;                   // 8-bit digits
+constexpr int SORT_IPT = 16;                 // keys per thread of a sort tile
+constexpr int SORT_TILE = VT * SORT_IPT;     // 4 096 keys; a wave ranks 1 024 contiguous keys in 16 rounds of 64
+constexpr int RUN_IPT = 8;
+constexpr int RUN_TILE = VT * RUN_IPT;       // 2 048 items per tile of the run compactions
+constexpr int VOX_MAX_GRID = 2048;           // grid-strided kernels: 256 CUs x 8 blocks
+enum { SLOT_BOX = 0, SLOT_FINITE = 6, SLOT_RUNS = 7, SLOT_VOXELS = 8, SLOTS = 16 };
+
+__device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
+
+__device__ __forceinline__ unsigned lane_prefix(unsigned long long m) {
+  return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+}
+
+// inclusive scan of one value per thread over the block (256 threads); returns the block total through `total`
+__device__ __forceinline__ unsigned block_scan_incl(unsigned v, unsigned* lds, unsigned& total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned u = __shfl_up(v, o, 64);
+    if (lane >= o) v += u;
+  }
+  if (lane == 63) lds[wave] = v;
+  __syncthreads();
+  unsigned before = 0;
+  for (int i = 0; i < wave; ++i) before += lds[i];
+  total = lds[0] + lds[1] + lds[2] + lds[3];
+  __syncthreads();
+  return v + before;
+}
+
+// ---- bounding box of the finite points ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(VT) void k_vox_box(const float4* __restrict__ in, unsigned n, float* __restrict__ part, unsigned* __restrict__ part_cnt) {
+  __shared__ float lds[VT / 64][6];
+  __shared__ unsigned ldc[VT / 64];
+  float v[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+  unsigned cnt = 0;
+  for (unsigned i = blockIdx.x * VT + threadIdx.x; i < n; i += gridDim.x * VT) {
+    const float4 a = in[2 * (size_t)i];     // x y z nx of a 32-byte record
+    if (finite3(a.x, a.y, a.z)) {
+      ++cnt;
+      v[0] = fminf(v[0], a.x); v[1] = fminf(v[1], a.y); v[2] = fminf(v[2], a.z);
+      v[3] = fmaxf(v[3], a.x); v[4] = fmaxf(v[4], a.y); v[5] = fmaxf(v[5], a.z);
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    for (int k = 0; k < 3; ++k) v[k] = fminf(v[k], __shfl_xor(v[k], o, 64));
+    for (int k = 3; k < 6; ++k) v[k] = fmaxf(v[k], __shfl_xor(v[k], o, 64));
+    cnt += __shfl_xor(cnt, o, 64);
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) { for (int k = 0; k < 6; ++k) lds[wave][k] = v[k]; ldc[wave] = cnt; }
+  __syncthreads();
+  if (threadIdx.x < 6) {
+    const int k = threadIdx.x;
+    float r = lds[0][k];
+    for (int w = 1; w < VT / 64; ++w) r = k < 3 ? fminf(r, lds[w][k]) : fmaxf(r, lds[w][k]);
+    part[6 * blockIdx.x + k] = r;
+  }
+  if (threadIdx.x == 6) part_cnt[blockIdx.x] = ldc[0] + ldc[1] + ldc[2] + ldc[3];
+}
+
+// one wave: the block partials -> box[6] floats | finite count in the slot area
+__global__ __launch_bounds__(64) void k_vox_box_final(const float* __restrict__ part, const unsigned* __restrict__ part_cnt, int nb, unsigned* __restrict__ slots) {
+  float v[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+  unsigned cnt = 0;
+  for (int b = threadIdx.x; b < nb; b += 64) {
+    for (int k = 0; k < 3; ++k) v[k] = fminf(v[k], part[6 * b + k]);
+    for (int k = 3; k < 6; ++k) v[k] = fmaxf(v[k], part[6 * b + k]);
+    cnt += part_cnt[b];
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    for (int k = 0; k < 3; ++k) v[k] = fminf(v[k], __shfl_xor(v[k], o, 64));
+    for (int k = 3; k < 6; ++k) v[k] = fmaxf(v[k], __shfl_xor(v[k], o, 64));
+    cnt += __shfl_xor(cnt, o, 64);
+  }
+  if (threadIdx.x == 0) {
+    for (int k = 0; k < 6; ++k) slots[SLOT_BOX + k] = __float_as_uint(v[k]);
+    slots[SLOT_FINITE] = cnt;
+  }
+}
+
+// ---- keys -----------------------------------------------------------------------------------------------------------------------
+struct VoxGrid {
+  float inv[3];                 // 1.f / leaf
+  float minb[3];                // (float) min_b
+  unsigned long long d0, d01;   // div_b_0, div_b_0 div_b_1
+  unsigned long long sentinel;  // largest key of a finite point + 1: the key of the non-finite records
+};
+
+// PCL's cell index: one float multiply, floorf, a float subtraction, the truncation (the host has checked that it lies in [0, 2^31))
+__device__ __forceinline__ unsigned long long cell_key(float x, float y, float z, const VoxGrid& g) {
+  RGBID_FP_STRICT
+  const unsigned i0 = (unsigned)(int)(floorf(x * g.inv[0]) - g.minb[0]);
+  const unsigned i1 = (unsigned)(int)(floorf(y * g.inv[1]) - g.minb[1]);
+  const unsigned i2 = (unsigned)(int)(floorf(z * g.inv[2]) - g.minb[2]);
+  return (unsigned long long)i0 + (unsigned long long)i1 * g.d0 + (unsigned long long)i2 * g.d01;
+}
+
+template <typename K>
+__global__ __launch_bounds__(VT) void k_vox_keys(const float4* __restrict__ in, unsigned n, VoxGrid g, K* __restrict__ keys, unsigned* __restrict__ idx) {
+  for (unsigned i = blockIdx.x * VT + threadIdx.x; i < n; i += gridDim.x * VT) {
+    const float4 a = in[2 * (size_t)i];
+    keys[i] = (K)(finite3(a.x, a.y, a.z) ? cell_key(a.x, a.y, a.z, g) : g.sentinel);
+    idx[i] = i;
+  }
+}
+
+// ---- stable LSD radix sort of (key, index), 8 bits per pass -----------------------------------------------------------------------
+template <typename K>
+__device__ __forceinline__ unsigned digit_of(K k, int shift) { return (unsigned)(k >> shift) & (RADIX - 1); }
+
+// digit counts of one tile -> hist[digit][tile] (digit-major: a scan along a digit's row gives the tiles' offsets)
+template <typename K>
+__global__ __launch_bounds__(VT) void k_vox_hist(const K* __restrict__ keys, unsigned n, int shift, unsigned* __restrict__ hist, unsigned ntiles) {
+  __shared__ unsigned cnt[RADIX];
+  cnt[threadIdx.x] = 0;
+  __syncthreads();
+  const size_t base = (size_t)blockIdx.x * SORT_TILE;
+  unsigned d[SORT_IPT];
+#pragma unroll
+  for (int j = 0; j < SORT_IPT; ++j) {
+    const size_t i = base + j * VT + threadIdx.x;
+    d[j] = i < n ? digit_of(keys[i], shift) : RADIX;
+  }
+#pragma unroll
+  for (int j = 0; j < SORT_IPT; ++j)
+    if (d[j] < RADIX) atomicAdd(&cnt[d[j]], 1u);     // integer counts: exact in any order
+  __syncthreads();
+  hist[(size_t)threadIdx.x * ntiles + blockIdx.x] = cnt[threadIdx.x];
+}
+
+// one block per digit: exclusive scan of its tile counts in place, the digit's total
+__global__ __launch_bounds__(VT) void k_vox_scan_digits(unsigned* __restrict__ hist, unsigned ntiles, unsigned* __restrict__ dtotal) {
+  __shared__ unsigned lds[VT / 64];
+  unsigned* h = hist + (size_t)blockIdx.x * ntiles;
+  unsigned carry = 0;
+  for (unsigned base = 0; base < ntiles; base += VT) {
+    const unsigned i = base + threadIdx.x;
+    const unsigned v = i < ntiles ? h[i] : 0u;
+    unsigned tot;
+    const unsigned incl = block_scan_incl(v, lds, tot);
+    if (i < ntiles) h[i] = carry + incl - v;
+    carry += tot;
+  }
+  if (threadIdx.x == 0) dtotal[blockIdx.x] = carry;
+}
+
+// A tile's keys in input order are (wave, round, lane): wave w owns keys [w 1024, (w + 1) 1024) of the tile.  In each round the lanes
+// of equal digit find each other with 8 ballots; the lowest of them adds the group's size to the wave's counter of that digit (an LDS
+// integer add returning the old value, in program order) and broadcasts the old value.  Position = digit base + tile offset + the
+// counts of lower waves + the rank inside the wave: stable.
+template <typename K>
+__global__ __launch_bounds__(VT) void k_vox_scatter(const K* __restrict__ kin, const unsigned* __restrict__ vin, K* __restrict__ kout,
+                                                    unsigned* __restrict__ vout, unsigned n, int shift, const unsigned* __restrict__ hist,
+                                                    const unsigned* __restrict__ dtotal, unsigned ntiles) {
+  __shared__ unsigned wcnt[VT / 64][RADIX];
+  __shared__ unsigned base[RADIX];
+  __shared__ unsigned lds[VT / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  {
+    const unsigned v = dtotal[threadIdx.x];
+    unsigned tot;
+    const unsigned incl = block_scan_incl(v, lds, tot);
+    base[threadIdx.x] = incl - v + hist[(size_t)threadIdx.x * ntiles + blockIdx.x];
+  }
+  for (int w = 0; w < VT / 64; ++w) wcnt[w][threadIdx.x] = 0;
+  __syncthreads();
+  const size_t t0 = (size_t)blockIdx.x * SORT_TILE + (size_t)wave * (64 * SORT_IPT);
+  K k[SORT_IPT];
+  unsigned v[SORT_IPT], rank[SORT_IPT];
+#pragma unroll
+  for (int j = 0; j < SORT_IPT; ++j) {
+    const size_t i = t0 + j * 64 + lane;
+    k[j] = i < n ? kin[i] : (K)0;
+    v[j] = i < n ? vin[i] : 0u;
+  }
+#pragma unroll
+  for (int j = 0; j < SORT_IPT; ++j) {
+    const bool valid = t0 + j * 64 + lane < n;
+    const unsigned d = digit_of(k[j], shift);
+    unsigned long long m = __ballot(valid);
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+      const unsigned long long bb = __ballot((d >> b) & 1u);
+      m &= ((d >> b) & 1u) ? bb : ~bb;
+    }
+    const unsigned pre = lane_prefix(m);
+    const int leader = m ? __builtin_ctzll(m) : 0;
+    unsigned old = 0;
+    if (valid && pre == 0) old = atomicAdd(&wcnt[wave][d], (unsigned)__popcll(m));
+    old = __shfl(old, leader, 64);
+    rank[j] = old + pre;
+  }
+  __syncthreads();
+  {
+    const unsigned c0 = wcnt[0][threadIdx.x], c1 = wcnt[1][threadIdx.x], c2 = wcnt[2][threadIdx.x];
+    const unsigned b0 = base[threadIdx.x];
+    wcnt[0][threadIdx.x] = b0;
+    wcnt[1][threadIdx.x] = b0 + c0;
+    wcnt[2][threadIdx.x] = b0 + c0 + c1;
+    wcnt[3][threadIdx.x] = b0 + c0 + c1 + c2;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < SORT_IPT; ++j) {
+    if (t0 + j * 64 + lane >= n) continue;
+    const unsigned pos = wcnt[wave][digit_of(k[j], shift)] + rank[j];
+    kout[pos] = k[j];
+    vout[pos] = v[j];
+  }
+}
+
+// ---- stable compactions: run heads, then the runs of >= min_points members ------------------------------------------------------
+// A source says how many items it has (size), which of them are kept (flag) and what a kept item writes at its rank (write).
+template <typename K>
+struct HeadSrc {                       // item i < finite: key[i] != key[i - 1] -> starts[rank] = i
+  const K* keys;
+  unsigned finite;
+  unsigned* starts;
+  __device__ __forceinline__ unsigned size() const { return finite; }
+  __device__ __forceinline__ bool flag(unsigned i) const { return i == 0 || keys[i] != keys[i - 1]; }
+  __device__ __forceinline__ void write(unsigned pos, unsigned i) const { starts[pos] = i; }
+};
+
+struct KeepSrc {                       // run r < runs: starts[r + 1] - starts[r] >= min_points -> (begin, end) of voxel `rank`
+  const unsigned* starts;
+  const unsigned* runs;                // device slot
+  unsigned min_points;
+  unsigned* vbeg;
+  unsigned* vend;
+  __device__ __forceinline__ unsigned size() const { return *runs; }
+  __device__ __forceinline__ bool flag(unsigned r) const { return starts[r + 1] - starts[r] >= min_points; }
+  __device__ __forceinline__ void write(unsigned pos, unsigned r) const { vbeg[pos] = starts[r]; vend[pos] = starts[r + 1]; }
+};
+
+template <class S>
+__global__ __launch_bounds__(VT) void k_vox_flag_count(S s, unsigned* __restrict__ bc) {
+  __shared__ unsigned lds[VT / 64];
+  const unsigned n = s.size();
+  const size_t t0 = (size_t)blockIdx.x * RUN_TILE;
+  unsigned c = 0;
+  for (int j = 0; j < RUN_IPT; ++j) {
+    const size_t i = t0 + j * VT + threadIdx.x;
+    if (i < n && s.flag((unsigned)i)) ++c;
+  }
+  unsigned tot;
+  block_scan_incl(c, lds, tot);
+  if (threadIdx.x == 0) bc[blockIdx.x] = tot;
+}
+
+// one block: exclusive scan of nb tile counts in place -> slots[slot] = total; tail (optional): tail[total] = tail_val
+__global__ __launch_bounds__(VT) void k_vox_scan1(unsigned* __restrict__ bc, unsigned nb, unsigned* __restrict__ slots, int slot,
+                                                  unsigned* __restrict__ tail, unsigned tail_val) {
+  __shared__ unsigned lds[VT / 64];
+  unsigned carry = 0;
+  for (unsigned base = 0; base < nb; base += VT) {
+    const unsigned i = base + threadIdx.x;
+    const unsigned v = i < nb ? bc[i] : 0u;
+    unsigned tot;
+    const unsigned incl = block_scan_incl(v, lds, tot);
+    if (i < nb) bc[i] = carry + incl - v;
+    carry += tot;
+  }
+  if (threadIdx.x == 0) {
+    slots[slot] = carry;
+    if (tail) tail[carry] = tail_val;
+  }
+}
+
+// items of a tile in (round, wave, lane) order: rank = tile offset + earlier rounds + lower waves + mbcnt
+template <class S>
+__global__ __launch_bounds__(VT) void k_vox_flag_write(S s, const unsigned* __restrict__ bc) {
+  __shared__ unsigned wsum[VT / 64];
+  const unsigned n = s.size();
+  const size_t t0 = (size_t)blockIdx.x * RUN_TILE;
+  if (t0 >= n) return;                 // uniform over the block
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned carry = bc[blockIdx.x];
+  for (int j = 0; j < RUN_IPT; ++j) {
+    const size_t i = t0 + j * VT + threadIdx.x;
+    const bool f = i < n && s.flag((unsigned)i);
+    const unsigned long long m = __ballot(f);
+    if (lane == 0) wsum[wave] = (unsigned)__popcll(m);
+    __syncthreads();
+    unsigned before = 0;
+    for (int w = 0; w < wave; ++w) before += wsum[w];
+    const unsigned tot = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    __syncthreads();
+    if (f) s.write(carry + before + lane_prefix(m), (unsigned)i);
+    carry += tot;
+  }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------------------
+unsigned grid_of(unsigned long long items) { return items < VOX_MAX_GRID ? (unsigned)(items ? items : 1) : VOX_MAX_GRID; }
+
+int bitlen(unsigned long long x) { return x ? 64 - __builtin_clzll(x) : 0; }
+
+// the grid of DESIGN.md section 12 from the box, in float32 as PCL forms it; RGBID_E_INVALID when a bound leaves the int32 range, a
+// cell index could not be held by an int, or the grid has 2^62 cells or more
+int form_grid(const float lo[3], const float hi[3], const float leaf[3], VoxGrid& g, long long grid[6]) {
+  RGBID_FP_STRICT
+  unsigned long long div[3], ijk_max[3];
+  for (int a = 0; a < 3; ++a) {
+    const float inv = 1.0f / leaf[a];
+    const float flo = floorf(lo[a] * inv), fhi = floorf(hi[a] * inv);
+    if (!(flo >= -2147483648.f && flo < 2147483648.f && fhi >= -2147483648.f && fhi < 2147483648.f)) return RGBID_E_INVALID;
+    const int min_b = (int)flo, max_b = (int)fhi;
+    const float span = fhi - (float)min_b;   // the largest cell index a point can get (the float operations are monotone)
+    if (!(span < 2147483648.f)) return RGBID_E_INVALID;
+    g.inv[a] = inv;
+    g.minb[a] = (float)min_b;
+    div[a] = (unsigned long long)((long long)max_b - min_b + 1);
+    ijk_max[a] = (unsigned long long)(int)span;
+    grid[a] = min_b;
+    grid[3 + a] = (long long)div[a];
+  }
+  const unsigned __int128 cells = (unsigned __int128)div[0] * div[1] * div[2];
+  if (cells >= ((unsigned __int128)1 << 62)) return RGBID_E_INVALID;
+  g.d0 = div[0];
+  g.d01 = div[0] * div[1];
+  const unsigned __int128 kmax = (unsigned __int128)ijk_max[0] + (unsigned __int128)ijk_max[1] * g.d0 + (unsigned __int128)ijk_max[2] * g.d01;
+  if (kmax >= ((unsigned __int128)1 << 63)) return RGBID_E_INVALID;
+  g.sentinel = (unsigned long long)kmax + 1;
+  return RGBID_OK;
+}
+
+// the sort of n (key, index) pairs by the low `bits` key bits, ping-ponging between the two buffers: three launches per 8-bit pass.
+// Returns the buffer that holds the sorted pairs.
+template <typename K>
+int radix_sort_pairs(hipStream_t s, K* const keys[2], unsigned* const idx[2], unsigned n, int bits, unsigned* hist, unsigned* dtotal) {
+  const unsigned ntiles = (n + SORT_TILE - 1) / SORT_TILE;
+  const int passes = (bits + 7) / 8;
+  int p = 0;
+  for (int pass = 0; pass < passes; ++pass, p ^= 1) {
+    hipLaunchKernelGGL(k_vox_hist<K>, dim3(ntiles), dim3(VT), 0, s, keys[p], n, 8 * pass, hist, ntiles);
+    hipLaunchKernelGGL(k_vox_scan_digits, dim3(RADIX), dim3(VT), 0, s, hist, ntiles, dtotal);
+    hipLaunchKernelGGL(k_vox_scatter<K>, dim3(ntiles), dim3(VT), 0, s, keys[p], idx[p], keys[p ^ 1], idx[p ^ 1], n, 8 * pass, hist, dtotal, ntiles);
+  }
+  return p;
+}
+
+}  // namespace
+}  // namespace rgbid

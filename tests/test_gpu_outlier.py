@@ -1,0 +1,424 @@
+"""GPU tests of the radius outlier filter (include/rgbid_outlier.h, csrc/kernels_outlier.hip, rgbid.outlier): counts, mask, kept and the
+emitted bytes against the numpy restatement (tests/outlier_mirror.py: brute force up to 20 000 records, the float64 grid mirror above) on
+clouds of every shape the grid walk must handle, boundary adversaries up to the documented grid bound, the engine's own exports, a
+chunked run with injected outliers; the refusals; the --cloud-radius option of tools/track_dataset.py."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from rgbid import cloud as CL
+from rgbid import outlier as OL
+from rgbid import sequence, synth, tum
+from rgbid import voxel as VX
+from tests.outlier_mirror import radius_counts_bruteforce, radius_counts_grid, radius_filter_numpy
+from tests.test_cpu_cloud import cloud_numpy, make_block, records_equal
+from tests.test_cpu_outlier import xyz_cloud
+from tests.test_cpu_voxel import random_cloud
+from tests.test_gpu_cloud import K_SMALL, make_lanes, write_tum_folder
+from tests.voxel_mirror import voxel_numpy
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F = np.float32
+R = 0.02
+
+
+def upload(p):
+    return torch.from_numpy(np.ascontiguousarray(p).view(np.uint8).reshape(-1, 32).copy()).cuda()
+
+
+def finite(p):
+    return np.isfinite(p["x"]) & np.isfinite(p["y"]) & np.isfinite(p["z"])
+
+
+def check(ctx, p, r=R, min_neighbours=4, cap=None, dev=None, rf=None, full=None):
+    """device filter of records p (structured) against the mirror: counts, mask, kept, the emitted bytes -> (counts, mask, plan).
+    full: the mirror's counts of (p, r) at a cap no smaller than this one, computed once for several calls"""
+    dev = upload(p) if dev is None else dev
+    own = rf is None
+    rf = OL.RadiusFilter(ctx, max(len(p), 1)) if own else rf
+    out, cnt, plan = rf.filter(dev, r, min_neighbours, cap, return_counts=True, return_plan=True)
+    if own:
+        rf.close()
+    ecnt, emask, ekept = radius_filter_numpy(p, r, min_neighbours, cap,
+                                             None if full is None else np.minimum(full, OL.neighbour_args(min_neighbours, cap)[1]))
+    got = cnt.cpu().numpy().view(np.uint32).astype(np.int64)
+    bad = np.nonzero(got != ecnt)[0]
+    assert bad.size == 0, (bad.size, bad[:5], got[bad[:5]], ecnt[bad[:5]], p[bad[:5]])
+    mask = finite(p) & (got >= min_neighbours)
+    assert np.array_equal(mask, emask)
+    assert (plan.kept, plan.n, plan.finite) == (int(emask.sum()), len(p), int(finite(p).sum())) and out.shape[0] == plan.kept
+    ok, first = records_equal(CL.as_numpy(out), ekept)
+    assert ok, first
+    return got, mask, plan
+
+
+@pytest.mark.parametrize("n", [0, 1, 2, 63, 64, 65, 4095, 4096, 4097, 3 * 4096 + 1000])
+def test_outlier_sizes(ctx, n):
+    """sizes around the wave, the block and the sort's 4 096-key tile, with NaN / inf positions and NaN normals; brute force judges"""
+    rng = np.random.default_rng(n)
+    p = random_cloud(rng, n, spread=0.03 if n <= 65 else 0.08)
+    full = radius_counts_bruteforce(p, R, 1 << 31)
+    for minn, cap in ((0, None), (2, None), (1, 1 << 31)):
+        got, mask, plan = check(ctx, p, R, minn, cap, full=full)
+    if n >= 4095:                                         # of the last one: some records have no neighbour, some have many
+        assert 0 < mask.sum() < finite(p).sum() and got.max() > 4
+
+
+def test_outlier_a_million_against_the_grid_mirror(ctx):
+    rng = np.random.default_rng(20)
+    p = random_cloud(rng, (1 << 20) + 3, spread=0.2)
+    got, mask, plan = check(ctx, p, 0.003, 1, 4)
+    assert plan.cells > 100_000 and 0.05 < mask.mean() < 0.95 and got.max() == 4
+
+
+# ---- boundary adversaries ---------------------------------------------------------------------------------------------------------
+def grid_line(k, inv):
+    """the smallest float32 p with floorf(p * inv) >= k: the first coordinate of the kernel grid's cell k"""
+    p = F(k) / inv
+    while np.floor(p * inv) >= k:
+        p = np.nextafter(p, F(-np.inf))
+    while np.floor(p * inv) < k:
+        p = np.nextafter(p, F(np.inf))
+    return p
+
+
+def adversaries(r, origin_cell):
+    """pairs at distance r, nextafter(r, 0), nextafter(r, inf) along each axis (both ways) and along the diagonal (where the coordinates'
+    own spacing is coarser than that, the nearest representable distance on the same side of r); one member's coordinate sits on a
+    cell boundary of the kernel's grid, one ulp below it and one above.  Pairs are 8 cells apart along x, so a pair is alone.
+    origin_cell: the cell index (every axis) the pairs start from; they extend towards 0 along x."""
+    r = F(r)
+    cell = OL.cell_size(r)
+    inv = F(1) / cell
+    step = -8 if origin_cell > 0 else 8
+    pts = []
+    t = 0
+    for d in (r, np.nextafter(r, F(0)), np.nextafter(r, F(np.inf))):
+        for axis in (0, 1, 2, 3):                        # 3: the diagonal
+            for sign in (1, -1):
+                for ulp in (0, -1, 1):
+                    k = [origin_cell + step * t, origin_cell, origin_cell]
+                    a = np.array([grid_line(k[0], inv) + cell / F(2), grid_line(k[1], inv) + cell / F(2), grid_line(k[2], inv) + cell / F(2)], F)
+                    for ax in ((axis,) if axis < 3 else (0, 1, 2)):
+                        a[ax] = grid_line(k[ax], inv)
+                        if ulp:
+                            a[ax] = np.nextafter(a[ax], F(ulp * np.inf))
+                    e = np.zeros(3, F)
+                    if axis < 3:
+                        e[axis] = d
+                    else:
+                        e[:] = d / np.sqrt(F(3))
+                    b = (a + F(sign) * e).astype(F)
+                    if axis < 3:                         # far from 0 the sum rounds: r and r - ulp stay within d, r + ulp stays beyond r
+                        while d <= r and abs(b[axis] - a[axis]) > d:
+                            b[axis] = np.nextafter(b[axis], a[axis])
+                        while d > r and abs(b[axis] - a[axis]) <= r:
+                            b[axis] = np.nextafter(b[axis], F(sign * np.inf))
+                    pts += [a, b]
+                    t += 1
+    q = np.array(pts, F)
+    return xyz_cloud(q[:, 0], q[:, 1], q[:, 2]), inv
+
+
+def cells_of(p, inv):
+    return np.stack([np.floor(p[c] * inv) for c in "xyz"], 1)
+
+
+@pytest.mark.parametrize("where", ["origin", "10m", "bound", "-bound"])
+def test_outlier_boundary_adversaries(ctx, where):
+    cell = OL.cell_size(R)
+    origin = {"origin": 0, "10m": int(10.0 / float(cell)), "bound": OL.MAX_CELL - 2, "-bound": -(OL.MAX_CELL - 2)}[where]
+    p, inv = adversaries(R, origin)
+    c = cells_of(p, inv)
+    assert np.abs(c).max() <= OL.MAX_CELL and (np.abs(c).max() >= OL.MAX_CELL - 3 or "bound" not in where)
+    got, mask, plan = check(ctx, p, R, 1, 3)
+    assert 0 < got.sum() < len(p) and got.max() == 1      # some pairs are neighbours, some are not; nobody has two
+
+
+def test_outlier_line_at_r_and_one_ulp_either_side(ctx):
+    """the hand-computed line of tests/test_cpu_outlier.py along each axis: r = 1 exactly, r less one ulp, r plus one ulp"""
+    x = [-(1 + 2.0 ** -23), -1.0, 0.0, 1 - 2.0 ** -24, 2 - 2.0 ** -23]
+    o = [0.0] * 5
+    for q in (xyz_cloud(x, o, o), xyz_cloud(o, x, o), xyz_cloud(o, o, x)):
+        got, mask, plan = check(ctx, q, 1.0, 2, 10)
+        assert got.tolist() == [1, 2, 2, 2, 1]
+        got, mask, plan = check(ctx, q, float(np.nextafter(F(1), F(0))), 2, 10)
+        assert got.tolist() == [1, 1, 1, 2, 1]
+
+
+def test_outlier_beyond_the_bound_is_refused(ctx):
+    """a finite point whose cell index is MAX_CELL + 1 on one axis, positive or negative: RGBID_E_INVALID; the next good plan succeeds"""
+    cell = OL.cell_size(R)
+    inv = F(1) / cell
+    p, _ = adversaries(R, OL.MAX_CELL - 2)
+    rf = OL.RadiusFilter(ctx, len(p))
+    for axis in "xyz":
+        for sign in (1, -1):
+            q = p.copy()
+            q[axis][5] = F(sign) * (grid_line(OL.MAX_CELL + 1, inv) + cell / F(2))
+            assert abs(np.floor(q[axis][5] * inv)) in (OL.MAX_CELL + 1, OL.MAX_CELL + 2)
+            with pytest.raises(Exception, match="rgbid error -1"):
+                rf.plan(upload(q), R, 1)
+            check(ctx, p, R, 1, 3, rf=rf)
+    with pytest.raises(Exception, match="rgbid error -1"):                # the same cloud fits at a larger radius only
+        rf.plan(upload(p), R / 2, 1)
+    check(ctx, p, R * 2, 1, 3, rf=rf)
+    rf.close()
+
+
+# ---- shapes of the cell table -----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("cap", [1, 4, 1 << 31])
+def test_outlier_all_points_in_one_cell(ctx, cap):
+    """10^4 copies of one point with a jitter below r / 100: every count is min(n - 1, cap)"""
+    rng = np.random.default_rng(31)
+    n = 10_000
+    p = random_cloud(rng, n, nan=0.0)
+    for a, c in enumerate("xyz"):
+        p[c] = (F(0.3) + F(0.011) * a + rng.uniform(-R / 200, R / 200, n)).astype(F)
+    got, mask, plan = check(ctx, p, R, min(cap, 4), cap)
+    assert plan.cells <= 8 and (got == min(n - 1, cap)).all() and mask.all()
+
+
+def test_outlier_every_point_its_own_cell(ctx):
+    """cell centres of every second cell of the grid, shuffled: nobody has a neighbour"""
+    rng = np.random.default_rng(32)
+    cell = float(OL.cell_size(R))
+    g = np.stack(np.meshgrid(np.arange(31), np.arange(23), np.arange(17), indexing="ij"), -1).reshape(-1, 3)
+    g = g[rng.permutation(len(g))]
+    p = random_cloud(rng, len(g), nan=0.0)
+    for a, c in enumerate("xyz"):
+        p[c] = ((2 * g[:, a] + 0.5) * cell - 0.3).astype(F)
+    got, mask, plan = check(ctx, p, R, 1)
+    assert plan.cells == len(p) and not got.any() and not mask.any()
+    got, mask, plan = check(ctx, p, R, 0)
+    assert mask.all()
+
+
+@pytest.mark.parametrize("thin", ["z", "y", "x", "yz", "xz", "xy"])
+def test_outlier_sheets_and_lines(ctx, thin):
+    """a sheet one cell thick and a line one cell wide along each axis: d = 1 on the thin axes, so every row of the walk is clipped at a
+    face of the grid, and at i = 0 / i = d0 - 1 the keys i - 1 / i + 1 belong to another row"""
+    rng = np.random.default_rng(sum(map(ord, thin)))
+    cell = float(OL.cell_size(R))
+    n = 6000 if len(thin) == 1 else 1500
+    p = random_cloud(rng, n, nan=0.01)
+    for c in "xyz":
+        u = rng.uniform(5.1, 5.9, n) if c in thin else rng.uniform(-20.0, 20.0, n)       # cells: one on a thin axis, 40 on the others
+        p[c] = np.where(np.isfinite(p[c]), (u * cell).astype(F), p[c])
+    got, mask, plan = check(ctx, p, R, 2, 1 << 31)
+    assert got.max() >= 2 and plan.cells <= (40 + 1) ** (3 - len(thin))
+
+
+def test_outlier_64bit_keys(ctx):
+    """two clusters 6 000 cells apart on every axis: 2.2e11 cells, the 64-bit key path"""
+    rng = np.random.default_rng(33)
+    n = 8_000
+    cell = float(OL.cell_size(R))
+    p = random_cloud(rng, n, spread=0.05, nan=0.01)
+    far = rng.random(n) < 0.5
+    for c in "xyz":
+        p[c] = np.where(far, p[c] + F(3000 * cell), p[c] - F(3000 * cell)).astype(F)
+    inv = F(1) / OL.cell_size(R)
+    c = cells_of(p[finite(p)], inv)
+    assert np.prod(c.max(0) - c.min(0) + 1) > 1 << 32
+    got, mask, plan = check(ctx, p, R, 3, 8)
+    assert 0 < mask.sum() < n
+
+
+def test_outlier_non_finite_inputs(ctx):
+    rng = np.random.default_rng(34)
+    p = random_cloud(rng, 9_000, nan=0.3)
+    p["y"][rng.random(len(p)) < 0.1] = -np.inf
+    p["z"][rng.random(len(p)) < 0.05] = np.nan
+    for f in ("nx", "ny", "nz"):
+        p[f][rng.random(len(p)) < 0.2] = (np.nan, np.inf, -np.inf)[rng.integers(3)]      # normals only: these records take part
+    full = radius_counts_bruteforce(p, R, 2)
+    got, mask, plan = check(ctx, p, R, 2, full=full)
+    nrm_bad = finite(p) & ~(np.isfinite(p["nx"]) & np.isfinite(p["ny"]) & np.isfinite(p["nz"]))
+    assert (mask & nrm_bad).any() and not got[~finite(p)].any()
+    got, mask, plan = check(ctx, p, R, 0, full=full)
+    assert np.array_equal(mask, finite(p))
+    q = p.copy()
+    q["x"] = np.nan
+    got, mask, plan = check(ctx, q, R, 0)
+    assert plan.finite == 0 and plan.kept == 0 and not got.any()
+
+
+def test_outlier_offset_inputs_and_reuse(ctx):
+    """records starting 1 and 3 records into a buffer, odd counts; one filter reused across plans of different sizes"""
+    rng = np.random.default_rng(35)
+    p = random_cloud(rng, 9_011, spread=0.06)
+    dev = upload(p)
+    rf = OL.RadiusFilter(ctx, len(p))
+    for off, end, r, minn, cap in ((1, len(p), R, 3, None), (3, 6_000, 0.01, 1, 5), (0, 5, R, 1, None), (0, len(p), 0.03, 8, 1 << 31)):
+        check(ctx, p[off:end], r, minn, cap, dev=dev[off:end], rf=rf)
+    rf.close()
+
+
+def test_outlier_deterministic(ctx):
+    rng = np.random.default_rng(36)
+    p = random_cloud(rng, 1 << 18, spread=0.15)
+    dev = upload(p)
+    a, ca = OL.radius_filter(ctx, dev, 0.005, 2, return_counts=True)
+    b, cb = OL.radius_filter(ctx, dev, 0.005, 2, return_counts=True)
+    assert torch.equal(a, b) and torch.equal(ca, cb) and 0 < len(a) < len(p)
+
+
+def test_outlier_refusals(ctx):
+    rng = np.random.default_rng(37)
+    p = random_cloud(rng, 100, nan=0.0)
+    dev = upload(p)
+    rf = OL.RadiusFilter(ctx, 100)
+    L = rf.L
+    kept = C.c_ulonglong()
+    ptr = C.c_void_p(dev.data_ptr())
+
+    def still_works():
+        got, mask, plan = check(ctx, p, 0.05, 1, dev=dev, rf=rf)
+        assert plan.kept > 1
+        return plan
+
+    for radius in (0.0, -0.02, float("nan"), float("inf")):
+        with pytest.raises(ValueError):
+            rf.plan(dev, radius, 1)
+        assert L.rgbid_outlier_plan(rf._h, ptr, 100, C.c_float(radius), 1, 1, None, C.byref(kept)) == -1    # the C-ABI itself, past the Python check
+        still_works()
+    for radius, cap, minn, n, at in ((R, 0, 0, 100, ptr), (R, 3, 4, 100, ptr), (R, 4, 4, 101, ptr), (R, 4, 4, 50, C.c_void_p(dev.data_ptr() + 8)),
+                                     (R, 4, 4, 5, None), (1e-30, 4, 4, 100, ptr), (1e30, 4, 4, 100, ptr)):
+        assert L.rgbid_outlier_plan(rf._h, at, n, C.c_float(radius), cap, minn, None, C.byref(kept)) == -1, (radius, cap, minn, n)
+        still_works()
+    with pytest.raises(ValueError):
+        rf.plan(dev, R, 4, 3)
+    with pytest.raises(ValueError):
+        rf.plan(dev, R, 1, 0)
+    plan = still_works()
+    canary = torch.full((plan.kept + 1, 32), 0xA5, dtype=torch.uint8, device="cuda")
+    with pytest.raises(Exception, match="rgbid error -1"):
+        rf.emit(canary[:plan.kept - 1])                                                  # capacity below the plan's kept
+    ctx.sync()
+    assert (canary == 0xA5).all()
+    rf.emit(canary[:plan.kept])                                                          # exactly kept: the record after them stays untouched
+    ctx.sync()
+    assert (canary[plan.kept] == 0xA5).all() and records_equal(CL.as_numpy(canary[:plan.kept]), radius_filter_numpy(p, 0.05, 1)[2])[0]
+    still_works()
+    rf.close()
+    with pytest.raises(Exception):
+        OL.RadiusFilter(ctx, 0)
+    with pytest.raises(Exception):
+        OL.RadiusFilter(ctx, (1 << 31) + 1)
+
+
+# ---- the map chain ----------------------------------------------------------------------------------------------------------------
+def test_outlier_from_engine_exports(ctx):
+    """engine exports -> Cloud.build -> RadiusFilter.filter -> voxel_grid, against the mirrors applied to the restated cloud"""
+    rows, cols, n, B = 120, 160, 9, 2
+    from rgbid import engine as E
+    seqs, depth, rgb = make_lanes(B, n, rows, cols, K_SMALL, trans_step=(0.01, 0.02), rot_step_deg=(0.5, 1.0))
+    eng = E.Engine(ctx, E.default_config(rows=rows, cols=cols, lanes=B, K=K_SMALL, record_capacity=n, keyframe_capacity=8,
+                                         visratio_odo=0.985, visratio_integr=0.97))
+    for k in range(n):
+        eng.step(depth[k], rgb[k])
+    counts = eng.keyframe_counts()
+    pairs = [(l, s) for l in range(B) for s in range(int(counts[l]))]
+    srcs, _ = eng.keyframe_sources(pairs)
+    kfs = [eng.read_keyframe(l, s) for l, s in pairs]
+    cl = CL.Cloud(ctx, rows, cols, len(pairs))
+    pts, _ = cl.build(srcs, K_SMALL, "novel")
+    raw = np.concatenate([cloud_numpy(make_block(a["overlap_mask"], a["colors"], a["depthinv"], a["normals"]), rows, cols, K_SMALL, a["R"],
+                                      a["t"], "novel") for a in kfs])
+    assert records_equal(CL.as_numpy(pts), raw)[0]
+    got, mask, plan = check(ctx, raw, 0.03, 6, dev=pts)
+    assert 0 < plan.kept < len(raw)
+    kept = OL.radius_filter(ctx, pts, 0.03, 6)
+    ekept = raw[mask]
+    assert records_equal(CL.as_numpy(kept), ekept)[0]
+    vox = VX.voxel_grid(ctx, kept, 0.01)
+    assert records_equal(VX.as_numpy(vox), voxel_numpy(ekept, 0.01))[0] and 0 < len(vox) < plan.kept
+    cl.close(); eng.close()
+
+
+def test_outlier_injected_on_the_chunked_cloud(ctx):
+    """the 2-chunk noise-free run of test_voxel_chunked_cloud_against_the_scene plus 200 points 0.3 m in front of the height field, 0.1 m
+    apart: the field's slope stays below 1.3, so each is farther than 0.18 m from the surface and has no neighbour within r = 2 cm; with
+    min_neighbours >= 1 all of them go.  The share of genuine points removed is printed, not asserted; measured on the MI355X: 0.436 % of
+    45 609 at min_neighbours = 1, 5.453 % at 4."""
+    rows, cols, n = 120, 160, 24
+    seq = synth.make_sequence(n, K=K_SMALL, rows=rows, cols=cols, device="cuda", noise=False, dropout=0.0, trans_step=(0.01, 0.02),
+                              rot_step_deg=(0.5, 1.0))
+    depth, rgb = seq["depth"].to(torch.int16).contiguous(), seq["rgb"].contiguous()
+    _, _, _, pc = sequence.track_chunked(ctx, depth, rgb, 2, K_SMALL, cloud="novel", visratio_odo=0.985, visratio_integr=0.97)
+    raw = pc.numpy()
+    scene = synth.Scene(seed=synth.SEED)
+    fin = finite(raw)
+    gx, gy = np.meshgrid(np.arange(20) * 0.1, np.arange(10) * 0.1, indexing="ij")
+    x = (gx.reshape(-1) - 0.95 + float(np.median(raw["x"][fin]))).astype(F)
+    y = (gy.reshape(-1) - 0.45 + float(np.median(raw["y"][fin]))).astype(F)
+    z = (scene.depth(torch.from_numpy(x.astype(np.float64)), torch.from_numpy(y.astype(np.float64))).numpy() - 0.3).astype(F)
+    inj = xyz_cloud(x, y, z)
+    inj["r"] = 255
+    assert len(inj) == 200
+    rng = np.random.default_rng(38)
+    allp = np.concatenate([raw, inj])
+    perm = rng.permutation(len(allp))                     # the injected points anywhere in the input
+    allp = allp[perm]
+    is_inj = perm >= len(raw)
+    full = radius_counts_grid(allp, R, 4)
+    for minn in (1, 4):
+        got, mask, plan = check(ctx, allp, R, minn, full=full)
+        assert not got[is_inj].any() and not mask[is_inj].any()
+        genuine = ~is_inj & finite(allp)
+        gone = float((genuine & ~mask).sum()) / float(genuine.sum())
+        print(f"injected outliers: r = {R} m, min_neighbours = {minn}: 200 of 200 injected removed, {100 * gone:.3f} % of {int(genuine.sum())} genuine points removed")
+
+
+def _ply(path):
+    data = open(path, "rb").read()
+    head, body = data.split(b"end_header\n", 1)
+    nv = int([l for l in head.split(b"\n") if l.startswith(b"element vertex")][0].split()[-1])
+    assert len(body) == 27 * nv
+    return data, nv, body
+
+
+def test_track_dataset_cloud_radius_option(ctx, tmp_path):
+    rows, cols, n = 120, 160, 30
+    seq = synth.make_sequence(n, K=K_SMALL, rows=rows, cols=cols, device="cuda", trans_step=(0.02, 0.04), rot_step_deg=(1.0, 2.0))
+    root = tmp_path / "synth"
+    write_tum_folder(root, seq)
+    tool = os.path.join(ROOT, "tools", "track_dataset.py")
+    base = [sys.executable, tool, str(root), "--rows", str(rows), "--cols", str(cols), "--K"] + [repr(float(v)) for v in K_SMALL] + ["--chunks", "2"]
+    flt = ["--cloud-radius", "0.02", "--cloud-min-neighbours", "4"]
+    for bad in (flt, ["--cloud", str(tmp_path / "x.ply"), "--cloud-radius", "0.02"], ["--cloud", str(tmp_path / "x.ply"), "--cloud-min-neighbours", "4"],
+                ["--cloud", str(tmp_path / "x.ply"), "--cloud-radius", "0", "--cloud-min-neighbours", "4"]):
+        r = subprocess.run(base + bad, capture_output=True, text=True, timeout=300)
+        assert r.returncode != 0 and "--cloud" in r.stderr, (bad, r.stderr[-500:])
+    assert not (tmp_path / "x.ply").exists()
+    runs = {}
+    for name, extra in (("raw", []), ("kept", flt), ("vox", flt + ["--voxel", "0.01"])):
+        r = subprocess.run(base + ["--out", str(tmp_path / f"traj_{name}.txt"), "--cloud", str(tmp_path / f"{name}.ply")] + extra,
+                           capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        runs[name] = r.stdout
+    assert (tmp_path / "traj_raw.txt").read_bytes() == (tmp_path / "traj_kept.txt").read_bytes() == (tmp_path / "traj_vox.txt").read_bytes()
+    raw, nraw, _ = _ply(tmp_path / "raw.ply")
+    kept, nkept, _ = _ply(tmp_path / "kept.ply")
+    vox, nvox, _ = _ply(tmp_path / "vox.ply")
+    assert 0 < nvox < nkept < nraw
+    assert f"{nkept} kept of {nraw}" in runs["kept"] and f"{nkept} kept of {nraw}" in runs["vox"] and f"{nvox} voxels" in runs["vox"], runs["vox"]
+    assert "kept of" not in runs["raw"]
+    # --cloud alone is what it was: the raw cloud of the same run in process; the filtered files are the mirror applied to its records
+    gs = tum.Dataset(str(root))
+    frames = [gs.grab(k, rows, cols) for k in range(len(gs))]
+    gs.close()
+    depth = torch.from_numpy(np.stack([f[0] for f in frames]).view(np.int16)).cuda()
+    rgb = torch.from_numpy(np.stack([f[1] for f in frames])).cuda()
+    _, _, _, pc = sequence.track_chunked(ctx, depth, rgb, 2, K_SMALL, cloud="novel", use_graph=0)
+    assert CL.ply_bytes(pc.points) == raw
+    ekept = radius_filter_numpy(pc.numpy(), 0.02, 4)[2]
+    assert len(ekept) == nkept and CL.ply_bytes(upload(ekept)) == kept
+    assert CL.ply_bytes(upload(voxel_numpy(ekept, 0.01))) == vox

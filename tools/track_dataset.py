@@ -39,6 +39,10 @@ def main():
     ap.add_argument("--voxel", type=float, default=None, metavar="LEAF",
                     help="with --cloud: write the voxel-grid filtered map (centroids of LEAF-metre cells, as the reference writes its map: "
                     "0.01) instead of every point; with several ranks each rank filters its own points (voxels are not merged across ranks)")
+    ap.add_argument("--cloud-radius", type=float, default=None, metavar="R",
+                    help="with --cloud and --cloud-min-neighbours: first remove the isolated points, those with fewer than N other points of "
+                    "the rank's cloud within R metres (DESIGN.md section 15); --voxel then filters what is left")
+    ap.add_argument("--cloud-min-neighbours", type=int, default=None, metavar="N", help="with --cloud-radius: the neighbours a point needs to stay")
     ap.add_argument("--optimise", nargs="?", const="auto", default=None, choices=["auto", "multilevel", "single"],
                     help="optimise the trajectory with the pose-graph back-end once over the run (single rank; DESIGN.md section 11)")
     ap.add_argument("--loops", default=None, choices=["auto", "appearance"],
@@ -58,6 +62,16 @@ def main():
     args = ap.parse_args()
     if args.voxel is not None and not args.cloud:
         ap.error("--voxel needs --cloud")
+    if (args.cloud_radius is None) != (args.cloud_min_neighbours is None):
+        ap.error("--cloud-radius and --cloud-min-neighbours need each other")
+    if args.cloud_radius is not None:
+        if not args.cloud:
+            ap.error("--cloud-radius / --cloud-min-neighbours need --cloud")
+        from rgbid import outlier as OL
+        try:
+            OL.radius32(args.cloud_radius); OL.neighbour_args(args.cloud_min_neighbours)
+        except ValueError as e:
+            ap.error(str(e))
 
     world = int(os.environ.get("WORLD_SIZE", "1")); rank = int(os.environ.get("RANK", "0")); local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     assert torch.cuda.is_available(), "needs a HIP device (there is no CPU path)"
@@ -129,14 +143,18 @@ def main():
         if world > 1:
             root, ext = os.path.splitext(path)
             path = f"{root}.rank{rank}{ext}"
+        points, said = pc.points, f"rank {rank}: {len(pc)} points of {len(pc.keyframes)} keyframes"
+        if args.cloud_radius is not None:
+            points = OL.radius_filter(ctx, points, args.cloud_radius, args.cloud_min_neighbours)
+            said += f" -> {points.shape[0]} kept of {len(pc)} ({args.cloud_min_neighbours} within {args.cloud_radius:g} m)"
         if args.voxel is None:
-            CL.write_ply(path, pc.points)
-            print(f"rank {rank}: {len(pc)} points of {len(pc.keyframes)} keyframes -> {path}")
+            CL.write_ply(path, points)
+            print(f"{said} -> {path}")
         else:
             from rgbid import voxel as VX
-            vox, plan = VX.voxel_grid(ctx, pc.points, args.voxel, return_plan=True)
+            vox, plan = VX.voxel_grid(ctx, points, args.voxel, return_plan=True)
             CL.write_ply(path, vox)
-            print(f"rank {rank}: {len(pc)} points of {len(pc.keyframes)} keyframes -> {plan.voxels} voxels of {args.voxel:g} m -> {path}")
+            print(f"{said} -> {plan.voxels} voxels of {args.voxel:g} m -> {path}")
     if comm is not None:
         comm.close()
     if rank == 0:
