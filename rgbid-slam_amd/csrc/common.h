@@ -219,14 +219,9 @@ __device__ __forceinline__ float wave_sum_l63(float v) {
   v = dpp_add<0x143, 0xc>(v);  // row_bcast:31 -> rows 2,3
   return v;
 }
-// wave total broadcast to every lane (uniform, lives in an SGPR)
+// wave total broadcast to every lane (uniform, lives in an SGPR); integers and double: the template of wave_device.h
 __device__ __forceinline__ float wave_sum(float v) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_sum_l63(v)), 63));
-}
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 inline int div_up(int a, int b) { return (a + b - 1) / b; }

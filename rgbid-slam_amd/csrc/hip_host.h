@@ -1,5 +1,5 @@
 // hip_host.h -- the host-side plumbing every C-ABI handle shares: one status path, one allocation function, one owner of a handle's
-// buffers, one stage timer.  Host code only; a new feature file takes these instead of writing its own.
+// buffers, one destroy, one stage timer.  Host code only; a new feature file takes these instead of writing its own.
 #pragma once
 #include "../../include/rgbid.h"
 #include "ctx.h"
@@ -54,6 +54,16 @@ struct Buffers {
     return RGBID_OK;
   }
 };
+
+// the destroy of a handle whose state is its Buffers and StageTimer: the context's stream may still read its tables, so it is drained first
+template <class H>
+int destroy_handle(H* h) {
+  if (!h) return RGBID_OK;
+  (void)hipSetDevice(h->ctx->device);
+  if (h->ctx->stream) (void)hipStreamSynchronize(h->ctx->stream);
+  delete h;
+  return RGBID_OK;
+}
 
 // N events around the stages of a handle's calls: created on the first enable (a later enable creates what an earlier one could not),
 // recorded only while enabled, destroyed with the handle -- declare it after the handle's Buffers, whose release clears the sticky error.

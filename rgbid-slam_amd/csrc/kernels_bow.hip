@@ -19,6 +19,7 @@
 #include "../../include/rgbid_bow.h"
 #include "common.h"
 #include "hip_host.h"
+#include "wave_device.h"
 
 #include <algorithm>
 #include <cmath>
@@ -58,13 +59,6 @@ __device__ __forceinline__ void load_desc(const rgbid_loopfeat_kp* kp, u64 a[4])
 }
 __device__ __forceinline__ int ham(const u64 a[4], const u64* c) {
   return __popcll(a[0] ^ c[0]) + __popcll(a[1] ^ c[1]) + __popcll(a[2] ^ c[2]) + __popcll(a[3] ^ c[3]);
-}
-__device__ __forceinline__ u64 wave_sum_u64(u64 v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ unsigned lane_prefix(u64 m) {
-  return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
 }
 
 // atomicMax of per-lane keys on far[node]: when every active lane of the wave names the same node (the whole root level, most of the next)
@@ -315,19 +309,14 @@ __device__ __forceinline__ void sort_words(int* w, const int* __restrict__ words
 
 // the places where a run of equal words starts, compacted in order into hp[0 .. ne), hp[ne] = cnt; returns ne (uniform)
 __device__ __forceinline__ int run_heads(const int* w, int cnt, int* hp, unsigned* wtot) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   unsigned running = 0;
   for (int base = 0; base < cnt; base += BT) {
     const int i = base + threadIdx.x;
     const bool head = i < cnt && (i == 0 || w[i] != w[i - 1]);
-    const u64 m = __ballot(head);
-    if (lane == 0) wtot[wave] = (unsigned)__popcll(m);
-    __syncthreads();
-    unsigned pos = running + lane_prefix(m);
-    for (int k = 0; k < wave; ++k) pos += wtot[k];
+    unsigned tot;
+    const unsigned pos = running + block_rank(head, wtot, tot);
     if (head) hp[pos] = i;   // pos < cnt
-    running += wtot[0] + wtot[1] + wtot[2] + wtot[3];
-    __syncthreads();
+    running += tot;
   }
   if (threadIdx.x == 0) hp[running] = cnt;
   __syncthreads();
@@ -363,7 +352,7 @@ __global__ __launch_bounds__(BT) void k_bow_vector(const int* __restrict__ words
       const int i = hp[e], word = w[i];
       part += (u64)(unsigned)(hp[e + 1] - i) * (u64)((word >= 0 && word < nodes_cap) ? weight[word] : 0u);
     }
-    part = wave_sum_u64(part);
+    part = wave_sum(part);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = part;
     __syncthreads();
     A = wsum[0] + wsum[1] + wsum[2] + wsum[3];
@@ -396,7 +385,7 @@ __device__ __forceinline__ u64 wave_score(QW qw, QV qv, int nq, const rgbid_bow_
     }
     if (lo < nq && qw(lo) == ce.word) s += (u64)min(qv(lo), ce.value);
   }
-  return wave_sum_u64(s);
+  return wave_sum(s);
 }
 
 __global__ __launch_bounds__(BT) void k_bow_score(const rgbid_bow_entry* __restrict__ bow, const int* __restrict__ bow_counts, int n_kf, int max_kp,
@@ -572,13 +561,7 @@ int rgbid_bow_create(rgbid_bow** out, rgbid_ctx* ctx, int k, int depth) {
   return RGBID_OK;
 }
 
-int rgbid_bow_destroy(rgbid_bow* v) {
-  if (!v) return RGBID_OK;
-  (void)hipSetDevice(v->ctx->device);
-  if (v->ctx->stream) (void)hipStreamSynchronize(v->ctx->stream);
-  delete v;
-  return RGBID_OK;
-}
+int rgbid_bow_destroy(rgbid_bow* v) { return destroy_handle(v); }
 
 int rgbid_bow_set_weights(rgbid_bow* v, const rgbid_loopfeat_kp* kps_dev, const int32_t* counts_dev, int n_kf, int max_keypoints) {
   if (!v || !bow_batch_ok(n_kf, max_keypoints)) return RGBID_E_INVALID;

@@ -13,6 +13,7 @@
 #include "../../include/rgbid_cloud.h"
 #include "common.h"
 #include "hip_host.h"
+#include "wave_device.h"
 
 #include <cstring>
 #include <new>
@@ -106,7 +107,7 @@ __device__ __forceinline__ void wave_prefix(unsigned c, unsigned& prefix, unsign
   prefix = 0; total = 0;
   for (int b = 0; b < 3; ++b) {
     const unsigned long long m = __ballot((c >> b) & 1u);
-    prefix += __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u)) << b;
+    prefix += lane_prefix(m) << b;
     total += (unsigned)__popcll(m) << b;
   }
 }
@@ -151,22 +152,6 @@ __global__ __launch_bounds__(CT) void k_cloud_count(const rgbid_cloud_src* __res
   }
 }
 
-// inclusive scan of one value per thread over the block (256 threads); returns the block total through `total`
-__device__ __forceinline__ unsigned block_scan_incl(unsigned v, unsigned* lds, unsigned& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned u = __shfl_up(v, o, 64);
-    if (lane >= o) v += u;
-  }
-  if (lane == 63) lds[wave] = v;
-  __syncthreads();
-  unsigned before = 0;
-  for (int i = 0; i < wave; ++i) before += lds[i];
-  total = lds[0] + lds[1] + lds[2] + lds[3];
-  __syncthreads();
-  return v + before;
-}
-
 // one block per keyframe: tile counts -> exclusive tile offsets (in place), keyframe total
 __global__ __launch_bounds__(CT) void k_cloud_scan_tiles(unsigned* __restrict__ tiles_io, unsigned* __restrict__ kf_total, int tiles) {
   __shared__ unsigned lds[CT / 64];
@@ -186,28 +171,17 @@ __global__ __launch_bounds__(CT) void k_cloud_scan_tiles(unsigned* __restrict__ 
 // one block: keyframe totals -> offsets[n + 1] (64-bit: a batch may hold more than 2^32 points)
 __global__ __launch_bounds__(CT) void k_cloud_scan_kfs(const unsigned* __restrict__ kf_total, unsigned long long* __restrict__ offsets, int n) {
   __shared__ unsigned long long lds[CT / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   unsigned long long carry = 0;
   for (int base = 0; base < n; base += CT) {
     const int i = base + threadIdx.x;
-    const unsigned long long v0 = i < n ? kf_total[i] : 0ull;
-    unsigned long long v = v0;
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned long long u = __shfl_up(v, o, 64);
-      if (lane >= o) v += u;
-    }
-    if (lane == 63) lds[wave] = v;
-    __syncthreads();
-    unsigned long long before = 0;
-    for (int j = 0; j < wave; ++j) before += lds[j];
-    const unsigned long long tot = lds[0] + lds[1] + lds[2] + lds[3];
-    __syncthreads();
-    if (i < n) offsets[i] = carry + before + v - v0;
+    const unsigned long long v = i < n ? kf_total[i] : 0ull;
+    unsigned long long tot;
+    const unsigned long long incl = block_scan_incl(v, lds, tot);
+    if (i < n) offsets[i] = carry + incl - v;
     carry += tot;
   }
   if (threadIdx.x == 0) offsets[n] = carry;
 }
-
 
 __global__ __launch_bounds__(CT) void k_cloud_emit(const rgbid_cloud_src* __restrict__ src, CloudGeom g, const unsigned* __restrict__ tile_off,
                                                    const unsigned long long* __restrict__ kf_off, uint4* __restrict__ out) {
@@ -312,13 +286,7 @@ int rgbid_cloud_create(rgbid_cloud** out, rgbid_ctx* ctx, int rows, int cols, in
   return RGBID_OK;
 }
 
-int rgbid_cloud_destroy(rgbid_cloud* c) {
-  if (!c) return RGBID_OK;
-  (void)hipSetDevice(c->ctx->device);
-  if (c->ctx->stream) (void)hipStreamSynchronize(c->ctx->stream);   // an emit may still read the tables
-  delete c;   // its Buffers free the tables
-  return RGBID_OK;
-}
+int rgbid_cloud_destroy(rgbid_cloud* c) { return destroy_handle(c); }   // an emit may still read the tables
 
 int rgbid_cloud_plan(rgbid_cloud* c, int n, const rgbid_cloud_src* src, const float K[4], int mode, unsigned long long* offsets) {
   if (!c || n < 0 || n > c->cap || (n > 0 && !src) || !K || !offsets || (mode != RGBID_CLOUD_ALL && mode != RGBID_CLOUD_NOVEL_ONLY))

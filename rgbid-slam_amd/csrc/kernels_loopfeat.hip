@@ -20,6 +20,7 @@
 #include "../../include/rgbid_cloud.h"
 #include "common.h"
 #include "hip_host.h"
+#include "wave_device.h"
 
 #include <cmath>
 #include <cstddef>
@@ -58,15 +59,6 @@ struct LfLevel {
 struct LfGeom { int rows, cols, levels, max_kp, cells, slots, resp_stride, pyr_stride; };   // level 0's size; totals over the levels; per-keyframe strides
 struct LfKinv { double m[9]; };
 struct LfStaged { int idx; float resp; };
-
-__device__ __forceinline__ unsigned lane_prefix(unsigned long long m) {
-  return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // the level whose range of a flat grid holds block b (uniform over the block: scalar loads of a table of at most 8 entries)
 __device__ __forceinline__ int lf_level_of(const LfLevel* __restrict__ lv, int levels, int b, int LfLevel::*off) {
@@ -302,7 +294,7 @@ __global__ __launch_bounds__(LT) void k_lf_match(const rgbid_loopfeat_kp* __rest
                                                  int* __restrict__ match_counts) {
   extern __shared__ unsigned long long cdesc[];   // [max_kp][4]
   __shared__ unsigned wtot[LT / 64];
-  const int pair = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int pair = blockIdx.x;
   const int q = pairs[2 * pair], c = pairs[2 * pair + 1];
   const bool ok = q >= 0 && q < n_kf && c >= 0 && c < n_kf;
   const int nq = ok ? min(max(counts[q], 0), max_kp) : 0, nc = ok ? min(max(counts[c], 0), max_kp) : 0;
@@ -332,15 +324,10 @@ __global__ __launch_bounds__(LT) void k_lf_match(const rgbid_loopfeat_kp* __rest
       }
     }
     const bool keep = valid && (float)d0 < ratio * (float)d1;
-    const unsigned long long m = __ballot(keep);
-    if (lane == 0) wtot[wave] = (unsigned)__popcll(m);
-    __syncthreads();
-    unsigned pos = running + lane_prefix(m);
-    for (int w = 0; w < wave; ++w) pos += wtot[w];
-    const unsigned total = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+    unsigned total;
+    const unsigned pos = running + block_rank(keep, wtot, total);
     if (keep && out) out[pos] = rgbid_loopfeat_corr{i, i0, d0, d1};   // pos < nq <= max_kp
     running += total;
-    __syncthreads();
   }
   if (threadIdx.x == 0) match_counts[pair] = (int)running;
 }
@@ -747,13 +734,7 @@ int rgbid_loopfeat_create_levels(rgbid_loopfeat** out, rgbid_ctx* ctx, int rows,
   return RGBID_OK;
 }
 
-int rgbid_loopfeat_destroy(rgbid_loopfeat* f) {
-  if (!f) return RGBID_OK;
-  (void)hipSetDevice(f->ctx->device);
-  if (f->ctx->stream) (void)hipStreamSynchronize(f->ctx->stream);
-  delete f;   // its Buffers free tables and scratch, its StageTimer the events
-  return RGBID_OK;
-}
+int rgbid_loopfeat_destroy(rgbid_loopfeat* f) { return destroy_handle(f); }
 
 int rgbid_loopfeat_layout(const rgbid_loopfeat* f, int* cells_x, int* cells_y, int* per_cell) {
   return rgbid_loopfeat_level_layout(f, 0, nullptr, nullptr, cells_x, cells_y, per_cell, nullptr);

@@ -15,7 +15,7 @@
 #include "../../include/rgbid_outlier.h"
 #include "common.h"
 #include "hip_host.h"
-#include "voxel_device.h"   // box, grid, keys, radix sort, flag compaction
+#include "voxel_device.h"   // box, grid, keys, radix sort, flag compaction; the sort workspace
 
 #include <cmath>
 #include <cstring>
@@ -142,20 +142,11 @@ struct KeepRec {
 
 struct rgbid_outlier {
   rgbid_ctx* ctx = nullptr;
-  unsigned long long cap = 0;
-  unsigned sort_tiles = 0, run_tiles = 0;      // at capacity
-  unsigned long long* keys[2] = {nullptr, nullptr};   // [cap] 8 B each (32-bit keys use the first half); the free one holds the unique keys after the sort
-  unsigned* idx[2] = {nullptr, nullptr};       // [cap + 1]; the free one holds the cell starts after the sort
+  SortWorkspace ws;                            // after the sort the free index buffer holds the cell starts, the free key buffer the unique keys;
+                                               // its bc holds the keep compaction's tile offsets from the plan until the emit
   float4* spos = nullptr;                      // [cap] sorted positions
   unsigned* counts = nullptr;                  // [cap] input order
   unsigned char* keep = nullptr;               // [cap] input order
-  unsigned* hist = nullptr;                    // [RADIX][sort_tiles]
-  unsigned* dtotal = nullptr;                  // [RADIX]
-  float* box_part = nullptr;                   // [VOX_MAX_GRID][6]
-  unsigned* box_cnt = nullptr;                 // [VOX_MAX_GRID]
-  unsigned* bc = nullptr;                      // [run_tiles]: the keep compaction's tile offsets stay valid until the emit
-  unsigned* slots = nullptr;                   // [SLOTS] box, finite count, cells, kept
-  unsigned* slots_host = nullptr;              // pinned
   // the last plan
   const rgbid_cloud_point* in = nullptr;
   unsigned long long n = 0, kept = 0;
@@ -172,28 +163,20 @@ namespace {
 template <typename K>
 int sort_and_count(rgbid_outlier* o, const float4* in, unsigned n, unsigned finite, const OutGrid& og, unsigned cap, unsigned min_neighbours) {
   hipStream_t s = o->ctx->stream;
-  K* keys[2] = {reinterpret_cast<K*>(o->keys[0]), reinterpret_cast<K*>(o->keys[1])};
+  SortWorkspace& w = o->ws;
   o->mark(2);
-  hipLaunchKernelGGL(k_vox_keys<K>, dim3(grid_of((n + VT - 1) / VT)), dim3(VT), 0, s, in, n, og.g, keys[0], o->idx[0]);
-  const int p = radix_sort_pairs<K>(s, keys, o->idx, n, bitlen(og.g.sentinel), o->hist, o->dtotal);
+  w.make_keys<K>(s, in, n, og.g);
+  const SortedPairs<K> sp = w.sort<K>(s, n, og.g);
   o->mark(3);
-  // the sorted pairs are in buffer p; the other buffers are free: cell starts in idx[p ^ 1], unique keys in keys[p ^ 1]
-  unsigned* starts = o->idx[p ^ 1];
-  K* ukeys = keys[p ^ 1];
-  hipLaunchKernelGGL(k_outlier_gather, dim3((finite + VT - 1) / VT), dim3(VT), 0, s, in, o->idx[p], finite, o->spos);
-  const unsigned ctiles = (finite + RUN_TILE - 1) / RUN_TILE;
-  const CellSrc<K> cs{keys[p], finite, starts, ukeys};
-  hipLaunchKernelGGL(k_vox_flag_count<CellSrc<K>>, dim3(ctiles), dim3(VT), 0, s, cs, o->bc);
-  hipLaunchKernelGGL(k_vox_scan1, dim3(1), dim3(VT), 0, s, o->bc, ctiles, o->slots, (int)SLOT_CELLS, starts, finite);
-  hipLaunchKernelGGL(k_vox_flag_write<CellSrc<K>>, dim3(ctiles), dim3(VT), 0, s, cs, o->bc);
+  hipLaunchKernelGGL(k_outlier_gather, dim3((finite + VT - 1) / VT), dim3(VT), 0, s, in, sp.idx, finite, o->spos);
+  const CellSrc<K> cs{sp.keys, finite, sp.starts, sp.scratch};
+  w.count_scan(s, cs, finite, SLOT_CELLS, sp.starts, finite);
+  w.write(s, cs, finite);
   o->mark(4);
-  hipLaunchKernelGGL(k_outlier_count<K>, dim3((n + VT - 1) / VT), dim3(VT), 0, s, o->spos, o->idx[p], n, finite, og, ukeys, starts, o->slots, cap,
+  hipLaunchKernelGGL(k_outlier_count<K>, dim3((n + VT - 1) / VT), dim3(VT), 0, s, o->spos, sp.idx, n, finite, og, sp.scratch, sp.starts, w.slots, cap,
                      min_neighbours, o->counts, o->keep);
   o->mark(5);
-  const unsigned ktiles = (n + RUN_TILE - 1) / RUN_TILE;
-  const KeepRec kr{o->keep, n, nullptr, nullptr};
-  hipLaunchKernelGGL(k_vox_flag_count<KeepRec>, dim3(ktiles), dim3(VT), 0, s, kr, o->bc);
-  hipLaunchKernelGGL(k_vox_scan1, dim3(1), dim3(VT), 0, s, o->bc, ktiles, o->slots, (int)SLOT_KEPT, (unsigned*)nullptr, 0u);
+  w.count_scan(s, KeepRec{o->keep, n, nullptr, nullptr}, n, SLOT_KEPT);   // the emit writes with these offsets
   o->mark(6);
   RGBID_HIP(hipGetLastError());
   return RGBID_OK;
@@ -210,40 +193,23 @@ int rgbid_outlier_create(rgbid_outlier** out, rgbid_ctx* ctx, unsigned long long
   (void)hipSetDevice(ctx->device);
   rgbid_outlier* o = new (std::nothrow) rgbid_outlier;
   if (!o) return RGBID_E_NOMEM;
-  o->ctx = ctx; o->cap = max_points;
-  o->sort_tiles = (unsigned)((max_points + SORT_TILE - 1) / SORT_TILE);
-  o->run_tiles = (unsigned)((max_points + RUN_TILE - 1) / RUN_TILE);
+  o->ctx = ctx;
   const size_t cap = (size_t)max_points;
-  int r = RGBID_OK;
-  for (int i = 0; i < 2 && !r; ++i) r = o->buf.alloc(&o->keys[i], sizeof(unsigned long long) * cap);
-  for (int i = 0; i < 2 && !r; ++i) r = o->buf.alloc(&o->idx[i], sizeof(unsigned) * (cap + 1));
+  int r = o->ws.alloc(o->buf, max_points);
   if (!r) r = o->buf.alloc(&o->spos, sizeof(float4) * cap);
   if (!r) r = o->buf.alloc(&o->counts, sizeof(unsigned) * cap);
   if (!r) r = o->buf.alloc(&o->keep, cap);
-  if (!r) r = o->buf.alloc(&o->hist, sizeof(unsigned) * RADIX * (size_t)o->sort_tiles);
-  if (!r) r = o->buf.alloc(&o->dtotal, sizeof(unsigned) * RADIX);
-  if (!r) r = o->buf.alloc(&o->box_part, sizeof(float) * 6 * VOX_MAX_GRID);
-  if (!r) r = o->buf.alloc(&o->box_cnt, sizeof(unsigned) * VOX_MAX_GRID);
-  if (!r) r = o->buf.alloc(&o->bc, sizeof(unsigned) * o->run_tiles);
-  if (!r) r = o->buf.alloc(&o->slots, sizeof(unsigned) * SLOTS);
-  if (!r) r = o->buf.alloc_host(&o->slots_host, sizeof(unsigned) * SLOTS);
   if (r) { rgbid_outlier_destroy(o); return r; }
   *out = o;
   return RGBID_OK;
 }
 
-int rgbid_outlier_destroy(rgbid_outlier* o) {
-  if (!o) return RGBID_OK;
-  (void)hipSetDevice(o->ctx->device);
-  if (o->ctx->stream) (void)hipStreamSynchronize(o->ctx->stream);   // an emit may still read the tables
-  delete o;   // its Buffers free the tables, its StageTimer the events
-  return RGBID_OK;
-}
+int rgbid_outlier_destroy(rgbid_outlier* o) { return destroy_handle(o); }   // an emit may still read the tables
 
 int rgbid_outlier_plan(rgbid_outlier* o, const rgbid_cloud_point* in_dev, unsigned long long n, float radius, unsigned cap,
                        unsigned min_neighbours, unsigned long long stats[3], unsigned long long* kept) {
   RGBID_FP_STRICT
-  if (!o || !kept || n > o->cap || (n > 0 && !in_dev) || (((uintptr_t)in_dev) & 15)) return RGBID_E_INVALID;
+  if (!o || !kept || !records_in_ok(in_dev, n, o->ws.cap)) return RGBID_E_INVALID;
   if (!(std::isfinite(radius) && radius >= RGBID_OUTLIER_MIN_RADIUS && radius <= RGBID_OUTLIER_MAX_RADIUS)) return RGBID_E_INVALID;
   if (cap == 0 || min_neighbours > cap) return RGBID_E_INVALID;
   o->kept = 0; o->n = 0; o->in = nullptr; o->counted = false;
@@ -255,39 +221,29 @@ int rgbid_outlier_plan(rgbid_outlier* o, const rgbid_cloud_point* in_dev, unsign
   RGBID_HIP(hipStreamSynchronize(s));   // the previous emit has read the tables
   const float4* in = reinterpret_cast<const float4*>(in_dev);
   const unsigned nu = (unsigned)n;
-  const unsigned nb = grid_of((n + VT - 1) / VT);
   o->plan_timed = false; o->emit_timed = false;
   o->mark(0);
-  hipLaunchKernelGGL(k_vox_box, dim3(nb), dim3(VT), 0, s, in, nu, o->box_part, o->box_cnt);
-  hipLaunchKernelGGL(k_vox_box_final, dim3(1), dim3(64), 0, s, o->box_part, o->box_cnt, (int)nb, o->slots);
+  o->ws.box(s, in, nu);
   o->mark(1);
-  RGBID_HIP(hipGetLastError());
-  RGBID_HIP(hipMemcpyAsync(o->slots_host, o->slots, sizeof(unsigned) * SLOTS, hipMemcpyDeviceToHost, s));
-  RGBID_HIP(hipStreamSynchronize(s));
-  const unsigned finite = o->slots_host[SLOT_FINITE];
+  unsigned finite;
+  float lo[3], hi[3];
+  if (int r = o->ws.read_box(s, finite, lo, hi)) return r;
   if (stats) stats[0] = finite;
   if (finite == 0) { o->n = n; return RGBID_OK; }   // every count is 0, nothing is kept
-  float lo[3], hi[3];
-  memcpy(lo, o->slots_host + SLOT_BOX, sizeof lo);
-  memcpy(hi, o->slots_host + SLOT_BOX + 3, sizeof hi);
   const float cell = radius * RGBID_OUTLIER_CELL_FACTOR;
   const float leaf[3] = {cell, cell, cell};
   OutGrid og;
   long long gr[6];
-  const int r = form_grid(lo, hi, leaf, og.g, gr);
-  if (r) return r;
+  if (int r = form_grid(lo, hi, leaf, og.g, gr)) return r;
   for (int a = 0; a < 3; ++a) {   // the bound of the 3 x 3 x 3 walk: |floorf(p * inv)| <= 2^18 at both ends of the box
     if (gr[a] < -(long long)RGBID_OUTLIER_MAX_CELL || gr[a] + gr[3 + a] - 1 > (long long)RGBID_OUTLIER_MAX_CELL) return RGBID_E_INVALID;
     og.d[a] = (int)gr[3 + a];
   }
   og.r2 = radius * radius;
-  const int e = og.g.sentinel < (1ull << 32) ? sort_and_count<unsigned>(o, in, nu, finite, og, cap, min_neighbours)
-                                             : sort_and_count<unsigned long long>(o, in, nu, finite, og, cap, min_neighbours);
-  if (e) return e;
-  RGBID_HIP(hipMemcpyAsync(o->slots_host, o->slots, sizeof(unsigned) * SLOTS, hipMemcpyDeviceToHost, s));
-  RGBID_HIP(hipStreamSynchronize(s));
-  const unsigned k = o->slots_host[SLOT_KEPT];
-  if (stats) { stats[1] = o->slots_host[SLOT_CELLS]; stats[2] = k; }
+  if (int r = with_key_type(og.g, [&](auto k) { return sort_and_count<decltype(k)>(o, in, nu, finite, og, cap, min_neighbours); })) return r;
+  if (int r = o->ws.read_slots(s)) return r;
+  const unsigned k = o->ws.slots_host[SLOT_KEPT];
+  if (stats) { stats[1] = o->ws.slots_host[SLOT_CELLS]; stats[2] = k; }
   *kept = k;
   o->kept = k; o->n = n; o->in = in_dev; o->counted = true;
   o->plan_timed = o->timer.on;
@@ -307,12 +263,11 @@ int rgbid_outlier_counts(rgbid_outlier* o, uint32_t* counts_dev) {
 int rgbid_outlier_emit(rgbid_outlier* o, rgbid_cloud_point* out_dev, unsigned long long capacity) {
   if (!o) return RGBID_E_INVALID;
   if (o->kept == 0) return RGBID_OK;
-  if (!out_dev || capacity < o->kept || (((uintptr_t)out_dev) & 15)) return RGBID_E_INVALID;
+  if (!records_out_ok(out_dev, capacity, o->kept)) return RGBID_E_INVALID;
   (void)hipSetDevice(o->ctx->device);
   const unsigned nu = (unsigned)o->n;
-  const KeepRec kr{o->keep, nu, reinterpret_cast<const uint4*>(o->in), reinterpret_cast<uint4*>(out_dev)};
   o->mark(7);
-  hipLaunchKernelGGL(k_vox_flag_write<KeepRec>, dim3((nu + RUN_TILE - 1) / RUN_TILE), dim3(VT), 0, o->ctx->stream, kr, o->bc);
+  o->ws.write(o->ctx->stream, KeepRec{o->keep, nu, reinterpret_cast<const uint4*>(o->in), reinterpret_cast<uint4*>(out_dev)}, nu);
   o->mark(8);
   RGBID_HIP(hipGetLastError());
   o->emit_timed = o->timer.on;

@@ -15,7 +15,7 @@
 #include "../../include/rgbid_voxel.h"
 #include "common.h"
 #include "hip_host.h"
-#include "voxel_device.h"   // box, grid, keys, radix sort, flag compaction
+#include "voxel_device.h"   // box, grid, keys, radix sort, flag compaction; the sort workspace
 
 #include <cmath>
 #include <cstddef>
@@ -89,17 +89,7 @@ __global__ __launch_bounds__(VT) void k_vox_emit(const uint4* __restrict__ in, c
 
 struct rgbid_voxel {
   rgbid_ctx* ctx = nullptr;
-  unsigned long long cap = 0;
-  unsigned sort_tiles = 0, run_tiles = 0;      // at capacity
-  unsigned long long* keys[2] = {nullptr, nullptr};   // [cap] 8 B each (32-bit keys use the first half); the free one holds vbeg | vend after the sort
-  unsigned* idx[2] = {nullptr, nullptr};       // [cap + 1]; the free one holds the run starts after the sort
-  unsigned* hist = nullptr;                    // [RADIX][sort_tiles]
-  unsigned* dtotal = nullptr;                  // [RADIX]
-  float* box_part = nullptr;                   // [VOX_MAX_GRID][6]
-  unsigned* box_cnt = nullptr;                 // [VOX_MAX_GRID]
-  unsigned* bc = nullptr;                      // [run_tiles]
-  unsigned* slots = nullptr;                   // [SLOTS] box, finite count, runs, voxels
-  unsigned* slots_host = nullptr;              // pinned
+  SortWorkspace ws;                            // after the sort the free index buffer holds the run starts, the free key buffer vbeg | vend
   // the last plan (voxels == 0: nothing to emit)
   const rgbid_cloud_point* in = nullptr;
   const unsigned* sidx = nullptr;
@@ -118,32 +108,27 @@ namespace {
 template <typename K>
 int sort_and_runs(rgbid_voxel* v, const float4* in, unsigned n, unsigned finite, const VoxGrid& g, unsigned min_points) {
   hipStream_t s = v->ctx->stream;
-  K* keys[2] = {reinterpret_cast<K*>(v->keys[0]), reinterpret_cast<K*>(v->keys[1])};
+  SortWorkspace& w = v->ws;
   v->mark(2);
-  hipLaunchKernelGGL(k_vox_keys<K>, dim3(grid_of((n + VT - 1) / VT)), dim3(VT), 0, s, in, n, g, keys[0], v->idx[0]);
+  w.make_keys<K>(s, in, n, g);
   v->mark(3);
-  const int p = radix_sort_pairs<K>(s, keys, v->idx, n, bitlen(g.sentinel), v->hist, v->dtotal);
+  const SortedPairs<K> sp = w.sort<K>(s, n, g);
   v->mark(4);
-  // the sorted pairs are in buffer p; the other buffers are free: run starts in idx[p ^ 1], voxel bounds in keys[p ^ 1]
-  unsigned* starts = v->idx[p ^ 1];
-  unsigned* vbeg = reinterpret_cast<unsigned*>(v->keys[p ^ 1]);
-  unsigned* vend = vbeg + v->cap;
-  const unsigned rtiles = (finite + RUN_TILE - 1) / RUN_TILE;
-  const HeadSrc<K> hs{keys[p], finite, starts};
-  hipLaunchKernelGGL(k_vox_flag_count<HeadSrc<K>>, dim3(rtiles), dim3(VT), 0, s, hs, v->bc);
-  hipLaunchKernelGGL(k_vox_scan1, dim3(1), dim3(VT), 0, s, v->bc, rtiles, v->slots, (int)SLOT_RUNS, starts, finite);
-  hipLaunchKernelGGL(k_vox_flag_write<HeadSrc<K>>, dim3(rtiles), dim3(VT), 0, s, hs, v->bc);
+  const HeadSrc<K> hs{sp.keys, finite, sp.starts};
+  w.count_scan(s, hs, finite, SLOT_RUNS, sp.starts, finite);
+  w.write(s, hs, finite);
   if (min_points > 1) {
-    const KeepSrc ks{starts, v->slots + SLOT_RUNS, min_points, vbeg, vend};
-    hipLaunchKernelGGL(k_vox_flag_count<KeepSrc>, dim3(rtiles), dim3(VT), 0, s, ks, v->bc);
-    hipLaunchKernelGGL(k_vox_scan1, dim3(1), dim3(VT), 0, s, v->bc, rtiles, v->slots, (int)SLOT_VOXELS, (unsigned*)nullptr, 0u);
-    hipLaunchKernelGGL(k_vox_flag_write<KeepSrc>, dim3(rtiles), dim3(VT), 0, s, ks, v->bc);
+    unsigned* vbeg = reinterpret_cast<unsigned*>(sp.scratch);
+    unsigned* vend = vbeg + w.cap;
+    const KeepSrc ks{sp.starts, w.slots + SLOT_RUNS, min_points, vbeg, vend};
+    w.count_scan(s, ks, finite, SLOT_VOXELS);
+    w.write(s, ks, finite);
     v->vbeg = vbeg; v->vend = vend;
   } else {
-    v->vbeg = starts; v->vend = starts + 1;     // every run has >= 1 member
+    v->vbeg = sp.starts; v->vend = sp.starts + 1;     // every run has >= 1 member
   }
   v->mark(5);
-  v->sidx = v->idx[p];
+  v->sidx = sp.idx;
   RGBID_HIP(hipGetLastError());
   return RGBID_OK;
 }
@@ -159,36 +144,17 @@ int rgbid_voxel_create(rgbid_voxel** out, rgbid_ctx* ctx, unsigned long long max
   (void)hipSetDevice(ctx->device);
   rgbid_voxel* v = new (std::nothrow) rgbid_voxel;
   if (!v) return RGBID_E_NOMEM;
-  v->ctx = ctx; v->cap = max_points;
-  v->sort_tiles = (unsigned)((max_points + SORT_TILE - 1) / SORT_TILE);
-  v->run_tiles = (unsigned)((max_points + RUN_TILE - 1) / RUN_TILE);
-  const size_t cap = (size_t)max_points;
-  int r = RGBID_OK;
-  for (int i = 0; i < 2 && !r; ++i) r = v->buf.alloc(&v->keys[i], sizeof(unsigned long long) * cap);
-  for (int i = 0; i < 2 && !r; ++i) r = v->buf.alloc(&v->idx[i], sizeof(unsigned) * (cap + 1));
-  if (!r) r = v->buf.alloc(&v->hist, sizeof(unsigned) * RADIX * (size_t)v->sort_tiles);
-  if (!r) r = v->buf.alloc(&v->dtotal, sizeof(unsigned) * RADIX);
-  if (!r) r = v->buf.alloc(&v->box_part, sizeof(float) * 6 * VOX_MAX_GRID);
-  if (!r) r = v->buf.alloc(&v->box_cnt, sizeof(unsigned) * VOX_MAX_GRID);
-  if (!r) r = v->buf.alloc(&v->bc, sizeof(unsigned) * v->run_tiles);
-  if (!r) r = v->buf.alloc(&v->slots, sizeof(unsigned) * SLOTS);
-  if (!r) r = v->buf.alloc_host(&v->slots_host, sizeof(unsigned) * SLOTS);
-  if (r) { rgbid_voxel_destroy(v); return r; }
+  v->ctx = ctx;
+  if (int r = v->ws.alloc(v->buf, max_points)) { rgbid_voxel_destroy(v); return r; }
   *out = v;
   return RGBID_OK;
 }
 
-int rgbid_voxel_destroy(rgbid_voxel* v) {
-  if (!v) return RGBID_OK;
-  (void)hipSetDevice(v->ctx->device);
-  if (v->ctx->stream) (void)hipStreamSynchronize(v->ctx->stream);   // an emit may still read the tables
-  delete v;   // its Buffers free the tables, its StageTimer the events
-  return RGBID_OK;
-}
+int rgbid_voxel_destroy(rgbid_voxel* v) { return destroy_handle(v); }   // an emit may still read the tables
 
 int rgbid_voxel_plan(rgbid_voxel* v, const rgbid_cloud_point* in_dev, unsigned long long n, const float leaf[3],
                      unsigned min_points, long long grid[6], unsigned long long stats[3], unsigned long long* voxels) {
-  if (!v || !leaf || !voxels || n > v->cap || (n > 0 && !in_dev) || (((uintptr_t)in_dev) & 15)) return RGBID_E_INVALID;
+  if (!v || !leaf || !voxels || !records_in_ok(in_dev, n, v->ws.cap)) return RGBID_E_INVALID;
   for (int a = 0; a < 3; ++a) if (!(std::isfinite(leaf[a]) && leaf[a] > 0.f)) return RGBID_E_INVALID;
   v->voxels = 0; v->in = nullptr;
   *voxels = 0;
@@ -200,33 +166,23 @@ int rgbid_voxel_plan(rgbid_voxel* v, const rgbid_cloud_point* in_dev, unsigned l
   RGBID_HIP(hipStreamSynchronize(s));   // the previous emit has read the tables
   const float4* in = reinterpret_cast<const float4*>(in_dev);
   const unsigned nu = (unsigned)n;
-  const unsigned nb = grid_of((n + VT - 1) / VT);
   v->plan_timed = false; v->emit_timed = false;
   v->mark(0);
-  hipLaunchKernelGGL(k_vox_box, dim3(nb), dim3(VT), 0, s, in, nu, v->box_part, v->box_cnt);
-  hipLaunchKernelGGL(k_vox_box_final, dim3(1), dim3(64), 0, s, v->box_part, v->box_cnt, (int)nb, v->slots);
+  v->ws.box(s, in, nu);
   v->mark(1);
-  RGBID_HIP(hipGetLastError());
-  RGBID_HIP(hipMemcpyAsync(v->slots_host, v->slots, sizeof(unsigned) * SLOTS, hipMemcpyDeviceToHost, s));
-  RGBID_HIP(hipStreamSynchronize(s));
-  const unsigned finite = v->slots_host[SLOT_FINITE];
+  unsigned finite;
+  float lo[3], hi[3];
+  if (int r = v->ws.read_box(s, finite, lo, hi)) return r;
   if (stats) stats[0] = finite;
   if (finite == 0) return RGBID_OK;
-  float lo[3], hi[3];
-  memcpy(lo, v->slots_host + SLOT_BOX, sizeof lo);
-  memcpy(hi, v->slots_host + SLOT_BOX + 3, sizeof hi);
   VoxGrid g;
   long long gr[6];
-  const int r = form_grid(lo, hi, leaf, g, gr);
-  if (r) return r;
+  if (int r = form_grid(lo, hi, leaf, g, gr)) return r;
   if (grid) memcpy(grid, gr, sizeof gr);
-  const int e = g.sentinel < (1ull << 32) ? sort_and_runs<unsigned>(v, in, nu, finite, g, min_points)
-                                          : sort_and_runs<unsigned long long>(v, in, nu, finite, g, min_points);
-  if (e) return e;
-  RGBID_HIP(hipMemcpyAsync(v->slots_host, v->slots, sizeof(unsigned) * SLOTS, hipMemcpyDeviceToHost, s));
-  RGBID_HIP(hipStreamSynchronize(s));
-  const unsigned runs = v->slots_host[SLOT_RUNS];
-  const unsigned vox = min_points > 1 ? v->slots_host[SLOT_VOXELS] : runs;
+  if (int r = with_key_type(g, [&](auto k) { return sort_and_runs<decltype(k)>(v, in, nu, finite, g, min_points); })) return r;
+  if (int r = v->ws.read_slots(s)) return r;
+  const unsigned runs = v->ws.slots_host[SLOT_RUNS];
+  const unsigned vox = min_points > 1 ? v->ws.slots_host[SLOT_VOXELS] : runs;
   if (stats) { stats[1] = runs; stats[2] = vox; }
   *voxels = vox;
   v->voxels = vox;
@@ -238,7 +194,7 @@ int rgbid_voxel_plan(rgbid_voxel* v, const rgbid_cloud_point* in_dev, unsigned l
 int rgbid_voxel_emit(rgbid_voxel* v, rgbid_voxel_point* out_dev, unsigned long long capacity) {
   if (!v) return RGBID_E_INVALID;
   if (v->voxels == 0) return RGBID_OK;
-  if (!out_dev || capacity < v->voxels || (((uintptr_t)out_dev) & 15)) return RGBID_E_INVALID;
+  if (!records_out_ok(out_dev, capacity, v->voxels)) return RGBID_E_INVALID;
   (void)hipSetDevice(v->ctx->device);
   const unsigned nv = (unsigned)v->voxels;
   v->mark(6);

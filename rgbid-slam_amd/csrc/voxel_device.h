@@ -1,12 +1,17 @@
-// voxel_device.h -- what the map filters over rgbid_cloud_point records share (kernels_voxel.hip, kernels_outlier.hip): the box of the
-// finite points, the float32 grid and its cell keys, the stable LSD radix sort of (key, index) pairs and the stable flag compaction.
+// voxel_device.h -- what the map filters over rgbid_cloud_point records share (kernels_voxel.hip, kernels_outlier.hip).  Device half: the
+// box of the finite points, the float32 grid and its cell keys, the stable LSD radix sort of (key, index) pairs and the stable flag
+// compaction (the wave and block primitives they stand on are wave_device.h's).  Host half: SortWorkspace, the buffers of one filter
+// handle and the launches over them, and the argument checks every plan / emit makes.
 // Everything has internal linkage: each including file compiles its own copy of the kernels it launches.
 #pragma once
 #include "../../include/rgbid.h"
 #include "common.h"
+#include "hip_host.h"
+#include "wave_device.h"
 
 #include <cmath>
 #include <cstddef>
+#include <cstring>
 
 namespace rgbid {
 namespace {
@@ -21,26 +26,6 @@ constexpr int VOX_MAX_GRID = 2048;           // grid-strided kernels: 256 CUs x 
 enum { SLOT_BOX = 0, SLOT_FINITE = 6, SLOT_RUNS = 7, SLOT_VOXELS = 8, SLOTS = 16 };
 
 __device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
-
-__device__ __forceinline__ unsigned lane_prefix(unsigned long long m) {
-  return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-}
-
-// inclusive scan of one value per thread over the block (256 threads); returns the block total through `total`
-__device__ __forceinline__ unsigned block_scan_incl(unsigned v, unsigned* lds, unsigned& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned u = __shfl_up(v, o, 64);
-    if (lane >= o) v += u;
-  }
-  if (lane == 63) lds[wave] = v;
-  __syncthreads();
-  unsigned before = 0;
-  for (int i = 0; i < wave; ++i) before += lds[i];
-  total = lds[0] + lds[1] + lds[2] + lds[3];
-  __syncthreads();
-  return v + before;
-}
 
 // ---- bounding box of the finite points ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(VT) void k_vox_box(const float4* __restrict__ in, unsigned n, float* __restrict__ part, unsigned* __restrict__ part_cnt) {
@@ -284,23 +269,17 @@ __global__ __launch_bounds__(VT) void k_vox_scan1(unsigned* __restrict__ bc, uns
 // items of a tile in (round, wave, lane) order: rank = tile offset + earlier rounds + lower waves + mbcnt
 template <class S>
 __global__ __launch_bounds__(VT) void k_vox_flag_write(S s, const unsigned* __restrict__ bc) {
-  __shared__ unsigned wsum[VT / 64];
+  __shared__ unsigned lds[VT / 64];
   const unsigned n = s.size();
   const size_t t0 = (size_t)blockIdx.x * RUN_TILE;
   if (t0 >= n) return;                 // uniform over the block
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   unsigned carry = bc[blockIdx.x];
   for (int j = 0; j < RUN_IPT; ++j) {
     const size_t i = t0 + j * VT + threadIdx.x;
     const bool f = i < n && s.flag((unsigned)i);
-    const unsigned long long m = __ballot(f);
-    if (lane == 0) wsum[wave] = (unsigned)__popcll(m);
-    __syncthreads();
-    unsigned before = 0;
-    for (int w = 0; w < wave; ++w) before += wsum[w];
-    const unsigned tot = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    __syncthreads();
-    if (f) s.write(carry + before + lane_prefix(m), (unsigned)i);
+    unsigned tot;
+    const unsigned rank = block_rank(f, lds, tot);
+    if (f) s.write(carry + rank, (unsigned)i);
     carry += tot;
   }
 }
@@ -339,20 +318,117 @@ int form_grid(const float lo[3], const float hi[3], const float leaf[3], VoxGrid
   return RGBID_OK;
 }
 
-// the sort of n (key, index) pairs by the low `bits` key bits, ping-ponging between the two buffers: three launches per 8-bit pass.
-// Returns the buffer that holds the sorted pairs.
-template <typename K>
-int radix_sort_pairs(hipStream_t s, K* const keys[2], unsigned* const idx[2], unsigned n, int bits, unsigned* hist, unsigned* dtotal) {
-  const unsigned ntiles = (n + SORT_TILE - 1) / SORT_TILE;
-  const int passes = (bits + 7) / 8;
-  int p = 0;
-  for (int pass = 0; pass < passes; ++pass, p ^= 1) {
-    hipLaunchKernelGGL(k_vox_hist<K>, dim3(ntiles), dim3(VT), 0, s, keys[p], n, 8 * pass, hist, ntiles);
-    hipLaunchKernelGGL(k_vox_scan_digits, dim3(RADIX), dim3(VT), 0, s, hist, ntiles, dtotal);
-    hipLaunchKernelGGL(k_vox_scatter<K>, dim3(ntiles), dim3(VT), 0, s, keys[p], idx[p], keys[p ^ 1], idx[p ^ 1], n, 8 * pass, hist, dtotal, ntiles);
-  }
-  return p;
+// calls f with a value of the key type the grid needs: 32-bit keys when the largest key + 1 < 2^32, 64-bit otherwise
+template <class F>
+int with_key_type(const VoxGrid& g, F&& f) { return g.sentinel < (1ull << 32) ? f(0u) : f(0ull); }
+
+// what every plan checks about its input records and every emit about its output: count against capacity, null, 16-byte alignment
+bool records_in_ok(const void* in_dev, unsigned long long n, unsigned long long cap) {
+  return n <= cap && (n == 0 || in_dev) && !(((uintptr_t)in_dev) & 15);
 }
+bool records_out_ok(const void* out_dev, unsigned long long capacity, unsigned long long records) {
+  return out_dev && capacity >= records && !(((uintptr_t)out_dev) & 15);
+}
+
+// the ping-pong buffers after a sort, for keys of type K
+template <typename K>
+struct SortedPairs {
+  const K* keys;           // [n] ascending, the non-finite records' sentinel last
+  const unsigned* idx;     // [n] their record indices, stable
+  unsigned* starts;        // the free index buffer [cap + 1]
+  K* scratch;              // the free key buffer: 8 B x cap whatever K is
+};
+
+// The buffers one filter handle sorts and compacts with, and the launches over them.  It launches and reads back; the stage marks and
+// the launch check (hipGetLastError) stay with the caller.  24 B per point of capacity + the tables.
+struct SortWorkspace {
+  unsigned long long cap = 0;
+  unsigned sort_tiles = 0, run_tiles = 0;             // at capacity
+  unsigned long long* keys[2] = {nullptr, nullptr};   // [cap] 8 B each (32-bit keys use the first half)
+  unsigned* idx[2] = {nullptr, nullptr};              // [cap + 1]
+  unsigned* hist = nullptr;                           // [RADIX][sort_tiles]
+  unsigned* dtotal = nullptr;                         // [RADIX]
+  float* box_part = nullptr;                          // [VOX_MAX_GRID][6]
+  unsigned* box_cnt = nullptr;                        // [VOX_MAX_GRID]
+  unsigned* bc = nullptr;                             // [run_tiles] tile offsets of the last count_scan: valid until the next one
+  unsigned* slots = nullptr;                          // [SLOTS] box, finite count, two compaction totals
+  unsigned* slots_host = nullptr;                     // pinned
+
+  int alloc(Buffers& buf, unsigned long long max_points) {
+    cap = max_points;
+    sort_tiles = (unsigned)((max_points + SORT_TILE - 1) / SORT_TILE);
+    run_tiles = (unsigned)((max_points + RUN_TILE - 1) / RUN_TILE);
+    const size_t c = (size_t)max_points;
+    int r = RGBID_OK;
+    for (int i = 0; i < 2 && !r; ++i) r = buf.alloc(&keys[i], sizeof(unsigned long long) * c);
+    for (int i = 0; i < 2 && !r; ++i) r = buf.alloc(&idx[i], sizeof(unsigned) * (c + 1));
+    if (!r) r = buf.alloc(&hist, sizeof(unsigned) * RADIX * (size_t)sort_tiles);
+    if (!r) r = buf.alloc(&dtotal, sizeof(unsigned) * RADIX);
+    if (!r) r = buf.alloc(&box_part, sizeof(float) * 6 * VOX_MAX_GRID);
+    if (!r) r = buf.alloc(&box_cnt, sizeof(unsigned) * VOX_MAX_GRID);
+    if (!r) r = buf.alloc(&bc, sizeof(unsigned) * run_tiles);
+    if (!r) r = buf.alloc(&slots, sizeof(unsigned) * SLOTS);
+    if (!r) r = buf.alloc_host(&slots_host, sizeof(unsigned) * SLOTS);
+    return r;
+  }
+
+  // the slot area as the stream leaves it -> slots_host; one host synchronisation
+  int read_slots(hipStream_t s) {
+    RGBID_HIP(hipMemcpyAsync(slots_host, slots, sizeof(unsigned) * SLOTS, hipMemcpyDeviceToHost, s));
+    RGBID_HIP(hipStreamSynchronize(s));
+    return RGBID_OK;
+  }
+
+  // box and count of the finite points of n records -> slots
+  void box(hipStream_t s, const float4* in, unsigned n) {
+    const unsigned nb = grid_of(((unsigned long long)n + VT - 1) / VT);
+    hipLaunchKernelGGL(k_vox_box, dim3(nb), dim3(VT), 0, s, in, n, box_part, box_cnt);
+    hipLaunchKernelGGL(k_vox_box_final, dim3(1), dim3(64), 0, s, box_part, box_cnt, (int)nb, slots);
+  }
+  int read_box(hipStream_t s, unsigned& finite, float lo[3], float hi[3]) {
+    RGBID_HIP(hipGetLastError());
+    if (int r = read_slots(s)) return r;
+    finite = slots_host[SLOT_FINITE];
+    memcpy(lo, slots_host + SLOT_BOX, 3 * sizeof(float));
+    memcpy(hi, slots_host + SLOT_BOX + 3, 3 * sizeof(float));
+    return RGBID_OK;
+  }
+
+  // one (key, index) pair per record into buffer 0
+  template <typename K>
+  void make_keys(hipStream_t s, const float4* in, unsigned n, const VoxGrid& g) {
+    hipLaunchKernelGGL(k_vox_keys<K>, dim3(grid_of(((unsigned long long)n + VT - 1) / VT)), dim3(VT), 0, s, in, n, g, reinterpret_cast<K*>(keys[0]), idx[0]);
+  }
+
+  // the sort of the n pairs by the bits a key of the grid can have, ping-ponging between the two buffers: three launches per 8-bit pass
+  template <typename K>
+  SortedPairs<K> sort(hipStream_t s, unsigned n, const VoxGrid& g) {
+    K* const k[2] = {reinterpret_cast<K*>(keys[0]), reinterpret_cast<K*>(keys[1])};
+    const unsigned ntiles = (n + SORT_TILE - 1) / SORT_TILE;
+    const int passes = (bitlen(g.sentinel) + 7) / 8;
+    int p = 0;
+    for (int pass = 0; pass < passes; ++pass, p ^= 1) {
+      hipLaunchKernelGGL(k_vox_hist<K>, dim3(ntiles), dim3(VT), 0, s, k[p], n, 8 * pass, hist, ntiles);
+      hipLaunchKernelGGL(k_vox_scan_digits, dim3(RADIX), dim3(VT), 0, s, hist, ntiles, dtotal);
+      hipLaunchKernelGGL(k_vox_scatter<K>, dim3(ntiles), dim3(VT), 0, s, k[p], idx[p], k[p ^ 1], idx[p ^ 1], n, 8 * pass, hist, dtotal, ntiles);
+    }
+    return SortedPairs<K>{k[p], idx[p], idx[p ^ 1], k[p ^ 1]};
+  }
+
+  // The stable compaction of the flagged items of a source of at most `items` items, in two calls that may lie in different API calls.
+  // count_scan: tile counts -> exclusive tile offsets in bc, the total in slots[slot]; with a tail, tail[total] = tail_val.
+  template <class S>
+  void count_scan(hipStream_t s, const S& src, unsigned items, int slot, unsigned* tail = nullptr, unsigned tail_val = 0u) {
+    const unsigned tiles = (items + RUN_TILE - 1) / RUN_TILE;
+    hipLaunchKernelGGL(k_vox_flag_count<S>, dim3(tiles), dim3(VT), 0, s, src, bc);
+    hipLaunchKernelGGL(k_vox_scan1, dim3(1), dim3(VT), 0, s, bc, tiles, slots, slot, tail, tail_val);
+  }
+  // write: every flagged item at its rank, with the bc of the count_scan over the same flags
+  template <class S>
+  void write(hipStream_t s, const S& src, unsigned items) {
+    hipLaunchKernelGGL(k_vox_flag_write<S>, dim3((items + RUN_TILE - 1) / RUN_TILE), dim3(VT), 0, s, src, bc);
+  }
+};
 
 }  // namespace
 }  // namespace rgbid

@@ -43,6 +43,20 @@ def kinv(K):
     return np.array(out[:], np.float64).reshape(3, 3)
 
 
+def records(points):
+    """assert that `points` is a contiguous CUDA uint8 tensor [M, 32] of 32-byte records (what the filters over a cloud take); -> points"""
+    assert isinstance(points, torch.Tensor) and points.is_cuda and points.dtype == torch.uint8 and points.dim() == 2 and points.shape[1] == 32, \
+        "points: a CUDA uint8 tensor [M, 32] of rgbid_cloud_point records"
+    assert points.is_contiguous(), "points must be contiguous"
+    return points
+
+
+def records_out(out):
+    """assert that `out` can take the 32-byte records of an emit: a contiguous CUDA uint8 tensor [>= M, 32]; -> out"""
+    assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.dim() == 2 and out.shape[1] == 32
+    return out
+
+
 def as_numpy(points):
     """[M, 32] uint8 records (a device or host tensor, or a numpy array) -> structured array of POINT_DTYPE"""
     a = points.cpu().numpy() if isinstance(points, torch.Tensor) else np.asarray(points)
@@ -69,7 +83,7 @@ class Cloud(_lib.CtxHandle):
 
     def emit(self, out):
         """write the points of the last plan into `out` (CUDA uint8 tensor [>= M, 32]).  Asynchronous on the context's stream."""
-        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.dim() == 2 and out.shape[1] == 32
+        records_out(out)
         self.L.rgbid_cloud_emit.argtypes = [C.c_void_p, C.c_void_p, C.c_ulonglong]
         check(self.L.rgbid_cloud_emit(self._h, C.c_void_p(out.data_ptr() if out.numel() else 0), C.c_ulonglong(out.shape[0])))
 

@@ -13,6 +13,7 @@ import torch
 
 from . import _lib
 from ._lib import check
+from .cloud import records, records_out
 
 MAX_POINTS = 1 << 31
 MAX_CELL = 1 << 18                      # RGBID_OUTLIER_MAX_CELL: the largest |floor(p * inv)| the plan accepts
@@ -70,13 +71,6 @@ class Plan:
         return f"Plan(kept={self.kept}, n={self.n}, finite={self.finite}, cells={self.cells})"
 
 
-def _records(points):
-    assert isinstance(points, torch.Tensor) and points.is_cuda and points.dtype == torch.uint8 and points.dim() == 2 and points.shape[1] == 32, \
-        "points: a CUDA uint8 tensor [M, 32] of rgbid_cloud_point records"
-    assert points.is_contiguous(), "points must be contiguous"
-    return points
-
-
 class RadiusFilter(_lib.CtxHandle):
     """Radius outlier filter for up to max_points input records per plan, on the context's stream."""
     _destroy = "rgbid_outlier_destroy"
@@ -94,7 +88,7 @@ class RadiusFilter(_lib.CtxHandle):
     def plan(self, points, radius, min_neighbours, cap=None):
         """grid, sort, count and mark pass over `points` (CUDA uint8 [M, 32] rgbid_cloud_point records) -> Plan.  Synchronises (on the
         context's stream: records written on torch's stream are waited for first)."""
-        _records(points)
+        records(points)
         r = radius32(radius)
         m, c = neighbour_args(min_neighbours, cap)
         stats = np.zeros(3, np.uint64); kept = C.c_ulonglong()
@@ -111,7 +105,7 @@ class RadiusFilter(_lib.CtxHandle):
 
     def emit(self, out):
         """write the kept records of the last plan into `out` (CUDA uint8 tensor [>= kept, 32]).  Asynchronous on the context's stream."""
-        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.dim() == 2 and out.shape[1] == 32
+        records_out(out)
         check(self.L.rgbid_outlier_emit(self._h, C.c_void_p(out.data_ptr() if out.numel() else 0), C.c_ulonglong(out.shape[0])))
 
     def timing(self, enable=True):

@@ -13,6 +13,7 @@ import torch
 
 from . import _lib
 from ._lib import check
+from .cloud import records, records_out
 
 # rgbid_voxel_point: centroid, mean normal, member count, mean colour, flags (bit 0: some member is novel)
 VOXEL_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"), ("count", "<u4"),
@@ -55,13 +56,6 @@ class Plan:
                 f"kept={self.kept})")
 
 
-def _records(points):
-    assert isinstance(points, torch.Tensor) and points.is_cuda and points.dtype == torch.uint8 and points.dim() == 2 and points.shape[1] == 32, \
-        "points: a CUDA uint8 tensor [M, 32] of rgbid_cloud_point records"
-    assert points.is_contiguous(), "points must be contiguous"
-    return points
-
-
 class VoxelGrid(_lib.CtxHandle):
     """Voxel-grid filter for up to max_points input records per plan, on the context's stream."""
     _destroy = "rgbid_voxel_destroy"
@@ -72,12 +66,13 @@ class VoxelGrid(_lib.CtxHandle):
         self.L.rgbid_voxel_create.argtypes = [C.c_void_p, C.c_void_p, C.c_ulonglong]
         self.L.rgbid_voxel_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]
         self.L.rgbid_voxel_emit.argtypes = [C.c_void_p, C.c_void_p, C.c_ulonglong]
+        self.L.rgbid_voxel_timing.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         self._created(self.L.rgbid_voxel_create(C.byref(self._h), ctx._h, C.c_ulonglong(self.max_points)))
 
     def plan(self, points, leaf=0.01, min_points=0):
         """grid, sort and count pass over `points` (CUDA uint8 [M, 32] rgbid_cloud_point records) -> Plan.  Synchronises (on the context's
         stream: records written on torch's stream are waited for first)."""
-        _records(points)
+        records(points)
         lf = (C.c_float * 3)(*leaf3(leaf))
         grid = np.zeros(6, np.int64); stats = np.zeros(3, np.uint64); nv = C.c_ulonglong()
         self.ctx.wait_torch_stream()
@@ -87,7 +82,7 @@ class VoxelGrid(_lib.CtxHandle):
 
     def emit(self, out):
         """write the voxels of the last plan into `out` (CUDA uint8 tensor [>= V, 32]).  Asynchronous on the context's stream."""
-        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.dim() == 2 and out.shape[1] == 32
+        records_out(out)
         check(self.L.rgbid_voxel_emit(self._h, C.c_void_p(out.data_ptr() if out.numel() else 0), C.c_ulonglong(out.shape[0])))
 
     def timing(self, enable=True):

@@ -314,6 +314,59 @@ def test_outlier_refusals(ctx):
         OL.RadiusFilter(ctx, (1 << 31) + 1)
 
 
+# ---- two filters on one context; the stage timer ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("nv, no", [(4097, 2049), (2049, 4097)])
+def test_voxel_and_outlier_interleaved_do_not_share_state(ctx, nv, no):
+    """a VoxelGrid and a RadiusFilter on one context, one past the sort tile (4 096) and one past the compaction tile (2 048), their plans
+    and emits interleaved both ways: every output equals, byte for byte, the output of the same filter run alone (a workspace buffer, the
+    slot area or the tile offsets shared between the handles, or kept in a static, would break this)"""
+    rng = np.random.default_rng(nv)
+    pv, po = upload(random_cloud(rng, nv)), upload(random_cloud(rng, no, spread=0.08))
+    leaf, minp, minn = 0.01, 2, 2
+    vox_alone = VX.voxel_grid(ctx, pv, leaf, minp)
+    kept_alone, cnt_alone = OL.radius_filter(ctx, po, R, minn, return_counts=True)
+    assert 0 < len(vox_alone) < nv and 0 < len(kept_alone) < no
+    vg, rf = VX.VoxelGrid(ctx, nv), OL.RadiusFilter(ctx, no)
+
+    def outputs(vp, op):
+        ctx.sync()
+        vox = torch.full((vp.voxels, 32), 0xA5, dtype=torch.uint8, device="cuda")
+        kept = torch.full((op.kept, 32), 0xA5, dtype=torch.uint8, device="cuda")
+        cnt = torch.full((no,), -1, dtype=torch.int32, device="cuda")
+        ctx.wait_torch_stream()
+        return vox, kept, cnt
+
+    for voxel_first in (True, False):
+        if voxel_first:                                   # voxel plan, outlier plan, voxel emit, outlier counts + emit
+            vp = vg.plan(pv, leaf, minp); op = rf.plan(po, R, minn)
+            vox, kept, cnt = outputs(vp, op)
+            vg.emit(vox); rf.counts(cnt); rf.emit(kept)
+        else:                                             # outlier plan, voxel plan, outlier counts + emit, voxel emit
+            op = rf.plan(po, R, minn); vp = vg.plan(pv, leaf, minp)
+            vox, kept, cnt = outputs(vp, op)
+            rf.counts(cnt); rf.emit(kept); vg.emit(vox)
+        ctx.sync()
+        assert torch.equal(vox, vox_alone), voxel_first
+        assert torch.equal(kept, kept_alone) and torch.equal(cnt, cnt_alone), voxel_first
+    vg.close(); rf.close()
+
+
+def test_voxel_and_outlier_stage_timing_keeps_its_shape(ctx):
+    """timing(True), one build / filter of 4 097 records, timing(False): the five stages of each filter by name, every value finite and
+    >= 0, their sum > 0; no magnitude is asserted"""
+    rng = np.random.default_rng(41)
+    dev = upload(random_cloud(rng, 4097))
+    vg, rf = VX.VoxelGrid(ctx, 4097), OL.RadiusFilter(ctx, 4097)
+    for h, run, stages in ((vg, lambda: vg.build(dev, 0.01, 2), VX.STAGES), (rf, lambda: rf.filter(dev, R, 2), OL.STAGES)):
+        h.timing(True)
+        assert len(run()) > 0
+        ms = h.timing(False)
+        print(type(h).__name__, "stage ms:", ms)
+        assert tuple(ms) == stages and len(stages) == 5
+        assert all(np.isfinite(v) and v >= 0 for v in ms.values()) and sum(ms.values()) > 0, ms
+    vg.close(); rf.close()
+
+
 # ---- the map chain ----------------------------------------------------------------------------------------------------------------
 def test_outlier_from_engine_exports(ctx):
     """engine exports -> Cloud.build -> RadiusFilter.filter -> voxel_grid, against the mirrors applied to the restated cloud"""

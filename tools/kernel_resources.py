@@ -45,7 +45,7 @@ def main():
         rows += resources(src)
     names = subprocess.run(["c++filt"], input="\n".join(r["mangled"] for r in rows), stdout=subprocess.PIPE, text=True).stdout.splitlines()
     for r, n in zip(rows, names):
-        r["name"] = re.sub(r"\(anonymous namespace\)::", "", n.split("(")[0].replace("void ", ""))
+        r["name"] = n.replace("(anonymous namespace)::", "").split("(")[0].replace("void ", "")   # the namespace first: its "(" is not the argument list's
     cols = ["name", "file", "vgprs", "agprs", "sgprs", "scratch_bytes_per_lane", "waves_per_simd", "lds_bytes_per_block"]
     with open(out, "w", newline="") as f:
         w = csv.writer(f)
