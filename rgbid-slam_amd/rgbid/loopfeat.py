@@ -376,14 +376,51 @@ def gate(kq, kc, matches, mask, rows, cols, min_inliers=MIN_INLIERS, min_hull=MI
     return bool(ok), int(len(sel)), hq, hc
 
 
+def compact_features(feats, bits, level):
+    """the records whose bit `level` is set, in order, at the front of every keyframe's row (the others zeroed): on the device"""
+    n, cap = bits.shape
+    slot = torch.arange(cap, device=bits.device)[None, :]
+    keep = (((bits >> level) & 1) != 0) & (slot < feats.counts[:, None])
+    order = torch.argsort((~keep).to(torch.uint8), dim=1, stable=True)
+    counts = keep.sum(1).to(torch.int32)
+    kps = torch.gather(feats.kps, 1, order[:, :, None].expand(-1, -1, feats.kps.shape[2]))
+    kps = torch.where((slot < counts[:, None])[:, :, None], kps, torch.zeros_like(kps)).contiguous()
+    return Features(kps, counts)
+
+
+def masked_features(ctx, feats, blocks, K, rows, cols, mask_level, batch=64, segment_k=None, segment_min=None, mask_out=None, max_segments=None):
+    """segment the keyframes (rgbid.segment), mark every keypoint with its mask bits and keep those of mask `mask_level`"""
+    from . import segment as SG
+    if not 0 < int(mask_level) < SG.DEFAULT_LEVELS:
+        raise ValueError(f"mask_level must lie in [0, {SG.DEFAULT_LEVELS}), got {mask_level!r}")
+    if blocks is None or len(blocks) != len(feats):
+        raise ValueError("mask_level > 0 needs the packed export block of every keyframe (blocks, or overlap_mask and normals in the keyframes)")
+
+    def bits_of(sg, s, res):
+        return sg.mask_keypoints(res[4], res[5], feats.kps[s:s + batch].contiguous(), feats.counts[s:s + batch].contiguous())
+    bits = torch.cat(SG.segment_batches(ctx, blocks, K, rows, cols, batch, max_segments, bits_of, k=segment_k, min_size=segment_min))
+    out = compact_features(feats, bits, int(mask_level))
+    if mask_out is not None:
+        kps, counts = out.numpy()
+        mask_out.update(bits=bits.cpu().numpy(), kps=kps, counts=counts)
+    return out
+
+
 def appearance_loops(ctx, keyframes, K, grey=None, max_keypoints=1000, min_separation=3, score_threshold=SCORE_THRESHOLD, per_query=(2, 2),
-                     batch=64, levels=1, scale=SCALE, proposal="match", vocabulary=None, shortlist_size=8):
+                     batch=64, levels=1, scale=SCALE, proposal="match", vocabulary=None, shortlist_size=8, mask_level=0, blocks=None,
+                     segment_k=None, segment_min=None, mask_out=None, max_segments=None):
     """features of all exported keyframes, `propose`, RANSAC and its gates.  keyframes: [dict(frame, depthinv, colors)] in export order.
     -> (pairs [(q, c)] that passed, guesses [(R, t)] = qTc_ini of each, report [dict(query, candidate, score, matches, inliers, hull_query,
     hull_candidate, ransac_ok)] over every proposed pair).  levels, scale: the feature pyramid (LoopFeat); the reference runs 8 levels at 1.2.
     proposal: "match" matches every pair; "bow" matches the shortlist_size candidates per keyframe that `vocabulary` ranks best, and the
     report gains bow_score and bow_rank.  vocabulary: a rgbid.bow.Vocabulary; None: one of the default size trained on these keyframes'
-    features; a path: the .npz of rgbid.bow.load when the file exists, otherwise one trained on these features and saved there."""
+    features; a path: the .npz of rgbid.bow.load when the file exists, otherwise one trained on these features and saved there.
+    mask_level m > 0: matching and the shortlist see only the keypoints that negentropy mask m of the keyframe keeps (rgbid.segment;
+    the reference's masked descriptors); it needs blocks, the packed export block of every keyframe (CUDA uint8 tensors or
+    rgbid.cloud Source records); segment_k, segment_min, max_segments: the segmenter's k, smallest segment and the segments per
+    keyframe its tables start with (rgbid.segment.segment_batches).  The records are compacted on the
+    device, keypoint indices in the results count the kept records.  mask_out (a dict) receives bits [n, max_keypoints] uint8 and the
+    compacted kps / counts as numpy.  mask_level 0 changes nothing."""
     import os
     from .posegraph import grey_from_colors
     if proposal not in ("match", "bow"):
@@ -400,6 +437,12 @@ def appearance_loops(ctx, keyframes, K, grey=None, max_keypoints=1000, min_separ
         parts = [lf.extract(np.stack(grey[s:s + batch]), np.stack([k["depthinv"] for k in keyframes[s:s + batch]]), K)
                  for s in range(0, len(keyframes), batch)]   # records do not depend on the batch
         feats = Features(torch.cat([p.kps for p in parts]), torch.cat([p.counts for p in parts]))
+        if mask_level:
+            if blocks is None and all("normals" in k and "overlap_mask" in k for k in keyframes):
+                blocks = [torch.from_numpy(np.concatenate([np.ascontiguousarray(k[f]).reshape(-1).view(np.uint8) for f in
+                                                           ("overlap_mask", "colors", "depthinv", "normals")])).to(f"cuda:{ctx.device}")
+                          for k in keyframes]
+            feats = masked_features(ctx, feats, blocks, K, rows, cols, mask_level, batch, segment_k, segment_min, mask_out, max_segments)
         voc, own, details = vocabulary, False, {}
         if proposal == "bow" and (voc is None or isinstance(voc, (str, os.PathLike))):
             from . import bow as BW

@@ -268,7 +268,9 @@ def optimise_run(ctx, R, t, chunk_records, first_frames, headers, keyframes, K, 
     loops: None, "auto" (candidates by distance on the trajectory), "appearance" (rgbid.loopfeat.appearance_loops: features, appearance
     proposal and RANSAC, no pose involved; each report row of a verified pair then also holds score, matches, inliers and hull ratios, and
     info["appearance"] lists every proposed pair; levels=, scale= among the keywords choose its feature pyramid, one level by default;
-    proposal="bow", vocabulary=, shortlist_size= shortlist the candidates with a binary vocabulary, rgbid.bow) or a list of (kf_a, kf_b)."""
+    proposal="bow", vocabulary=, shortlist_size= shortlist the candidates with a binary vocabulary, rgbid.bow; mask_level=, segment_k=,
+    segment_min= keep the features of a negentropy mask, rgbid.segment: the keyframes then also hold overlap_mask and normals) or a list
+    of (kf_a, kf_b)."""
     if optimise not in ("auto", "multilevel", "single"):
         raise ValueError(f"optimise must be 'auto', 'multilevel' or 'single', not {optimise!r}")
     P, E = graph_from_run(R, t, chunk_records, first_frames, headers)
@@ -278,7 +280,8 @@ def optimise_run(ctx, R, t, chunk_records, first_frames, headers, keyframes, K, 
             raise ValueError(f"loops must be None, 'auto', 'appearance' or a list of (kf_a, kf_b), not {loops!r}")
         if isinstance(loops, str) and loops == "appearance":
             from . import loopfeat
-            akw = {k: loop_kw.pop(k) for k in ("max_keypoints", "score_threshold", "per_query", "levels", "scale", "proposal", "vocabulary", "shortlist_size")
+            akw = {k: loop_kw.pop(k) for k in ("max_keypoints", "score_threshold", "per_query", "levels", "scale", "proposal", "vocabulary", "shortlist_size", "mask_level",
+                                               "segment_k", "segment_min", "mask_out", "max_segments", "blocks")
                    if k in loop_kw}
             pairs, guess, appearance = loopfeat.appearance_loops(ctx, keyframes, K, min_separation=loop_kw.get("min_separation", 3), **akw)
             lc, report = loop_constraints(ctx, keyframes, R, t, K, pairs, guess=guess, **loop_kw)

@@ -10,7 +10,8 @@ from . import dist as D
 from . import engine as E
 
 
-def track_chunked(ctx, depth, rgb, n_chunks, K, group=None, comm=None, cloud=None, optimise=None, loops=None, loop_options=None, **cfg_kw):
+def track_chunked(ctx, depth, rgb, n_chunks, K, group=None, comm=None, cloud=None, optimise=None, loops=None, loop_options=None, segment=None,
+                  **cfg_kw):
     """depth [T, rows, cols] 16-bit, rgb [T, rows, cols, 3] uint8 CUDA tensors of ONE sequence.
     Returns (R [T,3,3], t [T,3], ranges); the per-frame status / covariance are in track_chunked.last = (status, cov).
 
@@ -48,7 +49,7 @@ def track_chunked(ctx, depth, rgb, n_chunks, K, group=None, comm=None, cloud=Non
     L = max(b - a + 1 for a, b in ranges)
     if optimise is not None and world > 1:
         raise ValueError("optimise needs the whole run on one rank (torch.distributed has several)")
-    if cloud is not None or optimise is not None:
+    if cloud is not None or optimise is not None or segment is not None:
         cfg_kw = dict(cfg_kw, keyframe_capacity=L)
     eng = E.Engine(ctx, E.default_config(rows=rows, cols=cols, lanes=lanes, K=K, record_capacity=L, **cfg_kw))
     # Lane-major staging of the whole run, built once and kept alive until the records are read: the engine consumes its inputs
@@ -76,6 +77,12 @@ def track_chunked(ctx, depth, rgb, n_chunks, K, group=None, comm=None, cloud=Non
         except Exception:
             eng.close()
             raise
+    if segment is not None:
+        try:
+            track_chunked.last_labels = _segment(ctx, eng, mine, K, segment)
+        except Exception:
+            eng.close()
+            raise
     if cloud is None:
         eng.close()
         return R, t, ranges
@@ -85,6 +92,21 @@ def track_chunked(ctx, depth, rgb, n_chunks, K, group=None, comm=None, cloud=Non
     finally:
         eng.close()
     return R, t, ranges, pc
+
+
+def _segment(ctx, eng, mine, K, options, batch=16):
+    """segment=dict(k=, min_size=, max_segments=) of track_chunked: the superjut labels of every keyframe this rank's lanes exported
+    (rgbid.segment, on the ring's blocks) -> [(chunk, export number, labels int32 [rows, cols])], left in track_chunked.last_labels"""
+    from . import segment as SG
+    counts = eng.keyframe_counts()
+    pairs = [(lane, s) for lane in range(len(mine)) for s in range(int(counts[lane]))]
+    if not pairs:
+        return []
+    srcs, _ = eng.keyframe_sources(pairs)
+    labels = SG.segment_batches(ctx, srcs, K, eng.cfg.rows, eng.cfg.cols, batch, options.get("max_segments"),
+                                lambda sg, s, res: res[0].cpu().numpy(), k=options.get("k"), min_size=options.get("min_size"))
+    labels = [l for part in labels for l in part]
+    return [(mine[lane], seq, labels[i]) for i, (lane, seq) in enumerate(pairs)]
 
 
 def _optimise(ctx, eng, mine, ranges, rec, R, t, K, optimise, loops, loop_options, steps):
@@ -102,7 +124,11 @@ def _optimise(ctx, eng, mine, ranges, rec, R, t, K, optimise, loops, loop_option
             headers.append((lane, h))
             if loops is not None:
                 keyframes.append(dict(frame=a + int(h["id"]), depthinv=h["depthinv"], colors=h["colors"]))
-    keyframes.sort(key=lambda k: k["frame"])
+    order = sorted(range(len(keyframes)), key=lambda i: keyframes[i]["frame"])
+    if loops == "appearance" and loop_options.get("mask_level") and "blocks" not in loop_options and keyframes:
+        srcs, _ = eng.keyframe_sources([(lane, int(h["seq"])) for lane, h in headers])    # the masks read the ring's blocks on the device
+        loop_options = dict(loop_options, blocks=[srcs[i] for i in order])
+    keyframes = [keyframes[i] for i in order]
     Ro, to, info = PG.optimise_run(ctx, R, t, chunk_records, first, headers, keyframes, K, optimise, loops, **loop_options)
     track_chunked.last_optimise = info
     return Ro, to

@@ -23,6 +23,25 @@ import numpy as np
 import torch
 
 
+def run_options(args):
+    """the optimise / loops / loop_options / segment keywords of sequence.track_chunked that the parsed options ask for"""
+    opt = dict(optimise=args.optimise, loops=args.loops) if args.optimise else {}
+    lo = {}
+    if args.loops == "appearance" and (args.loop_levels != 1 or args.loop_scale != 1.2):
+        lo.update(levels=args.loop_levels, scale=args.loop_scale)
+    if args.loop_proposal == "bow":
+        lo.update(proposal="bow", vocabulary=args.loop_vocabulary)
+        if args.loop_shortlist is not None:
+            lo["shortlist_size"] = args.loop_shortlist
+    if args.loop_mask_level:
+        lo.update(mask_level=args.loop_mask_level, segment_k=args.segment_k, segment_min=args.segment_min, max_segments=args.segment_max)
+    if lo:
+        opt["loop_options"] = lo
+    if args.labels_out:
+        opt["segment"] = dict(k=args.segment_k, min_size=args.segment_min, max_segments=args.segment_max)
+    return opt
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("folder")
@@ -58,6 +77,17 @@ def main():
     ap.add_argument("--loop-vocabulary", default=None, metavar="FILE",
                     help="with --loop-proposal bow: load the vocabulary from FILE if it exists, otherwise train it on this run and save it there")
     ap.add_argument("--loop-shortlist", type=int, default=None, metavar="T", help="with --loop-proposal bow: candidates kept per keyframe (default 8)")
+    ap.add_argument("--loop-mask-level", type=int, default=0, metavar="M",
+                    help="with --loops appearance: match only the keypoints that negentropy mask M (1 .. 3) of their keyframe keeps, which takes "
+                         "the features off large low-information surfaces (DESIGN.md section 16); 0: every keypoint")
+    ap.add_argument("--segment-k", type=float, default=None, metavar="K", help="the segmenter's threshold constant (default 0.6)")
+    ap.add_argument("--segment-min", type=int, default=None, metavar="N", help="the segmenter's smallest segment in points (default 300)")
+    ap.add_argument("--segment-max", type=int, default=None, metavar="S",
+                    help="segments per keyframe the segmenter's tables start with (default 4096; a keyframe with more is segmented again "
+                         "with tables of its count)")
+    ap.add_argument("--labels-out", default="", metavar="DIR",
+                    help="segment every exported keyframe of this rank and write its labels as DIR/labels_<chunk>_<export>.npy (int32 "
+                         "[rows, cols], -1 where the pixel is no point)")
     ap.add_argument("--K", type=float, nargs=4, default=[525.0, 525.0, 319.5, 239.5], help="fx fy cx cy (tools/evaluation.cpp:64-67)")
     args = ap.parse_args()
     if args.voxel is not None and not args.cloud:
@@ -115,14 +145,13 @@ def main():
         ap.error("--loop-proposal / --loop-vocabulary / --loop-shortlist need --loops appearance")
     if (args.loop_vocabulary is not None or args.loop_shortlist is not None) and args.loop_proposal != "bow":
         ap.error("--loop-vocabulary / --loop-shortlist need --loop-proposal bow")
-    opt = dict(optimise=args.optimise, loops=args.loops) if args.optimise else {}
-    if args.loops == "appearance" and (args.loop_levels != 1 or args.loop_scale != 1.2):
-        opt["loop_options"] = dict(levels=args.loop_levels, scale=args.loop_scale)
-    if args.loop_proposal == "bow":
-        bow_opt = dict(proposal="bow", vocabulary=args.loop_vocabulary)
-        if args.loop_shortlist is not None:
-            bow_opt["shortlist_size"] = args.loop_shortlist
-        opt.setdefault("loop_options", {}).update(bow_opt)
+    if args.loop_mask_level and args.loops != "appearance":
+        ap.error("--loop-mask-level needs --loops appearance")
+    if not 0 <= args.loop_mask_level <= 3:
+        ap.error("--loop-mask-level must lie in 0 .. 3")
+    if (args.segment_k is not None or args.segment_min is not None or args.segment_max is not None) and not (args.loop_mask_level or args.labels_out):
+        ap.error("--segment-k / --segment-min / --segment-max need --loop-mask-level or --labels-out")
+    opt = run_options(args)
     if args.cloud:
         R, t, ranges, pc = sequence.track_chunked(ctx, depth, rgb, args.chunks, tuple(args.K), comm=comm, use_graph=0,
                                                   cloud="all" if args.cloud_all else "novel", **opt)
@@ -137,6 +166,11 @@ def main():
                   f"hull {a['hull_query']:.3f} / {a['hull_candidate']:.3f}, ransac {'ok' if a['ransac_ok'] else 'refused'}"
                   + (f", bow score {a['bow_score']:.3f} rank {a['bow_rank']}" if "bow_rank" in a else ""))
     el = time.perf_counter() - t0
+    if args.labels_out:
+        os.makedirs(args.labels_out, exist_ok=True)
+        for chunk, seq, labels in sequence.track_chunked.last_labels:
+            np.save(os.path.join(args.labels_out, f"labels_{chunk:04d}_{seq:04d}.npy"), labels)
+        print(f"rank {rank}: labels of {len(sequence.track_chunked.last_labels)} keyframes -> {args.labels_out}")
     if args.cloud:
         from rgbid import cloud as CL
         path = args.cloud
