@@ -134,9 +134,11 @@ class ChunkCloud:
         return as_numpy(self.points)
 
 
-def chunk_cloud(ctx, eng, lanes, R, t, K, mode, steps):
+def chunk_cloud(ctx, eng, lanes, R, t, K, mode, steps, depthinv=False):
     """points of every keyframe the given engine lanes exported: lanes = [(lane, chunk, first global frame of the chunk)]; R, t = the
-    composed trajectory.  A keyframe's world pose is the trajectory's pose at its global frame (first frame + header id)."""
+    composed trajectory.  A keyframe's world pose is the trajectory's pose at its global frame (first frame + header id).
+    depthinv: also keep each export's inverse-depth plane, a CUDA float32 [rows, cols] copy, as the keyframe's `depthinv` (what
+    rgbid.render.depth_agreement compares a rendering with)."""
     counts = eng.keyframe_counts()
     pairs = [(lane, s) for lane, _, _ in lanes for s in range(int(counts[lane]))]
     for lane, _, _ in lanes:
@@ -156,4 +158,12 @@ def chunk_cloud(ctx, eng, lanes, R, t, K, mode, steps):
         pts, off = cl.build(srcs, K, mode)
     finally:
         cl.close()
+    if depthinv:
+        N = eng.cfg.rows * eng.cfg.cols
+        for kf, src in zip(keyframes, srcs):               # the block: mask u8[N] | colours u8[3N] | inverse depth f32[N] | normals
+            kf["depthinv"] = torch.empty((eng.cfg.rows, eng.cfg.cols), dtype=torch.float32, device=f"cuda:{ctx.device}")
+        ctx.wait_torch_stream()
+        for kf, src in zip(keyframes, srcs):
+            check(ctx.L.rgbid_memcpy_d2d(ctx._h, C.c_void_p(kf["depthinv"].data_ptr()), C.c_void_p(src.block_dev + 4 * N), C.c_size_t(4 * N)))
+        ctx.sync()
     return ChunkCloud(pts, off, keyframes)

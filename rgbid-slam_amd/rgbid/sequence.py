@@ -11,7 +11,7 @@ from . import engine as E
 
 
 def track_chunked(ctx, depth, rgb, n_chunks, K, group=None, comm=None, cloud=None, optimise=None, loops=None, loop_options=None, segment=None,
-                  **cfg_kw):
+                  keyframe_depth=False, **cfg_kw):
     """depth [T, rows, cols] 16-bit, rgb [T, rows, cols, 3] uint8 CUDA tensors of ONE sequence.
     Returns (R [T,3,3], t [T,3], ranges); the per-frame status / covariance are in track_chunked.last = (status, cov).
 
@@ -31,7 +31,11 @@ def track_chunked(ctx, depth, rgb, n_chunks, K, group=None, comm=None, cloud=Non
     without seam-crossing loops run single level).  The returned trajectory (and the cloud) are then the optimised ones; what ran is in
     track_chunked.last_optimise (mode, status, chi2, loops).  It needs the whole run on one rank.  loop_options: keyword arguments of
     rgbid.posegraph.loop_constraints (radius, angle, gate, min_separation) and, with loops = "appearance", of rgbid.loopfeat.appearance_loops
-    (max_keypoints, score_threshold, per_query, and levels / scale of the feature pyramid: one level by default, the reference runs 8 at 1.2)."""
+    (max_keypoints, score_threshold, per_query, and levels / scale of the feature pyramid: one level by default, the reference runs 8 at 1.2).
+
+    keyframe_depth = True (with cloud) keeps every exported keyframe's inverse-depth plane on the device as `depthinv` of the cloud's
+    keyframes, for rgbid.render.depth_agreement; with optimise the cloud placed with the trajectory BEFORE the optimisation is left in
+    track_chunked.last_cloud_before as well, so that the agreement can be compared across it."""
     if cloud not in (None, "novel", "all"):
         raise ValueError(f"cloud must be None, 'novel' or 'all', not {cloud!r}")
     if optimise not in (None, "auto", "multilevel", "single"):
@@ -71,6 +75,7 @@ def track_chunked(ctx, depth, rgb, n_chunks, K, group=None, comm=None, cloud=Non
         allrec = D.gather_records_torch(local, group) if distributed else local[None]
     R, t, st, cov = D.compose_trajectory(allrec, world, n_chunks, ranges)
     track_chunked.last = (st, cov)
+    R0, t0 = R, t
     if optimise is not None:
         try:
             R, t = _optimise(ctx, eng, mine, ranges, allrec[0], R, t, K, optimise, loops, loop_options or {}, L)
@@ -88,7 +93,13 @@ def track_chunked(ctx, depth, rgb, n_chunks, K, group=None, comm=None, cloud=Non
         return R, t, ranges
     from . import cloud as CL
     try:
-        pc = CL.chunk_cloud(ctx, eng, [(i, c, ranges[c][0]) for i, c in enumerate(mine)], R, t, K, cloud, steps=L)
+        lanes_of = [(i, c, ranges[c][0]) for i, c in enumerate(mine)]
+        pc = CL.chunk_cloud(ctx, eng, lanes_of, R, t, K, cloud, steps=L, depthinv=keyframe_depth)
+        if keyframe_depth and optimise is not None:
+            before = CL.chunk_cloud(ctx, eng, lanes_of, R0, t0, K, cloud, steps=L)
+            for kf, after in zip(before.keyframes, pc.keyframes):
+                kf["depthinv"] = after["depthinv"]
+            track_chunked.last_cloud_before = before
     finally:
         eng.close()
     return R, t, ranges, pc

@@ -62,6 +62,17 @@ def main():
                     help="with --cloud and --cloud-min-neighbours: first remove the isolated points, those with fewer than N other points of "
                     "the rank's cloud within R metres (DESIGN.md section 15); --voxel then filters what is left")
     ap.add_argument("--cloud-min-neighbours", type=int, default=None, metavar="N", help="with --cloud-radius: the neighbours a point needs to stay")
+    ap.add_argument("--render", default="", metavar="DIR",
+                    help="with --cloud: render the map that --cloud writes (after --cloud-radius and --voxel) at every exported keyframe's "
+                         "pose on the device and write DIR/view_<i>.png (colour) and DIR/view_<i>_depth.png (16-bit, metres x 5000 as TUM "
+                         "depth files are scaled, 0 where the map is empty); DESIGN.md section 17")
+    ap.add_argument("--render-splat", type=int, default=None, metavar="S",
+                    help="with --render / --render-check: every point paints the (2 S + 1)^2 pixels around its own (0 .. 4, default 1)")
+    ap.add_argument("--render-check", action="store_true",
+                    help="with --cloud: print how well the keyframe cloud, rendered at each keyframe's pose without the keyframe's own points, "
+                         "agrees with the depth that keyframe measured (pixels compared, median and 90th percentile of the difference in "
+                         "metres), per keyframe and over the run; with --optimise before and after the optimisation.  It reads the cloud "
+                         "before --cloud-radius and --voxel: only there does a point still belong to its keyframe")
     ap.add_argument("--optimise", nargs="?", const="auto", default=None, choices=["auto", "multilevel", "single"],
                     help="optimise the trajectory with the pose-graph back-end once over the run (single rank; DESIGN.md section 11)")
     ap.add_argument("--loops", default=None, choices=["auto", "appearance"],
@@ -92,6 +103,18 @@ def main():
     args = ap.parse_args()
     if args.voxel is not None and not args.cloud:
         ap.error("--voxel needs --cloud")
+    if args.render and not args.cloud:
+        ap.error("--render needs --cloud")
+    if args.render_check and not args.cloud:
+        ap.error("--render-check needs --cloud")
+    if args.render_splat is not None and not (args.render or args.render_check):
+        ap.error("--render-splat needs --render or --render-check")
+    if args.render or args.render_check:
+        from rgbid import render as RD
+        try:
+            splat = RD.splat_arg(1 if args.render_splat is None else args.render_splat)
+        except ValueError as e:
+            ap.error(str(e))
     if (args.cloud_radius is None) != (args.cloud_min_neighbours is None):
         ap.error("--cloud-radius and --cloud-min-neighbours need each other")
     if args.cloud_radius is not None:
@@ -152,6 +175,8 @@ def main():
     if (args.segment_k is not None or args.segment_min is not None or args.segment_max is not None) and not (args.loop_mask_level or args.labels_out):
         ap.error("--segment-k / --segment-min / --segment-max need --loop-mask-level or --labels-out")
     opt = run_options(args)
+    if args.render_check:
+        opt["keyframe_depth"] = True
     if args.cloud:
         R, t, ranges, pc = sequence.track_chunked(ctx, depth, rgb, args.chunks, tuple(args.K), comm=comm, use_graph=0,
                                                   cloud="all" if args.cloud_all else "novel", **opt)
@@ -189,6 +214,30 @@ def main():
             vox, plan = VX.voxel_grid(ctx, points, args.voxel, return_plan=True)
             CL.write_ply(path, vox)
             print(f"{said} -> {plan.voxels} voxels of {args.voxel:g} m -> {path}")
+            points = vox
+        if args.render_check:
+            clouds = [("", pc)]
+            if args.optimise:
+                clouds = [(" before the optimisation", sequence.track_chunked.last_cloud_before), (" after the optimisation", pc)]
+            for when, c in clouds:
+                figures = RD.depth_agreement(ctx, c.points, c.offsets, c.keyframes, tuple(args.K), args.rows, args.cols, splat)
+                for kf, f in zip(c.keyframes, figures):
+                    print(f"rank {rank}: render check{when}: keyframe at frame {kf['frame']}: {f['pixels']} pixels, "
+                          f"median {f['median']:.6f} m, 90 % {f['p90']:.6f} m")
+                run = RD.agreement_summary(figures)
+                print(f"rank {rank}: render check{when}: {len(figures)} keyframes, {run['pixels']} pixels, median of medians {run['median']:.6f} m, "
+                      f"largest 90 % {run['p90']:.6f} m")
+        if args.render:
+            os.makedirs(args.render, exist_ok=True)
+            for a in range(0, len(pc.keyframes), RD.VIEW_CHUNK):
+                kfs = pc.keyframes[a:a + RD.VIEW_CHUNK]
+                views = RD.render_views(ctx, points, np.stack([k["R"] for k in kfs]), np.stack([k["t"] for k in kfs]), tuple(args.K), args.rows,
+                                        args.cols, splat)
+                for j in range(len(kfs)):
+                    name = f"view_{a + j:04d}" if world == 1 else f"view_rank{rank}_{a + j:04d}"
+                    tum.write_png(os.path.join(args.render, name + ".png"), views["colour"][j].cpu().numpy())
+                    tum.write_png(os.path.join(args.render, name + "_depth.png"), RD.depth_png(views["depth"][j]))
+            print(f"rank {rank}: {len(pc.keyframes)} views of {points.shape[0]} records, splat {splat} -> {args.render}")
     if comm is not None:
         comm.close()
     if rank == 0:
