@@ -281,6 +281,10 @@ __device__ __forceinline__ float func_weights_nu(const SM& S, float bias, float 
   double t[4];
   float af[4] = {(float)a[0], (float)a[1], (float)a[2], 0.f};
   block_sum4(af, t, sm);
+  // No valid sample at all (a keyframe pair whose second inverse-depth map is empty): the reference's sums are exactly 0 and its mean is 0 / 0 = NaN, which
+  // fails every comparison of the bisection and leaves nu = 9.75.  The register path's sums cancel only to a few ulp there (sum over all slots minus
+  // n_invalid times the slot's value, the pair sharing one logarithm), and residue / 0 = +-inf walked the bisection to some other nu.
+  if (t[2] == 0.0) return qnan();
   return ((float)t[0] - (float)t[1]) / (float)t[2];
 }
 

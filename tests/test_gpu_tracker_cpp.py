@@ -253,7 +253,8 @@ def test_keyframe_align_batched_partials_fit_every_pair_count_of_a_wide_geometry
 def test_keyframe_align_batched_many_pairs_one_wave_solve():
     """More pairs than compute units: the per-pair reduce-and-solve kernel runs as ONE wave per pair (kfalign.hip k_kfa_solve<64>: four slices of the fixed-order
     reduction per thread, the same doubles).  272 pairs carrying 4 distinct ones: duplicates agree to the last bit, and every pair agrees with its 4-pair run
-    (256-thread workgroups; another launch plan of the normal equations) inside the tolerance (3e-5 here at 160x120, where a flipped nu bisection step moves a pose by ~1e-5; 1e-4 the bar)."""
+    (256-thread workgroups; another launch plan of the normal equations) inside the tolerance (3e-5 here at 160x120, where a flipped nu bisection step moves a pose by ~1e-5; 1e-4 the bar),
+    and with orc_keyframe_align inside the bar (1e-4 rad, 1e-4 m, 1e-2 on the covariance)."""
     from rgbid import device, kfalign
     rows, cols = 120, 160
     K0 = (131.25, 131.25, 79.875, 59.875)
@@ -279,6 +280,14 @@ def test_keyframe_align_batched_many_pairs_one_wave_solve():
         assert np.array_equal(R[l], R[l % n]) and np.array_equal(t[l], t[l % n]) and np.array_equal(cov[l], cov[l % n]), l
     for l in range(n):
         assert rot_angle(R[l], Rf[l]) < 3e-5 and np.linalg.norm(t[l] - tf[l]) < 3e-5, (l, rot_angle(R[l], Rf[l]), np.linalg.norm(t[l] - tf[l]))
+    # and the one-wave solve is held to the oracle itself, not only to the other solve kernel
+    for l in range(n):
+        Ro, to, covo = O.keyframe_align(iDa[l], ga[l], iDb[l], gb[l], K0)
+        sc = np.sqrt(np.outer(np.diag(covo), np.diag(covo)))
+        dev = (rot_angle(R[l], Ro), np.linalg.norm(t[l] - to), (np.abs(cov[l] - covo) / sc).max())
+        print(f"pair {l} of 272 against the oracle: {dev[0]:.2e} rad, {dev[1]:.2e} m, {dev[2]:.2e} covariance")
+        assert np.isfinite(R[l]).all() and np.isfinite(t[l]).all() and np.isfinite(cov[l]).all()
+        assert dev[0] < 1e-4 and dev[1] < 1e-4 and dev[2] < 1e-2, (l, dev)
 
 
 def test_cli_eval_harness_on_tum_layout(tmp_path):
