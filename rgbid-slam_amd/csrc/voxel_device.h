@@ -1,4 +1,4 @@
-// voxel_device.h -- what the map filters over rgbid_cloud_point records share (kernels_voxel.hip, kernels_outlier.hip).  Device half: the
+// voxel_device.h -- what the map filters over rgbid_cloud_point records share (kernels_voxel.hip, kernels_outlier.hip, kernels_consist.hip).  Device half: the
 // box of the finite points, the float32 grid and its cell keys, the stable LSD radix sort of (key, index) pairs and the stable flag
 // compaction (the wave and block primitives they stand on are wave_device.h's).  Host half: SortWorkspace, the buffers of one filter
 // handle and the launches over them, and the argument checks every plan / emit makes.
@@ -354,21 +354,26 @@ struct SortWorkspace {
   unsigned* slots = nullptr;                          // [SLOTS] box, finite count, two compaction totals
   unsigned* slots_host = nullptr;                     // pinned
 
+  // what count_scan / write / read_slots need, for a handle that compacts up to max_items items and sorts nothing
+  int alloc_compaction(Buffers& buf, unsigned long long max_items) {
+    cap = max_items;
+    run_tiles = (unsigned)((max_items + RUN_TILE - 1) / RUN_TILE);
+    int r = buf.alloc(&bc, sizeof(unsigned) * run_tiles);
+    if (!r) r = buf.alloc(&slots, sizeof(unsigned) * SLOTS);
+    if (!r) r = buf.alloc_host(&slots_host, sizeof(unsigned) * SLOTS);
+    return r;
+  }
+
   int alloc(Buffers& buf, unsigned long long max_points) {
-    cap = max_points;
     sort_tiles = (unsigned)((max_points + SORT_TILE - 1) / SORT_TILE);
-    run_tiles = (unsigned)((max_points + RUN_TILE - 1) / RUN_TILE);
     const size_t c = (size_t)max_points;
-    int r = RGBID_OK;
+    int r = alloc_compaction(buf, max_points);
     for (int i = 0; i < 2 && !r; ++i) r = buf.alloc(&keys[i], sizeof(unsigned long long) * c);
     for (int i = 0; i < 2 && !r; ++i) r = buf.alloc(&idx[i], sizeof(unsigned) * (c + 1));
     if (!r) r = buf.alloc(&hist, sizeof(unsigned) * RADIX * (size_t)sort_tiles);
     if (!r) r = buf.alloc(&dtotal, sizeof(unsigned) * RADIX);
     if (!r) r = buf.alloc(&box_part, sizeof(float) * 6 * VOX_MAX_GRID);
     if (!r) r = buf.alloc(&box_cnt, sizeof(unsigned) * VOX_MAX_GRID);
-    if (!r) r = buf.alloc(&bc, sizeof(unsigned) * run_tiles);
-    if (!r) r = buf.alloc(&slots, sizeof(unsigned) * SLOTS);
-    if (!r) r = buf.alloc_host(&slots_host, sizeof(unsigned) * SLOTS);
     return r;
   }
 

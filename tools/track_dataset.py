@@ -62,6 +62,17 @@ def main():
                     help="with --cloud and --cloud-min-neighbours: first remove the isolated points, those with fewer than N other points of "
                     "the rank's cloud within R metres (DESIGN.md section 15); --voxel then filters what is left")
     ap.add_argument("--cloud-min-neighbours", type=int, default=None, metavar="N", help="with --cloud-radius: the neighbours a point needs to stay")
+    ap.add_argument("--cloud-consistency", type=float, default=None, metavar="TOL_REL",
+                    help="with --cloud: first remove the points that other keyframes saw through: a keyframe contradicts a point when, "
+                         "along its own ray, it measured only depths more than TOL_REL x depth (+ --cloud-consistency-abs) behind it "
+                         "(DESIGN.md section 18); --cloud-radius and --voxel then filter what is left; with --optimise the optimised poses are used")
+    ap.add_argument("--cloud-consistency-abs", type=float, default=None, metavar="M", help="with --cloud-consistency: metres added to the tolerance (default 0)")
+    ap.add_argument("--cloud-consistency-window", type=int, default=None, metavar="W",
+                    help="with --cloud-consistency: a keyframe looks at the (2 W + 1)^2 pixels around the point's projection (0 .. 2, default 1)")
+    ap.add_argument("--cloud-min-support", type=int, default=None, metavar="S",
+                    help="with --cloud-consistency: other keyframes that must have measured the point's depth for it to stay (default 0)")
+    ap.add_argument("--cloud-max-conflicts", type=int, default=None, metavar="C",
+                    help="with --cloud-consistency: contradicting keyframes a point may have and stay (default 0)")
     ap.add_argument("--render", default="", metavar="DIR",
                     help="with --cloud: render the map that --cloud writes (after --cloud-radius and --voxel) at every exported keyframe's "
                          "pose on the device and write DIR/view_<i>.png (colour) and DIR/view_<i>_depth.png (16-bit, metres x 5000 as TUM "
@@ -113,6 +124,19 @@ def main():
         from rgbid import render as RD
         try:
             splat = RD.splat_arg(1 if args.render_splat is None else args.render_splat)
+        except ValueError as e:
+            ap.error(str(e))
+    if args.cloud_consistency is not None and not args.cloud:
+        ap.error("--cloud-consistency needs --cloud")
+    if args.cloud_consistency is None and not (args.cloud_consistency_abs is None and args.cloud_consistency_window is None
+                                               and args.cloud_min_support is None and args.cloud_max_conflicts is None):
+        ap.error("--cloud-consistency-abs / --cloud-consistency-window / --cloud-min-support / --cloud-max-conflicts need --cloud-consistency")
+    if args.cloud_consistency is not None:
+        from rgbid import consist as CF
+        try:
+            consist = dict(zip(("tol_rel", "tol_abs"), CF.tolerances(args.cloud_consistency, args.cloud_consistency_abs or 0.0)))
+            consist["window"] = CF.window_arg(1 if args.cloud_consistency_window is None else args.cloud_consistency_window)
+            consist.update(zip(("min_support", "max_conflicts"), CF.vote_args(args.cloud_min_support or 0, args.cloud_max_conflicts or 0)))
         except ValueError as e:
             ap.error(str(e))
     if (args.cloud_radius is None) != (args.cloud_min_neighbours is None):
@@ -175,7 +199,7 @@ def main():
     if (args.segment_k is not None or args.segment_min is not None or args.segment_max is not None) and not (args.loop_mask_level or args.labels_out):
         ap.error("--segment-k / --segment-min / --segment-max need --loop-mask-level or --labels-out")
     opt = run_options(args)
-    if args.render_check:
+    if args.render_check or args.cloud_consistency is not None:
         opt["keyframe_depth"] = True
     if args.cloud:
         R, t, ranges, pc = sequence.track_chunked(ctx, depth, rgb, args.chunks, tuple(args.K), comm=comm, use_graph=0,
@@ -203,9 +227,18 @@ def main():
             root, ext = os.path.splitext(path)
             path = f"{root}.rank{rank}{ext}"
         points, said = pc.points, f"rank {rank}: {len(pc)} points of {len(pc.keyframes)} keyframes"
+        consistent = None
+        if args.cloud_consistency is not None and pc.keyframes:
+            points, kept_offsets, cp = CF.consistency_filter(ctx, points, pc.offsets, [k["depthinv"] for k in pc.keyframes],
+                                                             np.stack([k["R"] for k in pc.keyframes]), np.stack([k["t"] for k in pc.keyframes]),
+                                                             tuple(args.K), args.rows, args.cols, return_offsets=True, return_plan=True, **consist)
+            consistent = (points, kept_offsets)
+            said += (f" -> {cp.kept} kept, {cp.n - cp.kept} removed, {cp.contradicted} contradicted (tolerance {consist['tol_rel']:g} x depth"
+                     f" + {consist['tol_abs']:g} m, window {consist['window']}, support >= {consist['min_support']}, conflicts <= {consist['max_conflicts']})")
+        after_consistency = points.shape[0]
         if args.cloud_radius is not None:
             points = OL.radius_filter(ctx, points, args.cloud_radius, args.cloud_min_neighbours)
-            said += f" -> {points.shape[0]} kept of {len(pc)} ({args.cloud_min_neighbours} within {args.cloud_radius:g} m)"
+            said += f" -> {points.shape[0]} kept of {after_consistency} ({args.cloud_min_neighbours} within {args.cloud_radius:g} m)"
         if args.voxel is None:
             CL.write_ply(path, points)
             print(f"{said} -> {path}")
@@ -219,6 +252,8 @@ def main():
             clouds = [("", pc)]
             if args.optimise:
                 clouds = [(" before the optimisation", sequence.track_chunked.last_cloud_before), (" after the optimisation", pc)]
+            if consistent is not None:
+                clouds.append((" after the consistency filter", CL.ChunkCloud(consistent[0], consistent[1], pc.keyframes)))
             for when, c in clouds:
                 figures = RD.depth_agreement(ctx, c.points, c.offsets, c.keyframes, tuple(args.K), args.rows, args.cols, splat)
                 for kf, f in zip(c.keyframes, figures):
