@@ -2,6 +2,7 @@
 against (tests/consist_mirror.py) against the plain scalar loop of the contract; scenes whose counts are derived by hand; the Python
 argument checks one by one; the header as C99; the library's exports; refusals that need no device; the command line's option errors."""
 import ctypes
+import functools
 import os
 import re
 import shutil
@@ -69,6 +70,41 @@ def records_near_surface(rng, n):
         for c, v in (("x", x * s), ("y", y * s), ("z", z * s)):
             p[c] = np.where(on & np.isfinite(p[c]), v.astype(F), p[c])
     return p
+
+
+HALF = 524288                           # one full grid of the strided kernels and 256 tiles of the keep compaction (test_cpu_segment.py
+LARGE_N = 2 * HALF + 5003               # test_sizes_lie_on_the_intended_side_of_the_thresholds): three trips, the last one ragged
+LARGE_GATE = dict(tol_rel=0.02, tol_abs=0.001, window=1, z_min=0.3, z_max=5.0)
+
+
+@functools.lru_cache(maxsize=None)
+def large_cloud():
+    """LARGE_N records around the surface, 1 % of them with y = -inf, and VIEW_CHUNK + 1 cameras with their planes; tests/test_gpu_consist.py
+    filters prefixes of it against the first three views and against all of them"""
+    rng = np.random.default_rng(500)
+    R, t = cameras(rng, CF.VIEW_CHUNK + 1)
+    planes = surface_planes(rng, R, t)
+    p = records_near_surface(rng, LARGE_N)
+    p["y"][rng.random(len(p)) < 0.01] = -np.inf
+    return dict(p=p, R=R, t=t, planes=planes)
+
+
+def assert_every_trip_has_work(sup, con, keep, pairs, n):
+    """a trip of the stride that did nothing must not pass: the records of each trip include supported, contradicted and removed ones"""
+    assert keep.sum() > n // 2 and (sup > 0).sum() > n // 8 and (con > 0).sum() > n // 16 and pairs > n // 2
+    for lo in range(0, n, HALF):
+        hi = min(lo + HALF, n)
+        few = min(hi - lo, 5003) // 50                     # 100 of each kind, unless the trip has fewer than 5 003 records
+        assert (sup[lo:hi] > 0).sum() >= few and (con[lo:hi] > 0).sum() >= few and (~keep[lo:hi]).sum() >= few, (lo, hi)
+
+
+def test_large_cloud_has_work_on_every_trip():
+    sc = large_cloud()
+    counts, keep, kept, pairs = CM.consist_numpy(sc["p"], None, sc["planes"][:3], sc["R"][:3], sc["t"][:3], K, **LARGE_GATE)
+    sup, con = unpack(counts)
+    print(f"{LARGE_N} records, 3 views: {int(keep.sum())} kept, {int((sup > 0).sum())} supported, {int((con > 0).sum())} contradicted, {pairs} pairs")
+    assert_every_trip_has_work(sup, con, keep, pairs, LARGE_N)
+    assert len(kept) == keep.sum() < LARGE_N
 
 
 def unpack(counts):

@@ -1,7 +1,9 @@
 """CPU tests of the keyframe segmenter (include/rgbid_segment.h): the two restatements of tests/segment_mirror.py (the sequential loop
 and the reservation rounds) agree on every input the GPU tests use, for every window; the closed form of the mask rule equals the
 replay of the reference's loops; the header is C; the library exports what it declares; the bin table agrees with numpy.  The inputs
-(`scenes`) are export blocks built from synthetic depth and normals, shared with tests/test_gpu_segment.py."""
+(`scenes`) are export blocks built from synthetic depth and normals, shared with tests/test_gpu_segment.py.  `large_scenes` are the inputs
+of tests/test_gpu_segment_large.py at 120 x 160 and 480 x 640: what the mirror alone says about them, and on which side of the device's
+launch thresholds (csrc/voxel_device.h) the sizes of the large GPU tests lie."""
 import ctypes
 import functools
 import os
@@ -18,8 +20,10 @@ from tests.test_cpu_cloud import make_block
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 TOL = 2e-5          # negentropy: at most 128 terms of at most 0.37 each, logf good to about 2 ULP, the divisor at least ln 2
-SIZES = {"a": (37, 53), "b": (48, 64)}     # both ragged against 64-lane tiles
-K_OF = {"a": (45.0, 45.5, 26.0, 18.0), "b": (52.5, 52.5, 31.5, 23.5)}
+SIZES = {"a": (37, 53), "b": (48, 64),     # both ragged against 64-lane tiles
+         "c": (120, 160), "f": (480, 640)}  # the engine's export size and the full frame: large_scenes() only
+K_OF = {"a": (45.0, 45.5, 26.0, 18.0), "b": (52.5, 52.5, 31.5, 23.5),
+        "c": (131.25, 131.25, 79.875, 59.875), "f": (525.0, 525.0, 319.5, 239.5)}
 
 
 def _lib_handle():
@@ -114,11 +118,65 @@ def scenes():
     return out
 
 
+def _faceted(rows, cols, cell, seed):
+    """cells of cell x cell pixels, each a facet of its own normal unit((0.5 g1, 0.5 g2, -1)) at its own depth 1.5 + 0.05 g3; the noise on
+    the normals is 0.03 times a factor of the facet's own (0.25 .. 4), so that the segments' entropies spread over the thresholds"""
+    r = np.random.default_rng(seed)
+    gy, gx = -(-rows // cell), -(-cols // cell)
+    g = r.standard_normal((gy, gx, 3))
+    amp = 0.03 * 2.0 ** r.uniform(-2.0, 2.0, (gy, gx))
+    cy, cx = (np.arange(rows) // cell)[:, None], (np.arange(cols) // cell)[None, :]
+    G, A = g[cy, cx], amp[cy, cx]
+    depth = (1.5 + 0.05 * G[..., 2] + 0.002 * r.standard_normal((rows, cols))).astype(F)
+    n = _unit(np.stack([0.5 * G[..., 0], 0.5 * G[..., 1], -np.ones((rows, cols))], -1))
+    return depth, _unit(n + (A[..., None] * r.standard_normal((rows, cols, 3))).astype(F))
+
+
+def _holes(seed):
+    """15 % of the depths and 10 % of the normals' x NaN, and one NaN rectangle of a quarter by a third of the image"""
+    def edit(depth, n):
+        r = np.random.default_rng(seed)
+        rows, cols = depth.shape
+        depth[r.random(depth.shape) < 0.15] = np.nan
+        n[r.random(depth.shape) < 0.1, 0] = np.nan
+        depth[rows // 4:rows // 4 + rows // 4, cols // 8:cols // 8 + cols // 3] = np.nan
+    return edit
+
+
+FACETED = ("facets16", "facets5", "facets11_holes", "facets24_holes_f")
+
+
 @functools.lru_cache(maxsize=None)
-def mirror(name):
-    s = scenes()[name]
+def large_scenes():
+    """name -> dict(size key, block, kth, min_size) at the sizes past which the device's launches change shape (test_sizes_lie_on_the_
+    intended_side_of_the_thresholds).  Not part of scenes(): the proofs over every window would take minutes here."""
+    out = {}
+
+    def add(name, key, depth, n, kth, min_size, edit=None):
+        depth, n = depth.copy(), n.copy()
+        if edit:
+            edit(depth, n)
+        out[name] = dict(key=key, block=_block(depth, n), kth=kth, min_size=min_size)
+    rc, cc = SIZES["c"]; rf, cf = SIZES["f"]
+    add("facets16", "c", *_faceted(rc, cc, 16, 41), kth=0.05, min_size=20)
+    add("facets5", "c", *_faceted(rc, cc, 5, 42), kth=0.05, min_size=8)                 # hundreds of segments
+    add("facets11_holes", "c", *_faceted(rc, cc, 11, 43), kth=0.05, min_size=20, edit=_holes(6))
+    add("plane_c", "c", *_plane(rc, cc), kth=0.6, min_size=300)                          # every weight ties: about one round per point
+    add("k_zero_c", "c", *_noisy(rc, cc, 44), kth=0.0, min_size=1)                      # every point its own segment: past DEFAULT_MAX_SEGMENTS
+    add("facets24_holes_f", "f", *_faceted(rf, cf, 24, 45), kth=0.05, min_size=50, edit=_holes(7))
+    return out
+
+
+BATCH_SCENES = ("facets16", "facets5", "facets11_holes", "plane_c")     # the members of the 13- and 14-keyframe batches, cycled
+BATCH_PARAMS = dict(kth=0.05, min_size=20)                               # one call has one set of parameters
+
+
+@functools.lru_cache(maxsize=None)
+def mirror(name, kth=None, min_size=None):
+    """the mirror of a scene with its own parameters, or with the given ones"""
+    s = scenes()[name] if name in scenes() else large_scenes()[name]
     rows, cols = SIZES[s["key"]]
-    return SM.run(s["block"], rows, cols, K_OF[s["key"]], s["kth"], s["min_size"])
+    return SM.run(s["block"], rows, cols, K_OF[s["key"]], s["kth"] if kth is None else kth, s["min_size"] if min_size is None else min_size)
 
 
 def near_threshold(neg, valid):
@@ -175,6 +233,62 @@ def test_mask_comparisons_are_decided_by_the_mirror_alone(name):
     for d in (-TOL, TOL):
         moved = np.where(m["valid"].reshape(neg.shape), neg + F(d), neg).astype(F)
         assert np.array_equal(SM.mask_levels(moved), m["levels"])
+
+
+def _levels_are_decided(m):
+    neg = m["negentropy"]
+    assert near_threshold(neg, m["valid"]).mean() <= 0.01      # a condition on the input, not a tolerance: change the scene if it breaks
+    for d in (-TOL, TOL):
+        moved = np.where(m["valid"].reshape(neg.shape), neg + F(d), neg).astype(F)
+        assert np.array_equal(SM.mask_levels(moved), m["levels"])
+
+
+@pytest.mark.parametrize("name", sorted(large_scenes()))
+def test_large_scenes_have_what_they_are_for(name):
+    """from the mirror alone: the faceted scenes fill the segment tables, the plane is one segment of tied weights, k = 0 leaves more
+    segments than the tables start with; and the levels are decided as in the small scenes"""
+    m = mirror(name)
+    rows, cols = SIZES[large_scenes()[name]["key"]]
+    print(f"{name}: {m['count']} segments of {m['sizes'].min()} .. {m['sizes'].max()} points, {m['edges']} edges, levels {m['levels'].tolist()}")
+    if name in FACETED:
+        assert m["count"] >= 60 and m["sizes"].min() >= large_scenes()[name]["min_size"]
+        assert len(np.unique(m["negentropy"][m["labels"] >= 0])) >= 30          # the segments' entropies differ
+    elif name == "plane_c":
+        assert m["count"] == 1 and m["sizes"][0] == rows * cols
+    else:
+        from rgbid import segment as SG
+        assert name == "k_zero_c" and m["count"] > SG.DEFAULT_MAX_SEGMENTS == 4096
+    if "holes" in name:
+        assert 0.3 * 4 * rows * cols < m["edges"] < 0.6 * 4 * rows * cols and not m["valid"].all()
+    else:
+        assert m["edges"] == 4 * rows * cols - 3 * (rows + cols) + 2           # every pixel a point, no edge dropped
+    _levels_are_decided(m)
+    if name in BATCH_SCENES:
+        b = mirror(name, **BATCH_PARAMS)
+        assert b["count"] == 1 if name == "plane_c" else b["count"] >= 60
+        _levels_are_decided(b)
+
+
+def test_sizes_lie_on_the_intended_side_of_the_thresholds():
+    """the sizes of the large GPU tests (tests/test_gpu_segment.py, tests/test_gpu_consist.py) against the constants of csrc/voxel_device.h:
+    whoever retunes a constant learns here that those tests no longer reach the carried scans and the second trip of the strides"""
+    txt = open(os.path.join(ROOT, "rgbid-slam_amd", "csrc", "voxel_device.h")).read()
+    VT, SORT_IPT, RUN_IPT, MAX_GRID = (int(re.search(rf"constexpr int {n} = (\d+);", txt).group(1)) for n in ("VT", "SORT_IPT", "RUN_IPT", "VOX_MAX_GRID"))
+    assert re.search(r"constexpr int SORT_TILE = VT \* SORT_IPT;", txt) and re.search(r"constexpr int RUN_TILE = VT \* RUN_IPT;", txt)
+    assert len(re.findall(r"for \(unsigned base = 0; base < \w+; base \+= VT\)", txt)) == 2     # k_vox_scan_digits, k_vox_scan1: VT tiles per trip
+
+    def tiles(items, per):
+        return -(-items // per)
+    P = SIZES["c"][0] * SIZES["c"][1]
+    assert P == 19200 and SIZES["f"][0] * SIZES["f"][1] == 307200
+    assert tiles(13 * 4 * P, VT * SORT_IPT) <= VT           # 244 sort tiles: one trip of k_vox_scan_digits
+    assert tiles(14 * 4 * P, VT * SORT_IPT) > VT            # 263: the carry, 64-bit keys
+    assert tiles(4 * 307200, VT * SORT_IPT) > VT            # 300: the carry, 32-bit keys
+    assert P > 8 * VT                                       # k_seg_label carries over more than 8 tiles
+    n = 524288
+    assert tiles(n, VT) == MAX_GRID and tiles(n, VT * RUN_IPT) == VT          # exactly one grid, exactly one trip of k_vox_scan1
+    assert tiles(n + 1, VT) == MAX_GRID + 1 and tiles(n + 1, VT * RUN_IPT) == VT + 1
+    assert tiles(2 * n + 5003, MAX_GRID * VT) == 3          # three trips, the last one ragged
 
 
 def test_mask_rule_closed_form_equals_the_replay():

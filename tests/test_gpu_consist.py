@@ -1,6 +1,7 @@
 """GPU tests of the consistency filter (include/rgbid_consist.h, csrc/kernels_consist.hip, rgbid.consist): counts, kept count, statistics
 and the emitted bytes against the numpy restatement (tests/consist_mirror.py) on a random cloud with the adversaries of the contract and
-planes with every kind of hole, the tolerance and the gates to the ulp, windows clipped at the image border, record order, the position
+planes with every kind of hole, the same at 524 288, 524 289 and 1 053 579 records (one grid and 256 compaction tiles, one more, three
+trips of the strided kernels) with one handle that also filters small clouds in between, the tolerance and the gates to the ulp, windows clipped at the image border, record order, the position
 of a view in the batch, owner ranges, the refusals, the empty cloud, the cloud of a tracked run, and the options of
 tools/track_dataset.py."""
 import ctypes as C
@@ -18,7 +19,8 @@ from rgbid import consist as CF
 from rgbid import render as RD
 from rgbid import sequence, synth, tum
 from tests import consist_mirror as CM
-from tests.test_cpu_consist import COLS, K, ROWS, cameras, records_near_surface, surface_planes, unpack
+from tests.test_cpu_consist import (COLS, HALF, K, LARGE_GATE, LARGE_N, ROWS, assert_every_trip_has_work, cameras, large_cloud, records_near_surface,
+                                    surface_planes, unpack)
 from tests.test_gpu_cloud import K_SMALL, write_tum_folder
 
 pytestmark = pytest.mark.gpu
@@ -100,6 +102,65 @@ def test_consist_either_side_of_the_view_chunk(ctx):
         o = off[:nv + 1].copy(); o[-1] = n
         check(ctx, sc["p"], o, sc["planes"][:nv], sc["R"][:nv], sc["t"][:nv], dev=sc["dev"], dplanes=sc["dplanes"][:nv], tol_rel=0.02, tol_abs=0.001,
               window=1, min_support=1, max_conflicts=1, **GATE)
+
+
+# ---- past one grid of the strided kernels and one trip of the scan of the tile counts -------------------------------------------------
+@pytest.fixture(scope="module")
+def large(ctx):
+    """large_cloud() on the device and the one handle every large case and the small clouds between them go through"""
+    sc = dict(large_cloud())
+    sc.update(dev=upload(sc["p"]), dplanes=torch.from_numpy(sc["planes"]).cuda(), cf=CF.ConsistencyFilter(ctx, LARGE_N, CF.VIEW_CHUNK + 1))
+    yield sc
+    sc["cf"].close()
+
+
+def check_prefix(ctx, sc, n, V, offsets=None, **kw):
+    """the first n records of the large cloud against its first V views, through the shared handle"""
+    return check(ctx, sc["p"][:n], offsets, sc["planes"][:V], sc["R"][:V], sc["t"][:V], cf=sc["cf"], dev=sc["dev"][:n], dplanes=sc["dplanes"][:V],
+                 **dict(LARGE_GATE, **kw))
+
+
+@pytest.mark.parametrize("n", [HALF, HALF + 1, LARGE_N])
+def test_consist_either_side_of_one_grid(ctx, large, n):
+    """524 288 records: every thread makes one trip and k_vox_scan1 one; one record more: a second trip of one thread, a 257th tile;
+    1 053 579: three trips, the lanes of the last wave make different numbers of them"""
+    sup, con, keep, plan = check_prefix(ctx, large, n, 3)
+    print(f"{n} records, 3 views: {plan.kept} kept, {int((sup > 0).sum())} supported, {plan.contradicted} contradicted, {plan.pairs} pairs")
+    assert_every_trip_has_work(sup, con, keep, plan.pairs, n)
+
+
+def test_consist_owner_range_across_the_second_trip(ctx, large):
+    """the second view owns records 524 000 .. 524 599: the owner test on the first trip and on the second"""
+    off = np.array([0, 524000, 524600, LARGE_N], np.uint64)
+    free_sup, free_con, _, free = check_prefix(ctx, large, LARGE_N, 3)
+    sup, con, keep, plan = check_prefix(ctx, large, LARGE_N, 3, off)
+    assert_every_trip_has_work(sup, con, keep, plan.pairs, LARGE_N)
+    own = slice(524000, 524600)
+    assert plan.pairs < free.pairs and (sup <= free_sup).all() and (con <= free_con).all()
+    assert (sup[own][:288] < free_sup[own][:288]).any() and (sup[own][288:] < free_sup[own][288:]).any()       # either side of record 524 288
+
+
+def test_consist_one_handle_large_and_small_in_turn(ctx, large):
+    """large, small, large in chunks of views, small in chunks: each equals its mirror, so no count, keep flag or tile offset of a larger
+    plan is left in a smaller one.  The chunked large plan runs the memset of the counts, the integer adds of two chunks and the stride
+    of k_consist_mark past one grid, with owner ranges"""
+    V = CF.VIEW_CHUNK + 1
+    vote = dict(min_support=1, max_conflicts=1)
+
+    def small(views):
+        sc = scene(3 if views == 3 else 19)               # 5 003 records; the handle holds VIEW_CHUNK + 1 views
+        return check(ctx, sc["p"], None, sc["planes"][:views], sc["R"][:views], sc["t"][:views], cf=large["cf"], dev=sc["dev"],
+                     dplanes=sc["dplanes"][:views], tol_rel=0.02, tol_abs=0.001, window=1, **GATE, **(vote if views > 3 else {}))
+    check_prefix(ctx, large, LARGE_N, 3)
+    sup, con, _, plan = small(3)
+    assert (sup > 0).sum() > 500 and (con > 0).sum() > 100 and 0 < plan.kept < plan.n
+    n = HALF + 5003
+    off = (np.arange(V + 1, dtype=np.uint64) * np.uint64(n) // np.uint64(V)).astype(np.uint64)
+    sup, con, keep, plan = check_prefix(ctx, large, n, V, off, **vote)
+    print(f"{n} records, {V} views: {plan.kept} kept, {int((sup > 0).sum())} supported, {plan.contradicted} contradicted, {plan.pairs} pairs")
+    assert sup.max() > 3 and (con[HALF:] > 1).any() and (~keep[HALF:]).sum() > 100 and keep[HALF:].sum() > 100
+    sup, con, _, plan = small(V)
+    assert (sup > 0).sum() > 500 and (con > 0).sum() > 100 and 0 < plan.kept < plan.n
 
 
 # ---- the tolerance and the gates to the ulp -----------------------------------------------------------------------------------------

@@ -21,7 +21,7 @@ def upload(block):
 
 @pytest.fixture(scope="module")
 def segmenters(ctx):
-    made = {key: SG.Segmenter(ctx, r, c, 5, r * c) for key, (r, c) in SIZES.items()}
+    made = {key: SG.Segmenter(ctx, *SIZES[key], 5, SIZES[key][0] * SIZES[key][1]) for key in ("a", "b")}   # the sizes of scenes()
     yield made
     for s in made.values():
         s.close()
@@ -31,9 +31,10 @@ def host(out):
     return [t.cpu().numpy() for t in out]
 
 
-def assert_equals_mirror(name, got, member=0):
-    """one keyframe of a device result against the mirror of scene `name` -> the share of pixels a mask comparison skipped"""
-    m = mirror(name)
+def assert_equals_mirror(name, got, member=0, m=None):
+    """one keyframe of a device result against the mirror of scene `name` (or the mirror dict `m` of it, when the call did not use the
+    scene's own parameters) -> the pixels a mask comparison skipped"""
+    m = mirror(name) if m is None else m
     labels, counts, sizes, hist, neg, lev = [a[member] for a in got]
     c = m["count"]
     print(f"{name}: segments {counts} / {c}, edges {m['edges']}, levels {lev.tolist()} / {m['levels'].tolist()}")

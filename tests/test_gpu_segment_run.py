@@ -74,7 +74,7 @@ def test_tables_grow_to_the_reported_count(ctx):
             assert np.array_equal(r[0][k], m["labels"]) and r[1][k] == m["count"] and np.array_equal(r[2][k], m["sizes"])
 
 
-@pytest.mark.parametrize("args", [(37, 53, 1, 7), (48, 64, 5, 48 * 64), (120, 160, 3, 4096)])
+@pytest.mark.parametrize("args", [(37, 53, 1, 7), (48, 64, 5, 48 * 64), (120, 160, 3, 4096), (120, 160, 14, 4096)])
 def test_device_bytes_are_the_sizing(ctx, args):
     sg = SG.Segmenter(ctx, *args)
     try:
