@@ -134,11 +134,13 @@ class ChunkCloud:
         return as_numpy(self.points)
 
 
-def chunk_cloud(ctx, eng, lanes, R, t, K, mode, steps, depthinv=False):
+def chunk_cloud(ctx, eng, lanes, R, t, K, mode, steps, depthinv=False, colour=False):
     """points of every keyframe the given engine lanes exported: lanes = [(lane, chunk, first global frame of the chunk)]; R, t = the
     composed trajectory.  A keyframe's world pose is the trajectory's pose at its global frame (first frame + header id).
     depthinv: also keep each export's inverse-depth plane, a CUDA float32 [rows, cols] copy, as the keyframe's `depthinv` (what
-    rgbid.render.depth_agreement compares a rendering with)."""
+    rgbid.render.depth_agreement compares a rendering with).
+    colour: also keep each export's colour area, a CUDA uint8 [rows, cols, 3] copy, as the keyframe's `colour` (what rgbid.tsdf.fuse
+    colours a mesh with)."""
     counts = eng.keyframe_counts()
     pairs = [(lane, s) for lane, _, _ in lanes for s in range(int(counts[lane]))]
     for lane, _, _ in lanes:
@@ -165,5 +167,13 @@ def chunk_cloud(ctx, eng, lanes, R, t, K, mode, steps, depthinv=False):
         ctx.wait_torch_stream()
         for kf, src in zip(keyframes, srcs):
             check(ctx.L.rgbid_memcpy_d2d(ctx._h, C.c_void_p(kf["depthinv"].data_ptr()), C.c_void_p(src.block_dev + 4 * N), C.c_size_t(4 * N)))
+        ctx.sync()
+    if colour:
+        N = eng.cfg.rows * eng.cfg.cols
+        for kf in keyframes:
+            kf["colour"] = torch.empty((eng.cfg.rows, eng.cfg.cols, 3), dtype=torch.uint8, device=f"cuda:{ctx.device}")
+        ctx.wait_torch_stream()
+        for kf, src in zip(keyframes, srcs):
+            check(ctx.L.rgbid_memcpy_d2d(ctx._h, C.c_void_p(kf["colour"].data_ptr()), C.c_void_p(src.block_dev + N), C.c_size_t(3 * N)))
         ctx.sync()
     return ChunkCloud(pts, off, keyframes)

@@ -11,7 +11,7 @@ from . import engine as E
 
 
 def track_chunked(ctx, depth, rgb, n_chunks, K, group=None, comm=None, cloud=None, optimise=None, loops=None, loop_options=None, segment=None,
-                  keyframe_depth=False, **cfg_kw):
+                  keyframe_depth=False, keyframe_colour=False, **cfg_kw):
     """depth [T, rows, cols] 16-bit, rgb [T, rows, cols, 3] uint8 CUDA tensors of ONE sequence.
     Returns (R [T,3,3], t [T,3], ranges); the per-frame status / covariance are in track_chunked.last = (status, cov).
 
@@ -35,7 +35,10 @@ def track_chunked(ctx, depth, rgb, n_chunks, K, group=None, comm=None, cloud=Non
 
     keyframe_depth = True (with cloud) keeps every exported keyframe's inverse-depth plane on the device as `depthinv` of the cloud's
     keyframes, for rgbid.render.depth_agreement; with optimise the cloud placed with the trajectory BEFORE the optimisation is left in
-    track_chunked.last_cloud_before as well, so that the agreement can be compared across it."""
+    track_chunked.last_cloud_before as well, so that the agreement can be compared across it.
+
+    keyframe_colour = True (with cloud) keeps every exported keyframe's colours on the device as `colour` of the cloud's keyframes (uint8
+    [rows, cols, 3]), for rgbid.tsdf.fuse."""
     if cloud not in (None, "novel", "all"):
         raise ValueError(f"cloud must be None, 'novel' or 'all', not {cloud!r}")
     if optimise not in (None, "auto", "multilevel", "single"):
@@ -94,7 +97,7 @@ def track_chunked(ctx, depth, rgb, n_chunks, K, group=None, comm=None, cloud=Non
     from . import cloud as CL
     try:
         lanes_of = [(i, c, ranges[c][0]) for i, c in enumerate(mine)]
-        pc = CL.chunk_cloud(ctx, eng, lanes_of, R, t, K, cloud, steps=L, depthinv=keyframe_depth)
+        pc = CL.chunk_cloud(ctx, eng, lanes_of, R, t, K, cloud, steps=L, depthinv=keyframe_depth, colour=keyframe_colour)
         if keyframe_depth and optimise is not None:
             before = CL.chunk_cloud(ctx, eng, lanes_of, R0, t0, K, cloud, steps=L)
             for kf, after in zip(before.keyframes, pc.keyframes):

@@ -1,0 +1,339 @@
+"""Keyframes fused into a truncated signed distance volume, and the volume's surface as a triangle mesh (binding of include/rgbid_tsdf.h).
+
+`Volume.integrate` averages the inverse-depth planes (and colours) of keyframes, as `sequence.track_chunked(cloud=..., keyframe_depth=True,
+keyframe_colour=True)` leaves them on the device, into a dense voxel volume; `Volume.extract` cuts the volume's zero crossing with marching
+tetrahedra into vertices, vertex colours and index triples, byte-identical to the numpy restatement of the contract.
+`fuse` is the one-shot over the keyframes of a run and `write_mesh_ply` writes what any viewer opens.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check
+from .consist import planes_arg
+from .render import Pose, depth_range, image_size, intrinsics, poses
+
+MAX_VOXELS = 1 << 29
+MAX_VIEWS = 65535
+MAX_WEIGHT = 65535
+VIEW_CHUNK = 16                         # RGBID_TSDF_VIEW_CHUNK: views one launch walks; more go in further launches, in order
+EXPORTS = ["rgbid_tsdf_create", "rgbid_tsdf_destroy", "rgbid_tsdf_configure", "rgbid_tsdf_reset", "rgbid_tsdf_integrate", "rgbid_tsdf_get_state",
+           "rgbid_tsdf_set_state", "rgbid_tsdf_extract_plan", "rgbid_tsdf_extract_emit", "rgbid_tsdf_timing"]
+STAGES = ("integrate", "scan", "emit")
+
+
+class View(C.Structure):
+    """rgbid_tsdf_view: a keyframe's world pose, its inverse-depth plane and its colours (or NULL) on the device"""
+    _fields_ = [("pose", Pose), ("depthinv_dev", C.c_void_p), ("colour_dev", C.c_void_p)]
+
+
+def _integer(name, v):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        raise ValueError(f"{name}: an integer, got {v!r}")
+    return int(v)
+
+
+def _float32(name, v):
+    try:
+        with np.errstate(over="ignore"):
+            f = float(np.float32(v))
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"{name}: a number, got {v!r}")
+    if not math.isfinite(f):
+        raise ValueError(f"{name} must be finite, got {v!r}")
+    return f
+
+
+def capacity_arg(max_voxels, max_views):
+    """-> (max_voxels, max_views) of a handle: 8 .. 2^29 voxels and 1 .. 65 535 views per call (ValueError otherwise)"""
+    n, v = _integer("max_voxels", max_voxels), _integer("max_views", max_views)
+    if not 8 <= n <= MAX_VOXELS:
+        raise ValueError(f"max_voxels must lie in [8, 2^29], got {max_voxels!r}")
+    if not 1 <= v <= MAX_VIEWS:
+        raise ValueError(f"max_views must lie in [1, {MAX_VIEWS}], got {max_views!r}")
+    return n, v
+
+
+def grid_arg(nx, ny, nz, origin, voxel, trunc, max_voxels=MAX_VOXELS):
+    """-> (nx, ny, nz, origin, voxel, trunc) as the library takes them: dimensions >= 2 with nx ny nz <= max_voxels, origin three finite
+    float32 values, voxel and trunc finite float32 values > 0 (ValueError otherwise)"""
+    dims = tuple(_integer(n, v) for n, v in zip(("nx", "ny", "nz"), (nx, ny, nz)))
+    if min(dims) < 2:
+        raise ValueError(f"every dimension must be at least 2, got {dims}")
+    if dims[0] * dims[1] * dims[2] > max_voxels:
+        raise ValueError(f"{dims[0]} x {dims[1]} x {dims[2]} voxels are more than {max_voxels}")
+    try:
+        o = list(origin)
+    except TypeError:
+        raise ValueError(f"origin: three numbers, got {origin!r}")
+    if len(o) != 3:
+        raise ValueError(f"origin: three numbers, got {origin!r}")
+    o = [_float32("origin", v) for v in o]
+    h, tr = _float32("voxel", voxel), _float32("trunc", trunc)
+    if not (h > 0 and tr > 0):
+        raise ValueError(f"voxel and trunc must be > 0, got {voxel!r}, {trunc!r}")
+    return dims + (o, h, tr)
+
+
+def weight_arg(min_weight):
+    """-> min_weight: an integer in 1 .. 65 535 (ValueError otherwise)"""
+    w = _integer("min_weight", min_weight)
+    if not 1 <= w <= MAX_WEIGHT:
+        raise ValueError(f"min_weight must lie in [1, {MAX_WEIGHT}], got {min_weight!r}")
+    return w
+
+
+def colours_arg(colours, views, rows, cols, device=None):
+    """-> the colour planes as a list of `views` entries, each None or a contiguous CUDA uint8 tensor [rows, cols, 3] (ValueError
+    otherwise).  colours: None (no view has colours), a sequence of such entries or one tensor [views, rows, cols, 3]"""
+    if colours is None:
+        return [None] * views
+    if isinstance(colours, torch.Tensor):
+        colours = list(colours) if colours.dim() == 4 else [colours]
+    try:
+        colours = list(colours)
+    except TypeError:
+        raise ValueError("colours: a sequence of CUDA uint8 tensors [rows, cols, 3] or None")
+    if len(colours) != views:
+        raise ValueError(f"{views} views need {views} colour planes, got {len(colours)}")
+    for c in colours:
+        if c is None:
+            continue
+        if not (isinstance(c, torch.Tensor) and c.is_cuda and c.dtype == torch.uint8 and tuple(c.shape) == (rows, cols, 3) and c.is_contiguous()):
+            raise ValueError(f"colours: contiguous CUDA uint8 tensors [{rows}, {cols}, 3] or None")
+        if device is not None and c.device.index != device:
+            raise ValueError(f"colours must live on device {device}")
+    return colours
+
+
+def bounds_grid(bounds, voxel, max_voxels=MAX_VOXELS):
+    """the volume that covers the box bounds = x0 y0 z0 x1 y1 z1 with voxels of `voxel` metres: -> (nx, ny, nz, origin); voxel centres on
+    the box's low corner, at least 2 per axis.  ValueError for a box that is not finite or inverted, and, naming the voxel size that would
+    fit, for more than max_voxels voxels"""
+    try:
+        b = np.asarray(bounds, np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError(f"bounds: x0 y0 z0 x1 y1 z1, got {bounds!r}")
+    h = _float32("voxel", voxel)
+    if b.shape != (6,) or not np.isfinite(b).all() or (b[3:] < b[:3]).any():
+        raise ValueError(f"bounds: six finite numbers x0 y0 z0 x1 y1 z1 with x0 <= x1, y0 <= y1, z0 <= z1, got {bounds!r}")
+    if not h > 0:
+        raise ValueError(f"voxel must be > 0, got {voxel!r}")
+    ext = b[3:] - b[:3]
+    dims = [max(int(math.ceil(e / h)) + 1, 2) for e in ext]
+    if dims[0] * dims[1] * dims[2] > max_voxels:
+        fit = h
+        while np.prod([max(math.ceil(e / fit) + 1, 2) for e in ext]) > max_voxels:
+            fit *= 1.05
+        raise ValueError(f"a box of {ext[0]:.3g} x {ext[1]:.3g} x {ext[2]:.3g} m needs {dims[0]} x {dims[1]} x {dims[2]} voxels of {h:g} m, more than "
+                         f"{max_voxels}: a voxel of {fit:.3g} m would fit")
+    return dims[0], dims[1], dims[2], [float(np.float32(v)) for v in b[:3]]
+
+
+class Volume(_lib.CtxHandle):
+    """A TSDF volume of up to max_voxels voxels that takes up to max_views views per integrate call, on the context's stream."""
+    _destroy = "rgbid_tsdf_destroy"
+
+    def __init__(self, ctx, max_voxels, max_views, colour=True):
+        self.max_voxels, self.max_views = capacity_arg(max_voxels, max_views)
+        super().__init__(ctx)
+        self.colour = bool(colour)
+        self.nx = self.ny = self.nz = 2
+        L = self.L
+        L.rgbid_tsdf_create.argtypes = [C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_int, C.c_int]
+        L.rgbid_tsdf_configure.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_float]
+        L.rgbid_tsdf_reset.argtypes = [C.c_void_p]
+        L.rgbid_tsdf_integrate.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float]
+        L.rgbid_tsdf_get_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rgbid_tsdf_set_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rgbid_tsdf_extract_plan.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p]
+        L.rgbid_tsdf_extract_emit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_ulonglong]
+        L.rgbid_tsdf_timing.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        self._created(L.rgbid_tsdf_create(C.byref(self._h), ctx._h, C.c_ulonglong(self.max_voxels), self.max_views, int(self.colour)))
+
+    @property
+    def shape(self):
+        return (self.nz, self.ny, self.nx)
+
+    @property
+    def _dev(self):
+        return f"cuda:{self.ctx.device}"
+
+    def configure(self, nx, ny, nz, origin, voxel, trunc):
+        """the volume's shape (nx ny nz voxels of `voxel` metres, the centre of voxel (0, 0, 0) at `origin`, truncation `trunc` metres),
+        and a reset"""
+        nx, ny, nz, o, h, tr = grid_arg(nx, ny, nz, origin, voxel, trunc, self.max_voxels)
+        check(self.L.rgbid_tsdf_configure(self._h, nx, ny, nz, (C.c_float * 3)(*o), h, tr))
+        self.nx, self.ny, self.nz, self.origin, self.voxel, self.trunc = nx, ny, nz, o, h, tr
+
+    def reset(self):
+        check(self.L.rgbid_tsdf_reset(self._h))
+
+    def integrate(self, planes, colours, R, t, K, rows, cols, z_min=0.05, z_max=20.0):
+        """fuse the views R [V, 3, 3], t [V, 3] with the inverse-depth `planes` and `colours` (None, or per view None or a CUDA uint8
+        [rows, cols, 3]) into the volume, in this order.  Asynchronous on the context's stream (planes and colours written on torch's
+        stream are waited for first); they must stay unchanged until it has run."""
+        R, t = poses(R, t)
+        V = len(R)
+        rows, cols = image_size(rows, cols)
+        if V > self.max_views:
+            raise ValueError(f"{V} views are more than the volume's {self.max_views}")
+        planes = planes_arg(planes, V, rows, cols, self.ctx.device)
+        colours = colours_arg(colours, V, rows, cols, self.ctx.device)
+        lo, hi = depth_range(z_min, z_max)
+        k = (C.c_float * 4)(*intrinsics(K))
+        views = (View * V)(*[View(Pose((C.c_double * 9)(*R[v].reshape(9)), (C.c_double * 3)(*t[v])), planes[v].data_ptr(),
+                                  colours[v].data_ptr() if colours[v] is not None else None) for v in range(V)])
+        self.ctx.wait_torch_stream()
+        check(self.L.rgbid_tsdf_integrate(self._h, V, views, k, rows, cols, lo, hi))
+
+    def state(self):
+        """-> (D float32 [nz, ny, nx], counts int32 [nz, ny, nx] = W | Cn << 16, rgb_sum int32 [3, nz, ny, nx]) as new CUDA tensors.
+        Synchronises."""
+        D = torch.empty(self.shape, dtype=torch.float32, device=self._dev)
+        counts = torch.empty(self.shape, dtype=torch.int32, device=self._dev)
+        rgb = torch.empty((3,) + self.shape, dtype=torch.int32, device=self._dev)
+        self.ctx.wait_torch_stream()   # the outputs are torch's allocations
+        check(self.L.rgbid_tsdf_get_state(self._h, D.data_ptr(), counts.data_ptr(), rgb.data_ptr()))
+        self.ctx.sync()
+        return D, counts, rgb
+
+    def set_state(self, D, counts, rgb_sum=None):
+        """replace the state by CUDA tensors of state()'s shapes (counts and rgb_sum int32 or uint32 bits; None: zeros).  Synchronises."""
+        def plane(name, x, dtype_ok, shape):
+            if x is None:
+                return None
+            if not (isinstance(x, torch.Tensor) and x.is_cuda and dtype_ok(x) and tuple(x.shape) == shape and x.is_contiguous()
+                    and x.device.index == self.ctx.device):
+                raise ValueError(f"{name}: a contiguous CUDA tensor {list(shape)} of 4-byte elements on device {self.ctx.device}")
+            return x.data_ptr()
+        is_int = lambda x: x.element_size() == 4 and not x.is_floating_point()
+        d = plane("D", D, lambda x: x.dtype == torch.float32, self.shape)
+        c = plane("counts", counts, is_int, self.shape)
+        s = plane("rgb_sum", rgb_sum, is_int, (3,) + self.shape)
+        if s is not None and not self.colour:
+            raise ValueError("rgb_sum: the volume holds no colour")
+        self.ctx.wait_torch_stream()
+        check(self.L.rgbid_tsdf_set_state(self._h, d, c, s))
+        self.ctx.sync()
+
+    def extract(self, min_weight=1, colours=True):
+        """the surface among the voxels of weight >= min_weight -> (vertices float32 [nv, 3], colours uint8 [nv, 3] or None, triangles
+        int32 [nt, 3] holding the uint32 vertex indices) as CUDA tensors.  Synchronises."""
+        w = weight_arg(min_weight)
+        nv, nt = C.c_ulonglong(), C.c_ulonglong()
+        self.ctx.wait_torch_stream()
+        check(self.L.rgbid_tsdf_extract_plan(self._h, w, C.byref(nv), C.byref(nt)))
+        verts = torch.empty((nv.value, 3), dtype=torch.float32, device=self._dev)
+        cols = torch.empty((nv.value, 3), dtype=torch.uint8, device=self._dev) if colours else None
+        tris = torch.empty((nt.value, 3), dtype=torch.int32, device=self._dev)
+        self.ctx.wait_torch_stream()   # the outputs are torch's allocations
+        self.emit(verts, cols, tris)
+        self.ctx.sync()
+        return verts, cols, tris
+
+    def emit(self, vertices, colours, triangles):
+        """write the last plan's mesh into CUDA tensors [>= nv, 3] float32, [>= nv, 3] uint8 or None, [>= nt, 3] int32.  Asynchronous."""
+        assert vertices.is_cuda and vertices.dtype == torch.float32 and vertices.is_contiguous() and vertices.dim() == 2 and vertices.shape[1] == 3
+        assert triangles.is_cuda and triangles.element_size() == 4 and triangles.is_contiguous() and triangles.dim() == 2 and triangles.shape[1] == 3
+        if colours is not None:
+            assert colours.is_cuda and colours.dtype == torch.uint8 and colours.is_contiguous() and tuple(colours.shape) == tuple(vertices.shape)
+        ptr = lambda x: C.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
+        check(self.L.rgbid_tsdf_extract_emit(self._h, ptr(vertices), ptr(colours), ptr(triangles), C.c_ulonglong(vertices.shape[0]),
+                                             C.c_ulonglong(triangles.shape[0])))
+
+    def timing(self, enable=True):
+        """record HIP events around the stages of the following calls; -> the device ms of the last ones {stage: ms}"""
+        ms = (C.c_float * 3)()
+        check(self.L.rgbid_tsdf_timing(self._h, int(enable), ms))
+        return dict(zip(STAGES, ms[:]))
+
+
+def cloud_bounds(points, pad=0.0):
+    """the bounding box x0 y0 z0 x1 y1 z1 of the finite records of a cloud (CUDA uint8 [M, 32]), padded by `pad` metres; None without one"""
+    xyz = points.view(torch.float32)[:, :3]
+    xyz = xyz[torch.isfinite(xyz).all(1)]
+    if not len(xyz):
+        return None
+    lo, hi = xyz.min(0).values.cpu().numpy().astype(np.float64), xyz.max(0).values.cpu().numpy().astype(np.float64)
+    return [float(v) for v in np.concatenate([lo - pad, hi + pad])]
+
+
+def fuse(ctx, keyframes, K, rows, cols, bounds=None, voxel=0.02, trunc=None, min_weight=1, z_min=0.05, z_max=20.0, max_voxels=1 << 27,
+         points=None, return_volume=False):
+    """one-shot over the keyframes of a run (ChunkCloud.keyframes with `depthinv` and, for a coloured mesh, `colour`): a volume over
+    `bounds` = x0 y0 z0 x1 y1 z1 (None: the box of the cloud `points`, padded by trunc) with voxels of `voxel` metres, every keyframe
+    integrated in order with its world pose, the surface extracted -> (vertices, colours, triangles) as CUDA tensors, with return_volume
+    also a dict of the volume's figures (nx, ny, nz, origin, voxels, touched).  trunc defaults to 4 voxel."""
+    trunc = 4.0 * voxel if trunc is None else trunc
+    w = weight_arg(min_weight)
+    if not keyframes:
+        raise ValueError("no keyframes to fuse")
+    if bounds is None:
+        bounds = cloud_bounds(points, _float32("trunc", trunc)) if points is not None else None
+        if bounds is None:
+            raise ValueError("bounds: needed without a cloud of finite points")
+    nx, ny, nz, origin = bounds_grid(bounds, voxel, max_voxels)
+    grid_arg(nx, ny, nz, origin, voxel, trunc)
+    has_colour = all(kf.get("colour") is not None for kf in keyframes)
+    V = len(keyframes)
+    vol = Volume(ctx, nx * ny * nz, min(V, MAX_VIEWS), colour=has_colour)
+    try:
+        vol.configure(nx, ny, nz, origin, voxel, trunc)
+        for a in range(0, V, MAX_VIEWS):
+            kfs = keyframes[a:a + MAX_VIEWS]
+            vol.integrate([k["depthinv"] for k in kfs], [k["colour"] for k in kfs] if has_colour else None, np.stack([k["R"] for k in kfs]),
+                          np.stack([k["t"] for k in kfs]), K, rows, cols, z_min, z_max)
+        mesh = vol.extract(w, colours=True)
+        if not return_volume:
+            return mesh
+        _, counts, _ = vol.state()
+        info = dict(nx=nx, ny=ny, nz=nz, origin=origin, voxels=nx * ny * nz, touched=int(((counts & 0xFFFF) != 0).sum().item()))
+        return mesh + (info,)
+    finally:
+        vol.close()
+
+
+def mesh_ply_bytes(vertices, colours, triangles):
+    """binary little-endian PLY of a mesh: element vertex with x y z (float) and red green blue (uchar), element face with
+    `property list uchar uint vertex_indices`; colours None: black.  Tensors (host or device) or numpy arrays."""
+    host = lambda x: x.cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    v = np.ascontiguousarray(host(vertices), "<f4").reshape(-1, 3)
+    t = np.ascontiguousarray(host(triangles)).reshape(-1, 3)
+    t = t.view(np.uint32) if t.dtype == np.int32 else t.astype(np.uint32)
+    c = np.zeros((len(v), 3), np.uint8) if colours is None else np.ascontiguousarray(host(colours), np.uint8).reshape(-1, 3)
+    assert len(c) == len(v) and (not len(t) or int(t.max()) < len(v))
+    head = ("ply\nformat binary_little_endian 1.0\ncomment rgbid fused keyframe mesh\n"
+            f"element vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n"
+            "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+            f"element face {len(t)}\nproperty list uchar uint vertex_indices\nend_header\n")
+    vr = np.empty(len(v), np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")]))
+    vr["x"], vr["y"], vr["z"] = v[:, 0], v[:, 1], v[:, 2]
+    vr["red"], vr["green"], vr["blue"] = c[:, 0], c[:, 1], c[:, 2]
+    fr = np.empty(len(t), np.dtype([("n", "u1"), ("i", "<u4", (3,))]))
+    fr["n"] = 3
+    fr["i"] = t
+    return head.encode("ascii") + vr.tobytes() + fr.tobytes()
+
+
+def write_mesh_ply(path, vertices, colours, triangles):
+    with open(path, "wb") as f:
+        f.write(mesh_ply_bytes(vertices, colours, triangles))
+
+
+def read_mesh_ply(data):
+    """what mesh_ply_bytes wrote -> (vertices float32 [nv, 3], colours uint8 [nv, 3], triangles uint32 [nt, 3])"""
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    head = data[:end].decode("ascii").split("\n")
+    nv = int([l for l in head if l.startswith("element vertex")][0].split()[2])
+    nt = int([l for l in head if l.startswith("element face")][0].split()[2])
+    vd = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+    fd = np.dtype([("n", "u1"), ("i", "<u4", (3,))])
+    assert len(data) == end + nv * vd.itemsize + nt * fd.itemsize
+    v = np.frombuffer(data, vd, nv, end)
+    f = np.frombuffer(data, fd, nt, end + nv * vd.itemsize)
+    assert (f["n"] == 3).all()
+    return np.stack([v["x"], v["y"], v["z"]], 1), np.stack([v["red"], v["green"], v["blue"]], 1), f["i"].copy()

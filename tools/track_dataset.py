@@ -84,6 +84,17 @@ def main():
                          "agrees with the depth that keyframe measured (pixels compared, median and 90th percentile of the difference in "
                          "metres), per keyframe and over the run; with --optimise before and after the optimisation.  It reads the cloud "
                          "before --cloud-radius and --voxel: only there does a point still belong to its keyframe")
+    ap.add_argument("--mesh", default="", metavar="PATH",
+                    help="fuse the exported keyframes' depth and colours into a TSDF volume on the device and write its surface as a binary "
+                         "PLY triangle mesh (DESIGN.md section 19); with --optimise the optimised poses are used; with several ranks each "
+                         "writes PATH with .rank<r> before the extension")
+    ap.add_argument("--mesh-voxel", type=float, default=None, metavar="H", help="with --mesh: the voxel size in metres (default 0.02)")
+    ap.add_argument("--mesh-trunc", type=float, default=None, metavar="T", help="with --mesh: the truncation distance in metres (default 4 H)")
+    ap.add_argument("--mesh-min-weight", type=int, default=None, metavar="W",
+                    help="with --mesh: keyframes that must have measured a voxel for the surface to pass it (1 .. 65535, default 1)")
+    ap.add_argument("--mesh-bounds", type=float, nargs=6, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
+                    help="with --mesh: the volume's box in world metres (default: the box of the keyframe cloud, padded by T)")
+    ap.add_argument("--mesh-max-voxels", type=int, default=None, metavar="N", help="with --mesh: the largest volume to allocate (default 2^27 voxels)")
     ap.add_argument("--optimise", nargs="?", const="auto", default=None, choices=["auto", "multilevel", "single"],
                     help="optimise the trajectory with the pose-graph back-end once over the run (single rank; DESIGN.md section 11)")
     ap.add_argument("--loops", default=None, choices=["auto", "appearance"],
@@ -137,6 +148,21 @@ def main():
             consist = dict(zip(("tol_rel", "tol_abs"), CF.tolerances(args.cloud_consistency, args.cloud_consistency_abs or 0.0)))
             consist["window"] = CF.window_arg(1 if args.cloud_consistency_window is None else args.cloud_consistency_window)
             consist.update(zip(("min_support", "max_conflicts"), CF.vote_args(args.cloud_min_support or 0, args.cloud_max_conflicts or 0)))
+        except ValueError as e:
+            ap.error(str(e))
+    if not args.mesh and not (args.mesh_voxel is None and args.mesh_trunc is None and args.mesh_min_weight is None and args.mesh_bounds is None
+                              and args.mesh_max_voxels is None):
+        ap.error("--mesh-voxel / --mesh-trunc / --mesh-min-weight / --mesh-bounds / --mesh-max-voxels need --mesh")
+    if args.mesh:
+        from rgbid import tsdf as TS
+        try:
+            mesh = dict(voxel=0.02 if args.mesh_voxel is None else args.mesh_voxel, min_weight=TS.weight_arg(1 if args.mesh_min_weight is None else args.mesh_min_weight))
+            mesh["trunc"] = 4.0 * mesh["voxel"] if args.mesh_trunc is None else args.mesh_trunc
+            mesh["max_voxels"] = TS.capacity_arg((1 << 27) if args.mesh_max_voxels is None else args.mesh_max_voxels, 1)[0]
+            TS.grid_arg(2, 2, 2, (0.0, 0.0, 0.0), mesh["voxel"], mesh["trunc"])
+            if args.mesh_bounds is not None:
+                TS.bounds_grid(args.mesh_bounds, mesh["voxel"], mesh["max_voxels"])
+                mesh["bounds"] = args.mesh_bounds
         except ValueError as e:
             ap.error(str(e))
     if (args.cloud_radius is None) != (args.cloud_min_neighbours is None):
@@ -201,7 +227,9 @@ def main():
     opt = run_options(args)
     if args.render_check or args.cloud_consistency is not None:
         opt["keyframe_depth"] = True
-    if args.cloud:
+    if args.mesh:
+        opt.update(keyframe_depth=True, keyframe_colour=True)
+    if args.cloud or args.mesh:
         R, t, ranges, pc = sequence.track_chunked(ctx, depth, rgb, args.chunks, tuple(args.K), comm=comm, use_graph=0,
                                                   cloud="all" if args.cloud_all else "novel", **opt)
     else:
@@ -273,6 +301,20 @@ def main():
                     tum.write_png(os.path.join(args.render, name + ".png"), views["colour"][j].cpu().numpy())
                     tum.write_png(os.path.join(args.render, name + "_depth.png"), RD.depth_png(views["depth"][j]))
             print(f"rank {rank}: {len(pc.keyframes)} views of {points.shape[0]} records, splat {splat} -> {args.render}")
+    if args.mesh:
+        path = args.mesh
+        if world > 1:
+            root, ext = os.path.splitext(path)
+            path = f"{root}.rank{rank}{ext}"
+        if not pc.keyframes:
+            sys.exit(f"rank {rank}: --mesh: the run exported no keyframe")
+        try:
+            verts, cols, tris, vol = TS.fuse(ctx, pc.keyframes, tuple(args.K), args.rows, args.cols, points=pc.points, return_volume=True, **mesh)
+        except ValueError as e:
+            sys.exit(f"rank {rank}: --mesh: {e}")
+        TS.write_mesh_ply(path, verts, cols, tris)
+        print(f"rank {rank}: mesh of {len(pc.keyframes)} keyframes: {vol['nx']} x {vol['ny']} x {vol['nz']} = {vol['voxels']} voxels of {mesh['voxel']:g} m "
+              f"(truncation {mesh['trunc']:g} m), {vol['touched']} touched, {verts.shape[0]} vertices, {tris.shape[0]} triangles -> {path}")
     if comm is not None:
         comm.close()
     if rank == 0:
