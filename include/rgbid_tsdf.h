@@ -46,6 +46,8 @@
  *     A row has its last two entries swapped iff, with every cut at its edge's midpoint, ((M1 - M0) x (M2 - M0)) . (P_out - P_in) < 0 for
  *     the row's first edge: the normal points from inside to outside.  The swap depends on (tetrahedron, case) only; it is one constant
  *     table of 6 x 16 entries (case = sum of 1 << u over the inside vertices u).  Zero-area triangles (D_b = 0) are kept.
+ *
+ * Steps 13 - 23 (the volume ray-cast into camera views, a normal per vertex) and their calls are in rgbid_tsdf_raycast.h, included below.
  */
 #ifndef RGBID_TSDF_H_
 #define RGBID_TSDF_H_
@@ -112,4 +114,7 @@ int rgbid_tsdf_timing(rgbid_tsdf* v, int enable, float ms[3]);
 #ifdef __cplusplus
 }
 #endif
+
+/* steps 13 - 23 and their calls: the volume ray-cast into camera views, and a normal per mesh vertex */
+#include "rgbid_tsdf_raycast.h"
 #endif

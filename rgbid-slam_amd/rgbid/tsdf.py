@@ -14,7 +14,7 @@ import torch
 from . import _lib
 from ._lib import check
 from .consist import planes_arg
-from .render import Pose, depth_range, image_size, intrinsics, poses
+from .render import Pose, agreement_summary, depth_range, image_size, intrinsics, poses, rank_value  # noqa: F401 (agreement_summary: for callers)
 
 MAX_VOXELS = 1 << 29
 MAX_VIEWS = 65535
@@ -23,6 +23,9 @@ VIEW_CHUNK = 16                         # RGBID_TSDF_VIEW_CHUNK: views one launc
 EXPORTS = ["rgbid_tsdf_create", "rgbid_tsdf_destroy", "rgbid_tsdf_configure", "rgbid_tsdf_reset", "rgbid_tsdf_integrate", "rgbid_tsdf_get_state",
            "rgbid_tsdf_set_state", "rgbid_tsdf_extract_plan", "rgbid_tsdf_extract_emit", "rgbid_tsdf_timing"]
 STAGES = ("integrate", "scan", "emit")
+MAX_STEPS = 65536                       # RGBID_TSDF_MAX_STEPS: (z_max - z_min) / step at most
+RAYCAST_EXPORTS = ["rgbid_tsdf_pose_wc", "rgbid_tsdf_raycast", "rgbid_tsdf_raycast_timing", "rgbid_tsdf_extract_normals"]   # rgbid_tsdf_raycast.h
+RAYCAST_PLANES = ("depth", "normal", "colour")
 
 
 class View(C.Structure):
@@ -86,6 +89,43 @@ def weight_arg(min_weight):
     return w
 
 
+def step_arg(step, z_min, z_max):
+    """-> the ray cast's sample spacing as the float32 value the library receives: finite, > 0 and with (z_max - z_min) / step <= 65 536
+    for the gate's float32 values (ValueError otherwise)"""
+    lo, hi = depth_range(z_min, z_max)
+    s = _float32("step", step)
+    if not s > 0:
+        raise ValueError(f"step must be > 0, got {step!r}")
+    if (hi - lo) / s > MAX_STEPS:
+        raise ValueError(f"step {step!r} needs more than {MAX_STEPS} samples between {z_min!r} and {z_max!r}")
+    return s
+
+
+def raycast_outputs_arg(outputs):
+    """-> the requested planes as a tuple out of depth, normal, colour (ValueError otherwise)"""
+    outs = (outputs,) if isinstance(outputs, str) else tuple(outputs)
+    if not outs or any(o not in RAYCAST_PLANES for o in outs):
+        raise ValueError(f"outputs: some of {RAYCAST_PLANES}, got {outputs!r}")
+    return outs
+
+
+def pose_wc(R, t):
+    """the twelve float32 values R00 .. R22, tx, ty, tz of R_WC | t_WC as the library forms them from one world pose"""
+    p = Pose((C.c_double * 9)(*np.asarray(R, np.float64).reshape(9)), (C.c_double * 3)(*np.asarray(t, np.float64).reshape(3)))
+    out = (C.c_float * 12)()
+    check(_lib.lib().rgbid_tsdf_pose_wc(C.byref(p), out))
+    return np.array(out[:], np.float32)
+
+
+def shade(normal):
+    """a camera-frame normal plane float32 [3, rows, cols] (tensor or array) -> uint8 [rows, cols]: floor(255 max(0, -n_z) + 0.5) where
+    the normal is finite, 0 elsewhere.  A picture of the surface lit from the camera, not a contract."""
+    n = np.asarray(normal.cpu() if isinstance(normal, torch.Tensor) else normal, np.float32)
+    ok = np.isfinite(n).all(0)
+    v = np.floor(255.0 * np.maximum(0.0, -np.where(ok, n[2], 0).astype(np.float64)) + 0.5)
+    return np.where(ok, np.clip(v, 0, 255), 0).astype(np.uint8)
+
+
 def colours_arg(colours, views, rows, cols, device=None):
     """-> the colour planes as a list of `views` entries, each None or a contiguous CUDA uint8 tensor [rows, cols, 3] (ValueError
     otherwise).  colours: None (no view has colours), a sequence of such entries or one tensor [views, rows, cols, 3]"""
@@ -142,6 +182,7 @@ class Volume(_lib.CtxHandle):
         super().__init__(ctx)
         self.colour = bool(colour)
         self.nx = self.ny = self.nz = 2
+        self.origin, self.voxel, self.trunc = [0.0, 0.0, 0.0], 1.0, 1.0   # a new handle's shape (rgbid_tsdf_create)
         L = self.L
         L.rgbid_tsdf_create.argtypes = [C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_int, C.c_int]
         L.rgbid_tsdf_configure.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_float]
@@ -152,6 +193,10 @@ class Volume(_lib.CtxHandle):
         L.rgbid_tsdf_extract_plan.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p]
         L.rgbid_tsdf_extract_emit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_ulonglong]
         L.rgbid_tsdf_timing.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.rgbid_tsdf_raycast.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_uint,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rgbid_tsdf_raycast_timing.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.rgbid_tsdf_extract_normals.argtypes = [C.c_void_p, C.c_void_p, C.c_ulonglong]
         self._created(L.rgbid_tsdf_create(C.byref(self._h), ctx._h, C.c_ulonglong(self.max_voxels), self.max_views, int(self.colour)))
 
     @property
@@ -220,9 +265,10 @@ class Volume(_lib.CtxHandle):
         check(self.L.rgbid_tsdf_set_state(self._h, d, c, s))
         self.ctx.sync()
 
-    def extract(self, min_weight=1, colours=True):
+    def extract(self, min_weight=1, colours=True, normals=False):
         """the surface among the voxels of weight >= min_weight -> (vertices float32 [nv, 3], colours uint8 [nv, 3] or None, triangles
-        int32 [nt, 3] holding the uint32 vertex indices) as CUDA tensors.  Synchronises."""
+        int32 [nt, 3] holding the uint32 vertex indices) as CUDA tensors; with normals a fourth element, the vertices' world-frame unit
+        normals float32 [nv, 3] (0 0 0 where the gradient vanishes).  Synchronises."""
         w = weight_arg(min_weight)
         nv, nt = C.c_ulonglong(), C.c_ulonglong()
         self.ctx.wait_torch_stream()
@@ -230,10 +276,65 @@ class Volume(_lib.CtxHandle):
         verts = torch.empty((nv.value, 3), dtype=torch.float32, device=self._dev)
         cols = torch.empty((nv.value, 3), dtype=torch.uint8, device=self._dev) if colours else None
         tris = torch.empty((nt.value, 3), dtype=torch.int32, device=self._dev)
+        nrm = torch.empty((nv.value, 3), dtype=torch.float32, device=self._dev) if normals else None
         self.ctx.wait_torch_stream()   # the outputs are torch's allocations
         self.emit(verts, cols, tris)
+        if normals:
+            self.emit_normals(nrm)
         self.ctx.sync()
-        return verts, cols, tris
+        return (verts, cols, tris, nrm) if normals else (verts, cols, tris)
+
+    def emit_normals(self, normals):
+        """write the last plan's vertex normals into a CUDA tensor [>= nv, 3] float32.  Asynchronous."""
+        assert normals.is_cuda and normals.dtype == torch.float32 and normals.is_contiguous() and normals.dim() == 2 and normals.shape[1] == 3
+        check(self.L.rgbid_tsdf_extract_normals(self._h, C.c_void_p(normals.data_ptr() if normals.numel() else 0), C.c_ulonglong(normals.shape[0])))
+
+    def _raycast_args(self, R, t, K, rows, cols, step, min_weight, z_min, z_max):
+        """the ray cast's arguments as the library takes them (ValueError for what it would refuse)"""
+        R, t = poses(R, t)
+        rows, cols = image_size(rows, cols, len(R), (1 << 31) - 1)
+        if len(R) > self.max_views:
+            raise ValueError(f"{len(R)} views are more than the volume's {self.max_views}")
+        lo, hi = depth_range(z_min, z_max)
+        return R, t, intrinsics(K), rows, cols, step_arg(self.voxel if step is None else step, lo, hi), weight_arg(min_weight), lo, hi
+
+    def raycast_into(self, R, t, K, rows, cols, step, min_weight, z_min, z_max, depth=None, normal=None, colour=None):
+        """the raw call: checked arguments, the given CUDA planes (or None) filled asynchronously on the context's stream: depth float32
+        [V, rows, cols], normal float32 [V, 3, rows, cols], colour uint8 [V, rows, cols, 3], contiguous"""
+        R, t, k, rows, cols, s, w, lo, hi = self._raycast_args(R, t, K, rows, cols, step, min_weight, z_min, z_max)
+        V = len(R)
+        k = (C.c_float * 4)(*k)
+        shapes = dict(depth=((V, rows, cols), torch.float32), normal=((V, 3, rows, cols), torch.float32), colour=((V, rows, cols, 3), torch.uint8))
+        for name, x in (("depth", depth), ("normal", normal), ("colour", colour)):
+            if x is not None and not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == shapes[name][1] and tuple(x.shape) == shapes[name][0]
+                                      and x.is_contiguous() and x.device.index == self.ctx.device):
+                raise ValueError(f"{name}: a contiguous CUDA {shapes[name][1]} tensor {list(shapes[name][0])} on device {self.ctx.device}")
+        arr = (Pose * V)(*[Pose((C.c_double * 9)(*R[v].reshape(9)), (C.c_double * 3)(*t[v])) for v in range(V)])
+        ptr = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None
+        check(self.L.rgbid_tsdf_raycast(self._h, V, arr, k, rows, cols, C.c_float(lo), C.c_float(hi), C.c_float(s), w, ptr(depth), ptr(normal),
+                                        ptr(colour)))
+
+    def raycast(self, R, t, K, rows, cols, step=None, min_weight=1, z_min=0.05, z_max=20.0, outputs=RAYCAST_PLANES):
+        """the fused surface seen from the world poses R [V, 3, 3], t [V, 3] through K = fx, fy, cx, cy: every pixel's ray is marched
+        through the volume in samples `step` metres of camera depth apart (None: the voxel size) up to the first crossing from positive
+        to negative D among voxels of weight >= min_weight -> a dict of the requested planes as CUDA tensors: depth float32
+        [V, rows, cols] (NaN: no surface), normal float32 [V, 3, rows, cols] in the camera frame, colour uint8 [V, rows, cols, 3].
+        A step above trunc / |ray direction| may step over the band.  Synchronises."""
+        outs = raycast_outputs_arg(outputs)
+        R, t, _, rows, cols, step, min_weight, z_min, z_max = self._raycast_args(R, t, K, rows, cols, step, min_weight, z_min, z_max)
+        V = len(R)
+        shape = {"depth": ((V, rows, cols), torch.float32), "normal": ((V, 3, rows, cols), torch.float32), "colour": ((V, rows, cols, 3), torch.uint8)}
+        planes = {o: torch.empty(shape[o][0], dtype=shape[o][1], device=self._dev) for o in outs}
+        self.ctx.wait_torch_stream()   # the outputs are torch's allocations
+        self.raycast_into(R, t, K, rows, cols, step, min_weight, z_min, z_max, **planes)
+        self.ctx.sync()
+        return planes
+
+    def raycast_timing(self, enable=True):
+        """record HIP events around the following ray casts (the switch is `timing`'s); -> the device ms of the last one"""
+        ms = (C.c_float * 1)()
+        check(self.L.rgbid_tsdf_raycast_timing(self._h, int(enable), ms))
+        return float(ms[0])
 
     def emit(self, vertices, colours, triangles):
         """write the last plan's mesh into CUDA tensors [>= nv, 3] float32, [>= nv, 3] uint8 or None, [>= nt, 3] int32.  Asynchronous."""
@@ -263,11 +364,12 @@ def cloud_bounds(points, pad=0.0):
 
 
 def fuse(ctx, keyframes, K, rows, cols, bounds=None, voxel=0.02, trunc=None, min_weight=1, z_min=0.05, z_max=20.0, max_voxels=1 << 27,
-         points=None, return_volume=False):
+         points=None, return_volume=False, normals=False, keep_volume=False):
     """one-shot over the keyframes of a run (ChunkCloud.keyframes with `depthinv` and, for a coloured mesh, `colour`): a volume over
     `bounds` = x0 y0 z0 x1 y1 z1 (None: the box of the cloud `points`, padded by trunc) with voxels of `voxel` metres, every keyframe
-    integrated in order with its world pose, the surface extracted -> (vertices, colours, triangles) as CUDA tensors, with return_volume
-    also a dict of the volume's figures (nx, ny, nz, origin, voxels, touched).  trunc defaults to 4 voxel."""
+    integrated in order with its world pose, the surface extracted -> (vertices, colours, triangles) as CUDA tensors, with normals
+    also the vertex normals, with return_volume also a dict of the volume's figures (nx, ny, nz, origin, voxels, touched), with
+    keep_volume also the open Volume, which the caller closes (in this order).  trunc defaults to 4 voxel."""
     trunc = 4.0 * voxel if trunc is None else trunc
     w = weight_arg(min_weight)
     if not keyframes:
@@ -287,19 +389,51 @@ def fuse(ctx, keyframes, K, rows, cols, bounds=None, voxel=0.02, trunc=None, min
             kfs = keyframes[a:a + MAX_VIEWS]
             vol.integrate([k["depthinv"] for k in kfs], [k["colour"] for k in kfs] if has_colour else None, np.stack([k["R"] for k in kfs]),
                           np.stack([k["t"] for k in kfs]), K, rows, cols, z_min, z_max)
-        mesh = vol.extract(w, colours=True)
-        if not return_volume:
-            return mesh
-        _, counts, _ = vol.state()
-        info = dict(nx=nx, ny=ny, nz=nz, origin=origin, voxels=nx * ny * nz, touched=int(((counts & 0xFFFF) != 0).sum().item()))
-        return mesh + (info,)
+        mesh = vol.extract(w, colours=True, normals=normals)
+        if return_volume:
+            _, counts, _ = vol.state()
+            mesh += (dict(nx=nx, ny=ny, nz=nz, origin=origin, voxels=nx * ny * nz, touched=int(((counts & 0xFFFF) != 0).sum().item())),)
+        if keep_volume:
+            mesh += (vol,)
+            vol = None
+        return mesh
     finally:
-        vol.close()
+        if vol is not None:
+            vol.close()
 
 
-def mesh_ply_bytes(vertices, colours, triangles):
-    """binary little-endian PLY of a mesh: element vertex with x y z (float) and red green blue (uchar), element face with
-    `property list uchar uint vertex_indices`; colours None: black.  Tensors (host or device) or numpy arrays."""
+def surface_agreement(vol, keyframes, K, rows, cols, step=None, min_weight=1, z_min=0.05, z_max=20.0):
+    """How well the fused surface agrees with what each keyframe measured: the volume is ray-cast at every keyframe's pose (R, t of its
+    dict), in batches of at most the handle's views -> per keyframe dict(pixels, median, p90) of |z_cast - 1 / iD| (nearest rank) over the
+    pixels that hit and that the keyframe measured (`depthinv` finite and > 0); render.agreement_summary gives the run's figures.
+    Unlike render.depth_agreement, which ignores a keyframe's own records, a keyframe's own contribution to the volume cannot be
+    excluded: every voxel is a mean over all views, so the figure flatters a surface that few keyframes saw."""
+    out = []
+    for a in range(0, len(keyframes), vol.max_views):
+        kfs = keyframes[a:a + vol.max_views]
+        depth = vol.raycast(np.stack([np.asarray(k["R"]) for k in kfs]), np.stack([np.asarray(k["t"]) for k in kfs]), K, rows, cols, step,
+                            min_weight, z_min, z_max, outputs=("depth",))["depth"]
+        for j, k in enumerate(kfs):
+            iD = k["depthinv"]
+            iD = np.asarray(iD.cpu().numpy() if isinstance(iD, torch.Tensor) else iD, np.float32)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                own = np.where(np.isfinite(iD) & (iD > 0), np.float32(1) / iD, np.float32(np.nan)).astype(np.float32)
+            own = torch.from_numpy(own).to(depth.device)
+            both = torch.isfinite(depth[j]) & torch.isfinite(own)
+            d = torch.sort((depth[j][both] - own[both]).abs()).values.cpu().numpy()
+            out.append(dict(pixels=int(len(d)), median=rank_value(d, 5), p90=rank_value(d, 9)))
+    return out
+
+
+def _vertex_dtype(normals):
+    nrm = [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")] if normals else []
+    return np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4")] + nrm + [("red", "u1"), ("green", "u1"), ("blue", "u1")])
+
+
+def mesh_ply_bytes(vertices, colours, triangles, normals=None):
+    """binary little-endian PLY of a mesh: element vertex with x y z (float), with normals also nx ny nz (float), and red green blue
+    (uchar), element face with `property list uchar uint vertex_indices`; colours None: black.  Tensors (host or device) or numpy
+    arrays."""
     host = lambda x: x.cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
     v = np.ascontiguousarray(host(vertices), "<f4").reshape(-1, 3)
     t = np.ascontiguousarray(host(triangles)).reshape(-1, 3)
@@ -308,10 +442,15 @@ def mesh_ply_bytes(vertices, colours, triangles):
     assert len(c) == len(v) and (not len(t) or int(t.max()) < len(v))
     head = ("ply\nformat binary_little_endian 1.0\ncomment rgbid fused keyframe mesh\n"
             f"element vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n"
+            + ("property float nx\nproperty float ny\nproperty float nz\n" if normals is not None else "") +
             "property uchar red\nproperty uchar green\nproperty uchar blue\n"
             f"element face {len(t)}\nproperty list uchar uint vertex_indices\nend_header\n")
-    vr = np.empty(len(v), np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")]))
+    vr = np.empty(len(v), _vertex_dtype(normals is not None))
     vr["x"], vr["y"], vr["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if normals is not None:
+        n = np.ascontiguousarray(host(normals), "<f4").reshape(-1, 3)
+        assert len(n) == len(v)
+        vr["nx"], vr["ny"], vr["nz"] = n[:, 0], n[:, 1], n[:, 2]
     vr["red"], vr["green"], vr["blue"] = c[:, 0], c[:, 1], c[:, 2]
     fr = np.empty(len(t), np.dtype([("n", "u1"), ("i", "<u4", (3,))]))
     fr["n"] = 3
@@ -319,21 +458,24 @@ def mesh_ply_bytes(vertices, colours, triangles):
     return head.encode("ascii") + vr.tobytes() + fr.tobytes()
 
 
-def write_mesh_ply(path, vertices, colours, triangles):
+def write_mesh_ply(path, vertices, colours, triangles, normals=None):
     with open(path, "wb") as f:
-        f.write(mesh_ply_bytes(vertices, colours, triangles))
+        f.write(mesh_ply_bytes(vertices, colours, triangles, normals))
 
 
 def read_mesh_ply(data):
-    """what mesh_ply_bytes wrote -> (vertices float32 [nv, 3], colours uint8 [nv, 3], triangles uint32 [nt, 3])"""
+    """what mesh_ply_bytes wrote -> (vertices float32 [nv, 3], colours uint8 [nv, 3], triangles uint32 [nt, 3]), and as a fourth
+    element the normals float32 [nv, 3] when the file holds them"""
     end = data.index(b"end_header\n") + len(b"end_header\n")
     head = data[:end].decode("ascii").split("\n")
     nv = int([l for l in head if l.startswith("element vertex")][0].split()[2])
     nt = int([l for l in head if l.startswith("element face")][0].split()[2])
-    vd = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+    has_normals = "property float nx" in head
+    vd = _vertex_dtype(has_normals)
     fd = np.dtype([("n", "u1"), ("i", "<u4", (3,))])
     assert len(data) == end + nv * vd.itemsize + nt * fd.itemsize
     v = np.frombuffer(data, vd, nv, end)
     f = np.frombuffer(data, fd, nt, end + nv * vd.itemsize)
     assert (f["n"] == 3).all()
-    return np.stack([v["x"], v["y"], v["z"]], 1), np.stack([v["red"], v["green"], v["blue"]], 1), f["i"].copy()
+    mesh = (np.stack([v["x"], v["y"], v["z"]], 1), np.stack([v["red"], v["green"], v["blue"]], 1), f["i"].copy())
+    return mesh + (np.stack([v["nx"], v["ny"], v["nz"]], 1),) if has_normals else mesh

@@ -95,6 +95,14 @@ def main():
     ap.add_argument("--mesh-bounds", type=float, nargs=6, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
                     help="with --mesh: the volume's box in world metres (default: the box of the keyframe cloud, padded by T)")
     ap.add_argument("--mesh-max-voxels", type=int, default=None, metavar="N", help="with --mesh: the largest volume to allocate (default 2^27 voxels)")
+    ap.add_argument("--mesh-normals", action="store_true", help="with --mesh: the PLY also holds a unit normal per vertex (nx ny nz)")
+    ap.add_argument("--mesh-render", default="", metavar="DIR",
+                    help="with --mesh: ray-cast the fused volume at every exported keyframe's pose (DESIGN.md section 20) and write "
+                         "view_NNNN.png (colour), view_NNNN_depth.png (16-bit, metres * 5000) and view_NNNN_shaded.png into DIR")
+    ap.add_argument("--mesh-render-check", action="store_true",
+                    help="with --mesh: print how well the fused surface, ray-cast at each keyframe's pose, agrees with the depth the keyframe measured")
+    ap.add_argument("--mesh-render-step", type=float, default=None, metavar="S",
+                    help="with --mesh-render / --mesh-render-check: metres of camera depth between two samples of a ray (default: the voxel size)")
     ap.add_argument("--optimise", nargs="?", const="auto", default=None, choices=["auto", "multilevel", "single"],
                     help="optimise the trajectory with the pose-graph back-end once over the run (single rank; DESIGN.md section 11)")
     ap.add_argument("--loops", default=None, choices=["auto", "appearance"],
@@ -153,6 +161,10 @@ def main():
     if not args.mesh and not (args.mesh_voxel is None and args.mesh_trunc is None and args.mesh_min_weight is None and args.mesh_bounds is None
                               and args.mesh_max_voxels is None):
         ap.error("--mesh-voxel / --mesh-trunc / --mesh-min-weight / --mesh-bounds / --mesh-max-voxels need --mesh")
+    if not args.mesh and (args.mesh_normals or args.mesh_render or args.mesh_render_check or args.mesh_render_step is not None):
+        ap.error("--mesh-normals / --mesh-render / --mesh-render-check / --mesh-render-step need --mesh")
+    if args.mesh_render_step is not None and not (args.mesh_render or args.mesh_render_check):
+        ap.error("--mesh-render-step needs --mesh-render or --mesh-render-check")
     if args.mesh:
         from rgbid import tsdf as TS
         try:
@@ -163,6 +175,8 @@ def main():
             if args.mesh_bounds is not None:
                 TS.bounds_grid(args.mesh_bounds, mesh["voxel"], mesh["max_voxels"])
                 mesh["bounds"] = args.mesh_bounds
+            if args.mesh_render_step is not None:
+                TS.step_arg(args.mesh_render_step, 0.05, 20.0)
         except ValueError as e:
             ap.error(str(e))
     if (args.cloud_radius is None) != (args.cloud_min_neighbours is None):
@@ -308,13 +322,41 @@ def main():
             path = f"{root}.rank{rank}{ext}"
         if not pc.keyframes:
             sys.exit(f"rank {rank}: --mesh: the run exported no keyframe")
+        cast = bool(args.mesh_render or args.mesh_render_check)
         try:
-            verts, cols, tris, vol = TS.fuse(ctx, pc.keyframes, tuple(args.K), args.rows, args.cols, points=pc.points, return_volume=True, **mesh)
+            fused = TS.fuse(ctx, pc.keyframes, tuple(args.K), args.rows, args.cols, points=pc.points, return_volume=True, normals=args.mesh_normals,
+                            keep_volume=cast, **mesh)
         except ValueError as e:
             sys.exit(f"rank {rank}: --mesh: {e}")
-        TS.write_mesh_ply(path, verts, cols, tris)
+        verts, cols, tris = fused[:3]
+        vol = fused[4 if args.mesh_normals else 3]
+        TS.write_mesh_ply(path, verts, cols, tris, fused[3] if args.mesh_normals else None)
         print(f"rank {rank}: mesh of {len(pc.keyframes)} keyframes: {vol['nx']} x {vol['ny']} x {vol['nz']} = {vol['voxels']} voxels of {mesh['voxel']:g} m "
               f"(truncation {mesh['trunc']:g} m), {vol['touched']} touched, {verts.shape[0]} vertices, {tris.shape[0]} triangles -> {path}")
+        if cast:
+            volume = fused[-1]
+            try:
+                Kt, kfs_all = tuple(args.K), pc.keyframes
+                if args.mesh_render_check:
+                    figures = TS.surface_agreement(volume, kfs_all, Kt, args.rows, args.cols, args.mesh_render_step, mesh["min_weight"])
+                    run = TS.agreement_summary(figures)
+                    print(f"rank {rank}: mesh render check: {len(figures)} keyframes, {run['pixels']} pixels, median of medians {run['median']:.6f} m, "
+                          f"largest 90 % {run['p90']:.6f} m")
+                if args.mesh_render:
+                    from rgbid import render as RD
+                    os.makedirs(args.mesh_render, exist_ok=True)
+                    for a in range(0, len(kfs_all), volume.max_views):
+                        kfs = kfs_all[a:a + volume.max_views]
+                        views = volume.raycast(np.stack([k["R"] for k in kfs]), np.stack([k["t"] for k in kfs]), Kt, args.rows, args.cols,
+                                               args.mesh_render_step, mesh["min_weight"])
+                        for j in range(len(kfs)):
+                            name = f"view_{a + j:04d}" if world == 1 else f"view_rank{rank}_{a + j:04d}"
+                            tum.write_png(os.path.join(args.mesh_render, name + ".png"), views["colour"][j].cpu().numpy())
+                            tum.write_png(os.path.join(args.mesh_render, name + "_depth.png"), RD.depth_png(views["depth"][j]))
+                            tum.write_png(os.path.join(args.mesh_render, name + "_shaded.png"), TS.shade(views["normal"][j]))
+                    print(f"rank {rank}: {len(kfs_all)} ray-cast views of the volume -> {args.mesh_render}")
+            finally:
+                volume.close()
     if comm is not None:
         comm.close()
     if rank == 0:
