@@ -88,6 +88,21 @@ int rgbid_lattice_residuals_batched(rgbid_ctx*, int lanes, const rgbid_imgb* Wcu
                                     const rgbid_imgb* I0, const float* R_proj, const float* t_proj, int min_nsamples, int numerics,
                                     const float* kf_lat_dev, size_t kf_lat_lane_stride, float* res_dev, size_t res_lane_stride,
                                     float* ms);
+/* the same residuals with a lane mask and, optionally, the current frame's samples taken from the RAW input frame that Wcur / Icur were converted from by
+ * rgbid_prep_frame_batched (u16 depth + rgb24, converted in registers: what the engine's level-0 lattice runs).  depth_u16 / rgb_u8x3: both NULL = the fp32
+ * maps; otherwise every lane's image must start on a 4-byte boundary (RGBID_E_INVALID if not: the call never takes the other source on its own).
+ * kf_lat_dev is required.  lane_on_dev (nullable, device, [lanes]): lanes whose flag is not 1 are left untouched.  The residuals are bit-identical
+ * to rgbid_lattice_residuals_batched's. */
+int rgbid_lattice_residuals_raw_batched(rgbid_ctx*, int lanes, const rgbid_imgb* Wcur, const rgbid_imgb* W0, const rgbid_imgb* Icur,
+                                        const rgbid_imgb* I0, const float* R_proj, const float* t_proj, int min_nsamples, int numerics,
+                                        const float* kf_lat_dev, size_t kf_lat_lane_stride, float* res_dev, size_t res_lane_stride,
+                                        const rgbid_imgb* depth_u16, const rgbid_imgb* rgb_u8x3, float factor_depth, const int* lane_on_dev,
+                                        float* ms);
+/* every pixel of a raw frame through the accessors of that raw source: depthinv <- the point sample, intensity_pair <- the tap-pair load (the last column
+ * as the second texel of the last pair), intensity_single <- the single-texel tap.  All three must equal rgbid_prep_frame_batched's maps bit for bit.
+ * rows <= 65535. */
+int rgbid_frame_px_batched(rgbid_ctx*, int lanes, const rgbid_imgb* depth_u16, const rgbid_imgb* rgb_u8x3, const rgbid_imgb* depthinv,
+                           const rgbid_imgb* intensity_pair, const rgbid_imgb* intensity_single, float factor_depth, float* ms);
 /* computeSigmaAndNuStudent (:858-1066) of both channels of every lane from res_dev[lane][2][n], with the start values the tracker sets
  * before every iteration (bias 0, sigma 0.0025 / 5, nu 5; src/visodo.cpp:1168-1173); out (host) [lanes] */
 typedef struct rgbid_scale_pair { float bias_depthinv, sigma_depthinv, nu_depthinv, bias_int, sigma_int, nu_int; } rgbid_scale_pair;

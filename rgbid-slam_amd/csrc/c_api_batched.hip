@@ -231,6 +231,48 @@ int rgbid_lattice_residuals_batched(rgbid_ctx* c, int lanes, const rgbid_imgb* W
   return call.finish();
 }
 
+int rgbid_lattice_residuals_raw_batched(rgbid_ctx* c, int lanes, const rgbid_imgb* Wcur, const rgbid_imgb* W0, const rgbid_imgb* Icur, const rgbid_imgb* I0,
+                                        const float* R, const float* t, int min_nsamples, int numerics, const float* kf_lat_dev, size_t kf_lat_lane_stride,
+                                        float* res_dev, size_t res_lane_stride, const rgbid_imgb* depth, const rgbid_imgb* rgb, float factor_depth,
+                                        const int* lane_on_dev, float* ms) {
+  const rgbid_imgb* all[4] = {Wcur, W0, Icur, I0};
+  if (!c || lanes < 1 || !R || !t || !res_dev || !kf_lat_dev || !numerics_ok(numerics) || (depth == nullptr) != (rgb == nullptr)) return RGBID_E_INVALID;
+  for (int i = 0; i < 4; ++i) if (!ok_b(all[i], lanes) || !same_b(all[i], W0)) return RGBID_E_INVALID;
+  const int n = lattice_samples(W0->rows, W0->cols, min_nsamples);
+  if (res_lane_stride < 2 * (size_t)n || kf_lat_lane_stride < 2 * (size_t)n) return RGBID_E_INVALID;
+  const bool fast = numerics == RGBID_NUMERICS_FAST;
+  if (fast && !(W0->cols % 4 == 0 && W0->cols >= 4 && W0->rows >= 2 && al16(W0, lanes) && al16(I0, lanes) && W0->step == I0->step)) return RGBID_E_INVALID;
+  RawFrame raw{};
+  if (depth) {
+    if (!ok_b(depth, lanes, 2) || !ok_b(rgb, lanes, 3) || !same_b(depth, W0) || !same_b(rgb, W0)) return RGBID_E_INVALID;
+    raw = RawFrame{BB(depth, lanes), BB(rgb, lanes), factor_depth};
+    if (!lattice_raw_supported(raw, BB(W0, lanes), lanes)) return RGBID_E_INVALID;   // a frame the raw source cannot read is an error here, never the other path
+  }
+  hipSetDevice(c->device);
+  int e = ctx_reserve_lane(c, sizeof(WarpParams) * lanes);
+  if (e) return e;
+  if ((e = staging_free(c))) return e;
+  if ((e = stage_warps(c, lanes, R, t, 0))) return e;
+  if ((e = staging_sent(c))) return e;
+  Call call(c, ms);
+  launch_lattice_residuals_fused(c->stream, lanes, BB(Wcur, lanes), BB(W0, lanes), BB(Icur, lanes), BB(I0, lanes), reinterpret_cast<const WarpParams*>(c->lane_dev),
+                                 c->interp_mode, min_nsamples, LaneMask{lane_on_dev, 1}, fast, res_dev, res_lane_stride, kf_lat_dev, kf_lat_lane_stride, depth ? &raw : nullptr);
+  return call.finish();
+}
+
+int rgbid_frame_px_batched(rgbid_ctx* c, int lanes, const rgbid_imgb* depth, const rgbid_imgb* rgb, const rgbid_imgb* iD, const rgbid_imgb* I_pair,
+                           const rgbid_imgb* I_single, float factor_depth, float* ms) {
+  const rgbid_imgb* all[5] = {depth, rgb, iD, I_pair, I_single};
+  if (!c || lanes < 1) return RGBID_E_INVALID;
+  for (int i = 0; i < 5; ++i) if (!ok_b(all[i], lanes, i == 0 ? 2 : i == 1 ? 3 : 4) || !same_b(all[i], iD)) return RGBID_E_INVALID;
+  const RawFrame raw{BB(depth, lanes), BB(rgb, lanes), factor_depth};
+  if (iD->rows > 65535 || !lattice_raw_supported(raw, BB(iD, lanes), lanes)) return RGBID_E_INVALID;
+  hipSetDevice(c->device);
+  Call call(c, ms);
+  launch_frame_px(c->stream, lanes, raw, BB(iD, lanes), BB(I_pair, lanes), BB(I_single, lanes), ALL);
+  return call.finish();
+}
+
 int rgbid_sigma_pair_batched(rgbid_ctx* c, int lanes, const float* res_dev, size_t res_lane_stride, int n, int mestimator, rgbid_scale_pair* out, float* ms) {
   if (!c || lanes < 1 || !res_dev || n < 1 || res_lane_stride < 2 * (size_t)n || !out || mestimator < RGBID_LSQ || mestimator > RGBID_STUDENT) return RGBID_E_INVALID;
   hipSetDevice(c->device);

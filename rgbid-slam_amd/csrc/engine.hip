@@ -219,6 +219,12 @@ inline int update_prologue_max_lanes() {
   const char* e = getenv("RGBID_ENGINE_UPDATE_PROLOGUE_LANES");   // read when a step is enqueued / captured (tests and A/B runs switch it per engine)
   return e ? atoi(e) : 8;
 }
+// level-0 residual lattice gathered from the step's raw input frame (u16 depth + rgb24, converted in registers: kernels_sigma.hip k_lattice_residuals_fused<true>)
+// instead of the two fp32 maps converted from it -- bit-identical residuals, fewer 64-byte sectors.  RGBID_ENGINE_LATTICE_RAW=0 keeps the fp32 maps.
+inline bool lattice_raw_enabled() {
+  const char* e = getenv("RGBID_ENGINE_LATTICE_RAW");   // read when a step is enqueued / captured (tests and A/B runs switch it per engine)
+  return !(e && atoi(e) == 0);
+}
 // workgroup size of the per-lane reduce-and-solve kernels (engine_device.h reduce_partials): one wave per lane once there are more lanes than compute units
 inline int scalar_block_threads(int B) { return B > 256 ? 64 : 256; }
 
@@ -772,6 +778,12 @@ int enqueue_step(rgbid_engine* e, hipStream_t s, bool first) {
     // rgbid_engine_create ("e->cfg.fused_gn = 0") has taken both WARP_FIRST and CHI_SQUARED termination out of the fused path
     assert(!(c.fused_gn && (warp_first || chi_stop)));
     const bool prologue_plan = c.fused_gn && pdf && e->lat_res && B <= update_prologue_max_lanes();
+    // Level 0's current maps are per-pixel conversions of this step's input frame (launch_prep_frame above) unless the custom registration resamples them, and the
+    // frame stays readable for the whole step (k_save_integr_kf reads cur_rgb at its end; graph mode: the staging copies): the FAST class's level-0 lattice
+    // gathers from the frame itself.  Lanes that were not fed this step hold a stale slice of the frame, but k_step_begin clears f.gn (== f.lvl on the fused
+    // path) for them, so no such lane is in LV.  The few-lane plan's launches carry their own lattice code and keep the fp32 maps, as does everything else.
+    const RawFrame raw0{e->cur_depth, e->cur_rgb, c.factor_depth};
+    const bool lattice_raw = lattice_raw_enabled() && !custom && !prologue_plan && fast_at(0) && lattice_raw_supported(raw0, e->iD_kf[0], B);
     struct { bool on; int nblk, sys_level, sys_cov; } pend = {false, 0, -1, 0};
     int pose_in_alt = 0;   // which of the lane's two pose buffers holds the working pose (0: cur_*)
     int nblk;
@@ -794,9 +806,12 @@ int enqueue_step(rgbid_engine* e, hipStream_t s, bool first) {
             pose_in_alt ^= 1; pend.on = false;
           } else {
             launch_sigma_pair_fused(s, B, e->iD_curr[level], e->iD_kf[level], e->I_curr[level], e->I_kf[level], e->wp, c.interp_mode, c.nsamples,
-                                    e->sp, c.mestimator, LV, fast_at(level), e->lat_res, 2 * e->lat_cap, e->lat_kf[level], 2 * e->lat_cap);
+                                    e->sp, c.mestimator, LV, fast_at(level), e->lat_res, 2 * e->lat_cap, e->lat_kf[level], 2 * e->lat_cap,
+                                    level == 0 && lattice_raw ? &raw0 : nullptr);
           }
-          led.add(2, 0, 44 * ns);   // residual lattice: 36 B/sample (packed keyframe side 8, gathers 20, residuals written 8) + 8 read by the sigma / nu kernel
+          // residual lattice: 36 B/sample (packed keyframe side 8, gathers 20, residuals written 8) + 8 read by the sigma / nu kernel.  The byte model books the
+          // REFERENCE unit (fp32 maps) whichever source the level-0 gathers take: the raw frame's 2 + 4 x 3 bytes are the same samples in a smaller encoding
+          led.add(2, 0, 44 * ns);
         }
         system_events(level);
         nblk = launch_gn_fused(s, B, e->iD_kf[level], e->I_kf[level], e->gxD[level], e->gyD[level], e->gxI[level], e->gyI[level],

@@ -82,6 +82,8 @@ bool launch_kf_maps(hipStream_t s, int B, ImgB depthinv, ImgB vmap, ImgB nmap, I
 void launch_generate_image(hipStream_t s, int B, ImgB vmap, ImgB nmap, ImgB rgb, ImgB dst, const LightP* host_l, const LightP* lane_l, LaneMask m);
 
 // ---- residual lattice + sigma/nu (kernels_sigma.hip) --------------------------------------------
+// the raw input frame of an engine step (u16 depth, rgb24) and the depth factor of its conversion into the level-0 maps (launch_prep_frame)
+struct RawFrame { ImgB depth, rgb; float factor_depth; };
 void lattice_geometry(int rows, int cols, int min_nsamples, int* n, int* lrows, int* lcols, int* stride);
 void launch_error_lattice(hipStream_t s, int B, ImgB im1, ImgB im0, float* err, size_t err_lane_stride, int lrows, int lcols, int stride, LaneMask m);
 // mode 0: computeSigmaAndNuStudent, 1: computeNuStudent, 2: computeSigmaPdf.  io: device [B]
@@ -91,10 +93,16 @@ void launch_sigma_pair(hipStream_t s, int B, ImgB W1, ImgB W0, ImgB I1, ImgB I0,
 // same, but W1 / I1 are produced on the fly from the current frame (fused engine path: they are never stored)
 void launch_sigma_pair_fused(hipStream_t s, int B, ImgB Wcur, ImgB W0, ImgB Icur, ImgB I0, const WarpParams* lane_wp, int interp_mode,
                              int min_nsamples, SysParams* sp, int mestimator, LaneMask m, bool fast = false, float* res = nullptr, size_t res_lane_stride = 0,
-                             const float* kf_lat = nullptr, size_t kf_lat_lane_stride = 0);
+                             const float* kf_lat = nullptr, size_t kf_lat_lane_stride = 0, const RawFrame* raw = nullptr);
 // the two halves of launch_sigma_pair_fused on their own (C-ABI rgbid_lattice_residuals_batched / rgbid_sigma_pair_batched)
+// raw (nullable): the input frame Wcur / Icur were converted from by launch_prep_frame -- the current frame's samples are then gathered from it and
+// converted in registers (bit-identical residuals, fewer 64-byte sectors touched); it must pass lattice_raw_supported
 void launch_lattice_residuals_fused(hipStream_t s, int B, ImgB Wcur, ImgB W0, ImgB Icur, ImgB I0, const WarpParams* lane_wp, int interp_mode, int min_nsamples,
-                                    LaneMask m, bool fast, float* res, size_t res_lane_stride, const float* kf_lat, size_t kf_lat_lane_stride);
+                                    LaneMask m, bool fast, float* res, size_t res_lane_stride, const float* kf_lat, size_t kf_lat_lane_stride,
+                                    const RawFrame* raw = nullptr);
+bool lattice_raw_supported(const RawFrame& raw, const ImgB& W0, int B);
+// every pixel of a raw frame through the raw lattice's accessors (the conversion's parity check against launch_prep_frame); rows <= 65535
+void launch_frame_px(hipStream_t s, int B, const RawFrame& f, ImgB iD, ImgB I_pair, ImgB I_single, LaneMask m);
 void launch_sigma_pair_arrays(hipStream_t s, int B, const float* res, size_t res_lane_stride, int n, SysParams* sp, int mestimator, LaneMask m);
 // the keyframe side of a level's residual lattice packed as [lane][2][n] = W0 | I0 (once per keyframe; see k_lattice_residuals_fused)
 void launch_lattice_pack(hipStream_t s, int B, ImgB W0, ImgB I0, int min_nsamples, float* out, size_t out_lane_stride, LaneMask m);

@@ -147,9 +147,12 @@ void launch_sigma_pair(hipStream_t s, int B, ImgB W1, ImgB W0, ImgB I1, ImgB I0,
 // kf_lat (nullable): the keyframe side of the lattice, packed once per keyframe by k_lattice_pack -- [lane][2][n] = W0 | I0 at the lattice
 // points.  The lattice takes every stride-th pixel of every stride-th row, i.e. a quarter of the cache lines of each map it samples at
 // level 0; the two keyframe maps do not change between keyframes, so their samples are read here as two coalesced arrays instead.
+// RAW: the current frame's samples come from the input frame the level-0 maps were converted from (2 + 3 B/px instead of 4 + 4: fewer sectors under the
+// same footprint; warp_device.h frame_px), the keyframe side from kf_lat (required).  Projection, guard bands and the residual layout are the same code.
+template <bool RAW>
 __global__ __launch_bounds__(256) void k_lattice_residuals_fused(ImgB Wcur, ImgB W0, ImgB Icur, ImgB I0, const WarpParams* wp, int interp_mode, int n, int lcols,
                                                                  int stride, float* res, size_t res_lane_stride, const float* kf_lat, size_t kf_lat_lane_stride,
-                                                                 LaneMask m, int fast) {
+                                                                 LaneMask m, int fast, RawFrame raw) {
   const int lane = blockIdx.y;
   if (!m.on(lane)) return;
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -157,7 +160,10 @@ __global__ __launch_bounds__(256) void k_lattice_residuals_fused(ImgB Wcur, ImgB
   FusedLatticeGetter g{Wcur, Icur, W0, I0, wp[lane], lane, stride, interp_mode, fast};
   const int ly = i / lcols, lx = i - ly * lcols;
   float rd, ri;
-  if (kf_lat) {
+  if (RAW) {
+    const float* k = kf_lat + (size_t)lane * kf_lat_lane_stride;
+    g.both_given_raw(raw, ly, lx, k[i], k[n + i], rd, ri);
+  } else if (kf_lat) {
     const float* k = kf_lat + (size_t)lane * kf_lat_lane_stride;
     g.both_given(ly, lx, k[i], k[n + i], rd, ri);
   } else {
@@ -219,12 +225,22 @@ int lattice_samples(int rows, int cols, int min_nsamples) {
 
 // the lattice pre-pass of the fused path alone: both channels' residuals of every lattice sample into res[lane][2][n].  `fast` is the RESOLVED
 // numerics class of the level (kernels.h gn_fast_supported): the caller decides it once for the lattice and the normal equations.
+bool lattice_raw_supported(const RawFrame& raw, const ImgB& W0, int B) {
+  return raw.factor_depth == raw.factor_depth && raw.factor_depth != 0.f && raw.depth.rows == W0.rows && raw.depth.cols == W0.cols && raw_frame_ok(raw.depth, raw.rgb, B);
+}
 void launch_lattice_residuals_fused(hipStream_t s, int B, ImgB Wcur, ImgB W0, ImgB Icur, ImgB I0, const WarpParams* lane_wp, int interp_mode, int min_nsamples,
-                                    LaneMask m, bool fast, float* res, size_t res_lane_stride, const float* kf_lat, size_t kf_lat_lane_stride) {
+                                    LaneMask m, bool fast, float* res, size_t res_lane_stride, const float* kf_lat, size_t kf_lat_lane_stride,
+                                    const RawFrame* raw) {
   int n, lr, lc, st;
   lattice_geometry(W0.rows, W0.cols, min_nsamples, &n, &lr, &lc, &st);
-  hipLaunchKernelGGL(k_lattice_residuals_fused, dim3(div_up(n, 256), B), dim3(256), 0, s, Wcur, W0, Icur, I0, lane_wp, interp_mode, n, lc, st, res, res_lane_stride,
-                     kf_lat_lane_stride >= 2 * (size_t)n ? kf_lat : nullptr, kf_lat_lane_stride, m, fast ? 1 : 0);
+  const float* kf = kf_lat_lane_stride >= 2 * (size_t)n ? kf_lat : nullptr;
+  // the raw source needs the packed keyframe side (the engine always has it) and a frame of the lattice's geometry on 4-byte lane boundaries
+  if (raw && kf && lattice_raw_supported(*raw, W0, B))
+    hipLaunchKernelGGL((k_lattice_residuals_fused<true>), dim3(div_up(n, 256), B), dim3(256), 0, s, Wcur, W0, Icur, I0, lane_wp, interp_mode, n, lc, st, res, res_lane_stride,
+                       kf, kf_lat_lane_stride, m, fast ? 1 : 0, *raw);
+  else
+    hipLaunchKernelGGL((k_lattice_residuals_fused<false>), dim3(div_up(n, 256), B), dim3(256), 0, s, Wcur, W0, Icur, I0, lane_wp, interp_mode, n, lc, st, res, res_lane_stride,
+                       kf, kf_lat_lane_stride, m, fast ? 1 : 0, RawFrame{});
 }
 // computeSigmaAndNuStudent of both channels on res[lane][2][n] (start values of visodo.cpp:1168-1173), results into sp[lane]
 void launch_sigma_pair_arrays(hipStream_t s, int B, const float* res, size_t res_lane_stride, int n, SysParams* sp, int mestimator, LaneMask m) {
@@ -235,10 +251,29 @@ void launch_sigma_pair_arrays(hipStream_t s, int B, const float* res, size_t res
 }
 void launch_sigma_pair_fused(hipStream_t s, int B, ImgB Wcur, ImgB W0, ImgB Icur, ImgB I0, const WarpParams* lane_wp, int interp_mode,
                              int min_nsamples, SysParams* sp, int mestimator, LaneMask m, bool fast, float* res, size_t res_lane_stride,
-                             const float* kf_lat, size_t kf_lat_lane_stride) {
+                             const float* kf_lat, size_t kf_lat_lane_stride, const RawFrame* raw) {
   // res: [lane][2][n] scratch of at least 2 * lattice_samples() floats per lane (the engine sizes it at creation)
-  launch_lattice_residuals_fused(s, B, Wcur, W0, Icur, I0, lane_wp, interp_mode, min_nsamples, m, fast, res, res_lane_stride, kf_lat, kf_lat_lane_stride);
+  launch_lattice_residuals_fused(s, B, Wcur, W0, Icur, I0, lane_wp, interp_mode, min_nsamples, m, fast, res, res_lane_stride, kf_lat, kf_lat_lane_stride, raw);
   launch_sigma_pair_arrays(s, B, res, res_lane_stride, lattice_samples(W0.rows, W0.cols, min_nsamples), sp, mestimator, m);
+}
+
+// ---- the raw-frame sources on their own (C-ABI rgbid_frame_px_batched): every pixel of a frame through the accessors the raw lattice uses -- the point
+// sample, the 12-byte tap-pair window (its moved-back form at the end of the image included) and the single-texel taps of the cold paths
+__global__ __launch_bounds__(256) void k_frame_px(RawFrame f, ImgB iD, ImgB I_pair, ImgB I_single, LaneMask m) {
+  const int lane = blockIdx.z;
+  if (!m.on(lane)) return;
+  const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+  if (x >= iD.cols) return;
+  const DepthMapU16 D(f.depth, lane, f.factor_depth);
+  const LumaMapRgb L(f.rgb, lane);
+  px<float>(iD, lane, y, x) = D.at(y, x);
+  const bool last = x == iD.cols - 1;   // the last column is the second texel of the last pair
+  const float2 p = L.at2_raw(L.tap_off(y, last ? x - 1 : x), 0u);
+  px<float>(I_pair, lane, y, x) = last ? p.y : p.x;
+  px<float>(I_single, lane, y, x) = L.at_off(L.row(y), x);
+}
+void launch_frame_px(hipStream_t s, int B, const RawFrame& f, ImgB iD, ImgB I_pair, ImgB I_single, LaneMask m) {
+  hipLaunchKernelGGL(k_frame_px, dim3(div_up(iD.cols, 256), iD.rows, B), dim3(256), 0, s, f, iD, I_pair, I_single, m);
 }
 
 // ---- computeChiSquare sigmaFuncs.cu:1225-1297 (+ :137-150, :541-646) --------------------------------

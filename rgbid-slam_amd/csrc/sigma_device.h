@@ -359,6 +359,25 @@ struct ArrayGetter {
   __device__ __forceinline__ void step() { RGBID_FP_STRICT pos += SIG_T; }
 };
 
+// both channels' residuals of the lattice sample at pixel (x, y) against the keyframe values (w0, i0v); D / I: the current frame's inverse-depth and
+// intensity maps -- two FMaps, or the raw input frame converted on the fly (warp_device.h DepthMapU16 / LumaMapRgb: level 0 of the engine)
+template <class DMAP, class IMAP>
+__device__ __forceinline__ void lattice_residual_pair(const DMAP& D, const IMAP& I, const WarpParams& P, int x, int y, int interp_mode, int fast, float w0, float i0v,
+                                                      float& rd, float& ri) { RGBID_FP_STRICT
+  float w1, i1;
+  if (fast) {
+    // the same functions of the pixel as the normal-equation kernel that follows: identical W1 / I1, identical selection
+    const fastnum::Guard G = fastnum::lane_guard(P, D.cols, D.rows);
+    const fastnum::Ray r = fastnum::ray(P, (float)x, (float)y);
+    w1 = fastnum::warp_invdepth_px(D, r, x, y, w0, P, G);
+    i1 = fastnum::warp_intensity_px(I, r, x, y, w1, P, G, interp_mode);
+  } else {
+    w1 = warp_invdepth_px(D, x, y, w0, P);
+    i1 = warp_intensity_px(I, x, y, w1, P, interp_mode);
+  }
+  rd = w1 - w0; ri = i1 - i0v;
+}
+
 // fused engine path: the lattice residuals are warped on the fly (W1, I1 are never materialised)
 struct FusedLatticeGetter {
   ImgB cur_iD, cur_I, W0, I0;
@@ -370,19 +389,11 @@ struct FusedLatticeGetter {
     both_given(ly, lx, px<float>(W0, lane, ly * stride, lx * stride), px<float>(I0, lane, ly * stride, lx * stride), rd, ri);
   }
   __device__ __forceinline__ void both_given(int ly, int lx, float w0, float i0v, float& rd, float& ri) const { RGBID_FP_STRICT
-    int y = ly * stride, x = lx * stride;
-    float w1, i1;
-    if (fast) {
-      // the same functions of the pixel as the normal-equation kernel that follows: identical W1 / I1, identical selection
-      const fastnum::Guard G = fastnum::lane_guard(P, cur_iD.cols, cur_iD.rows);
-      const fastnum::Ray r = fastnum::ray(P, (float)x, (float)y);
-      w1 = fastnum::warp_invdepth_px(FMap(cur_iD, lane), r, x, y, w0, P, G);
-      i1 = fastnum::warp_intensity_px(FMap(cur_I, lane), r, x, y, w1, P, G, interp_mode);
-    } else {
-      w1 = warp_invdepth_px(FMap(cur_iD, lane), x, y, w0, P);
-      i1 = warp_intensity_px(FMap(cur_I, lane), x, y, w1, P, interp_mode);
-    }
-    rd = w1 - w0; ri = i1 - i0v;
+    lattice_residual_pair(FMap(cur_iD, lane), FMap(cur_I, lane), P, lx * stride, ly * stride, interp_mode, fast, w0, i0v, rd, ri);
+  }
+  // the same sample with the current frame's two maps taken from the raw input frame they were converted from (level 0; the caller holds the keyframe side)
+  __device__ __forceinline__ void both_given_raw(const RawFrame& f, int ly, int lx, float w0, float i0v, float& rd, float& ri) const { RGBID_FP_STRICT
+    lattice_residual_pair(DepthMapU16(f.depth, lane, f.factor_depth), LumaMapRgb(f.rgb, lane), P, lx * stride, ly * stride, interp_mode, fast, w0, i0v, rd, ri);
   }
 };
 

@@ -43,6 +43,7 @@ struct FMap {
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, row_b + ((unsigned)x << 2), 0, 0));
   }
   __device__ __forceinline__ float at(int y, int x) const { return at_off(row(y), x); }
+  __device__ __forceinline__ unsigned tap_off(int y, int x) const { return row(y) + ((unsigned)x << 2); }     // byte offset of texel (y, x): what at2_raw takes
   // two horizontally adjacent texels (x, x + 1) in ONE 8-byte load: the texture addresser handles 4 lanes per clock whatever the access
   // width, so a gather kernel's time is its number of vector-memory instructions, not its bytes (x + 1 must be a valid column)
   __device__ __forceinline__ float2 at2_off(unsigned row_b, int x) const {
@@ -73,9 +74,93 @@ struct FMapW {
   }
 };
 
+// ---- the level-0 current-frame maps read straight from the step's input frame ------------------------------------------------------------
+// The engine's level-0 inverse depth and intensity are per-pixel functions of the u16 depth and the rgb24 image (k_prep_frame4, kernels_prep.hip).  A
+// gather kernel that is bound by the 64-byte sectors it touches moves fewer of them when it gathers the 2 + 3 B/px input and converts in registers than
+// when it gathers the two fp32 maps.  frame_px IS that conversion: the operations k_prep_frame4 performs, one rounding each, in its order (the exhaustive
+// test in tests/test_gpu_lattice_raw.py holds it to launch_prep_frame bit for bit over every depth and every colour).
+struct FramePx { float iD, I; };
+// Every operation below is a plain operator under `fp contract(off)`: one IEEE operation, one rounding each, never fused (the division is hipcc's correctly
+// rounded one).  The __fmul_rn / __fadd_rn spellings are NOT used: this toolchain defines them as plain operators in a header compiled with contraction
+// allowed, and once inlined their products and sums were fused into v_fmac_f32 (seen in the ISA, and caught by the exhaustive test).
+__device__ __forceinline__ float frame_depth_scale(float factor_depth) {
+#pragma clang fp contract(off)
+  return (1.f / factor_depth) * 1000.f;
+}
+__device__ __forceinline__ FramePx frame_px(unsigned d, unsigned r, unsigned g, unsigned b, float scale) {
+#pragma clang fp contract(off)
+  FramePx o;
+  o.iD = d > 0u ? scale / (float)min(d, 10000u) : qnan();   // depth 0 is invalid, depths above 10 m are clamped
+  const float pr = 0.2126f * (float)r, pg = 0.7152f * (float)g, pb = 0.0722f * (float)b;
+  const float s1 = pr + pg;
+  const float v = s1 + pb;
+  o.I = fmaxf(0.f, fminf(v, 255.f));
+  return o;
+}
+// the u16 depth image as an inverse-depth map: the FMap members the point-sampling warps use.  The descriptor ends with the last pixel (the caller's
+// buffer need not hold the padding of the last row); an offset outside it reads depth 0, i.e. NaN -- only pixels that are rejected anyway get there.
+struct DepthMapU16 {
+  int rows, cols;
+  __amdgpu_buffer_rsrc_t rsrc;
+  unsigned pitch_b;
+  float scale;
+  __device__ __forceinline__ DepthMapU16(const ImgB& im, int lane, float factor_depth)
+      : rows(im.rows), cols(im.cols),
+        rsrc(__builtin_amdgcn_make_buffer_rsrc(row_ptr<uint16_t>(im, lane, 0), 0, (int)((unsigned)(im.rows - 1) * (unsigned)im.pitch + 2u * (unsigned)im.cols), 0x00020000)),
+        pitch_b((unsigned)im.pitch), scale(frame_depth_scale(factor_depth)) {}
+  __device__ __forceinline__ unsigned row(int y) const { return __umul24((unsigned)y, pitch_b); }
+  __device__ __forceinline__ float at(int y, int x) const {
+    const unsigned d = __builtin_amdgcn_raw_buffer_load_b16(rsrc, row(y) + ((unsigned)x << 1), 0, 0);
+    return frame_px(d, 0u, 0u, 0u, scale).iD;
+  }
+};
+// the rgb24 image as an intensity map: the FMap members the bilinear warps use.  The 6 colour bytes of a tap pair sit at byte 3 x of the row, unaligned;
+// they are taken from ONE 12-byte load at the 4-byte boundary below them (the lane's image starts on one: rgb_map_ok), which always holds them -- the
+// addresser's cost is per instruction, not per byte.  At the end of the image the window is moved back so that it ends with the dword that holds the
+// last pixel: nothing past that dword is ever addressed.
+struct LumaMapRgb {
+  int rows, cols;
+  __amdgpu_buffer_rsrc_t rsrc;
+  unsigned pitch_b, last_win;   // last_win: byte offset of the last legal 12-byte window
+  typedef unsigned v3u __attribute__((ext_vector_type(3)));
+  __device__ __forceinline__ LumaMapRgb(const ImgB& im, int lane)
+      : rows(im.rows), cols(im.cols),
+        rsrc(__builtin_amdgcn_make_buffer_rsrc(row_ptr<uint8_t>(im, lane, 0), 0, (int)((((unsigned)(im.rows - 1) * (unsigned)im.pitch + 3u * (unsigned)im.cols) + 3u) & ~3u), 0x00020000)),
+        pitch_b((unsigned)im.pitch), last_win(((((unsigned)(im.rows - 1) * (unsigned)im.pitch + 3u * (unsigned)im.cols) + 3u) & ~3u) - 12u) {}
+  __device__ __forceinline__ unsigned row(int y) const { return __umul24((unsigned)y, pitch_b); }
+  __device__ __forceinline__ unsigned tap_off(int y, int x) const { return row(y) + __umul24((unsigned)x, 3u); }
+  // one texel (the exact functions' four separate taps: cold paths only)
+  __device__ __forceinline__ float at_off(unsigned row_b, int x) const {
+    const unsigned o = row_b + __umul24((unsigned)x, 3u);
+    const unsigned r = __builtin_amdgcn_raw_buffer_load_b8(rsrc, o, 0, 0), g = __builtin_amdgcn_raw_buffer_load_b8(rsrc, o + 1u, 0, 0),
+                   b = __builtin_amdgcn_raw_buffer_load_b8(rsrc, o + 2u, 0, 0);
+    return frame_px(0u, r, g, b, 0.f).I;
+  }
+  // texels (x, x + 1) of a row: byte offset voff + soff of texel x (x + 1 must be a valid column)
+  __device__ __forceinline__ float2 at2_raw(unsigned voff, unsigned soff) const {
+    const unsigned p = voff + soff;
+    const unsigned w = min(p & ~3u, last_win), o = p - w;   // o in [0, 3], up to 6 in the moved-back window
+    const v3u d = __builtin_bit_cast(v3u, __builtin_amdgcn_raw_buffer_load_b96(rsrc, w, 0, 0));
+    const bool up = o >= 4u;
+    const unsigned a = up ? d.y : d.x, b = up ? d.z : d.y, c = up ? 0u : d.z;
+    const unsigned lo = __builtin_amdgcn_alignbyte(b, a, o & 3u), hi = __builtin_amdgcn_alignbyte(c, b, o & 3u);   // bytes o .. o + 3 | o + 4 .. o + 7
+    return float2{frame_px(0u, lo & 255u, (lo >> 8) & 255u, (lo >> 16) & 255u, 0.f).I, frame_px(0u, lo >> 24, hi & 255u, (hi >> 8) & 255u, 0.f).I};
+  }
+};
+// host: the geometry LumaMapRgb / DepthMapU16 need -- every lane's image starts on a 4-byte (depth: 2-byte) boundary, 32-bit offsets, at least one window
+inline bool raw_frame_ok(const ImgB& depth, const ImgB& rgb, int B) {
+  const bool many = B > 1;
+  return depth.base && rgb.base && depth.rows == rgb.rows && depth.cols == rgb.cols && rgb.rows >= 2 && rgb.cols >= 2 &&
+         (((uintptr_t)rgb.base) & 3) == 0 && (!many || (rgb.lane_stride & 3) == 0) && (((uintptr_t)depth.base) & 1) == 0 && (depth.pitch & 1) == 0 &&
+         (!many || (depth.lane_stride & 1) == 0) && depth.pitch >= 2 * (size_t)depth.cols && rgb.pitch >= 3 * (size_t)rgb.cols &&
+         depth.pitch < ((size_t)1 << 24) && rgb.pitch < ((size_t)1 << 24) && (unsigned long long)rgb.rows * rgb.pitch < (1ull << 31) &&
+         (unsigned long long)depth.rows * depth.pitch < (1ull << 31);
+}
+
 // CUDA linear filtering at unnormalised coordinates with clamp addressing (what tex2D<float> computes for the
 // reference's cudaFilterModeLinear texture, warping_registration.cu:938-944); mode 1 = 1.8 fixed-point weights
-__device__ __forceinline__ float tex2d_linear(const FMap& src, float xs, float ys, int mode) {
+template <class MAP>
+__device__ __forceinline__ float tex2d_linear(const MAP& src, float xs, float ys, int mode) {
 #pragma clang fp contract(off)
   float xB = xs - 0.5f, yB = ys - 0.5f;
   float fx0 = floorf(xB), fy0 = floorf(yB);
@@ -97,8 +182,8 @@ __device__ __forceinline__ float tex2d_linear(const FMap& src, float xs, float y
 }
 
 // trafo3DKernelInvDepthGridStride, warping_registration.cu:505-546 (one pixel; w = keyframe inverse depth)
-template <class RCP>
-__device__ __forceinline__ float warp_invdepth_px_t(const FMap& src, int x, int y, float w, const WarpParams& P, RCP& rcp) {
+template <class RCP, class MAP>
+__device__ __forceinline__ float warp_invdepth_px_t(const MAP& src, int x, int y, float w, const WarpParams& P, RCP& rcp) {
 #pragma clang fp contract(off)
   const bool valid = !isnan(w);
   const float ws = valid ? w : 1.f;
@@ -113,7 +198,8 @@ __device__ __forceinline__ float warp_invdepth_px_t(const FMap& src, int x, int 
   float res = (v1_z / (1.f - w2 * tz)) * w2;
   return (valid & inb & (res > 0.f)) ? res : qnan();
 }
-__device__ __forceinline__ float warp_invdepth_px(const FMap& src, int x, int y, float w, const WarpParams& P) {
+template <class MAP>
+__device__ __forceinline__ float warp_invdepth_px(const MAP& src, int x, int y, float w, const WarpParams& P) {
   RcpFast f;
   float res = warp_invdepth_px_t(src, x, y, w, P, f);
   if (__builtin_expect(f.failed(), 0)) { RcpIeee s; res = warp_invdepth_px_t(src, x, y, w, P, s); }
@@ -145,8 +231,8 @@ __device__ __forceinline__ float warp_invdepth_weighted_px_t(const FMap& src, in
 }
 
 // trafo3DKernelIntensityWithInvDepthGridStride, warping_registration.cu:465-501 (one pixel; w = sampling-grid iD)
-template <class RCP>
-__device__ __forceinline__ float warp_intensity_px_t(const FMap& src, int x, int y, float w, const WarpParams& P, int interp_mode, RCP& rcp) {
+template <class RCP, class MAP>
+__device__ __forceinline__ float warp_intensity_px_t(const MAP& src, int x, int y, float w, const WarpParams& P, int interp_mode, RCP& rcp) {
 #pragma clang fp contract(off)
   const bool valid = !isnan(w);
   const float ws = valid ? w : 1.f;
@@ -158,7 +244,8 @@ __device__ __forceinline__ float warp_intensity_px_t(const FMap& src, int x, int
   res = fmaxf(0.f, fminf(res, 255.f));  // NaN -> 255, as CUDA's min/max
   return (valid & inb) ? res : qnan();
 }
-__device__ __forceinline__ float warp_intensity_px(const FMap& src, int x, int y, float w, const WarpParams& P, int interp_mode) {
+template <class MAP>
+__device__ __forceinline__ float warp_intensity_px(const MAP& src, int x, int y, float w, const WarpParams& P, int interp_mode) {
   RcpFast f;
   float res = warp_intensity_px_t(src, x, y, w, P, interp_mode, f);
   if (__builtin_expect(f.failed(), 0)) { RcpIeee s; res = warp_intensity_px_t(src, x, y, w, P, interp_mode, s); }
@@ -298,7 +385,8 @@ __device__ __forceinline__ float id_finish_m(const IdProj& r, float w2, const Wa
   return okd ? res : r.ws;
 }
 // the whole pixel for kernels with one pixel per thread (lattice pre-pass, scalar path of the normal equations)
-__device__ __forceinline__ float warp_invdepth_px(const FMap& src, const Ray& q, int x, int y, float w, const WarpParams& P, const Guard& G) {
+template <class MAP>
+__device__ __forceinline__ float warp_invdepth_px(const MAP& src, const Ray& q, int x, int y, float w, const WarpParams& P, const Guard& G) {
   bool fixc, fixr;
   IdProj r = id_project(q, w, P, G, src.cols, src.rows, fixc);
   if (__builtin_expect(fixc, 0)) id_fix_coords(r, x, y, P, src.cols, src.rows);
@@ -345,7 +433,8 @@ __device__ __forceinline__ float tex8_weight(float a) {
   return (a + 49152.f) - 49152.f;
 }
 // `valid_in`: what the caller already knows about w (true: nothing; the fused kernel passes the mask of its warped inverse depth)
-__device__ __forceinline__ IntensityTaps intensity_taps(const FMap& src, const Ray& q, float w, const WarpParams& P, const Guard& G, int interp_mode, bool& border, bool valid_in = true) {
+template <class MAP>
+__device__ __forceinline__ IntensityTaps intensity_taps(const MAP& src, const Ray& q, float w, const WarpParams& P, const Guard& G, int interp_mode, bool& border, bool valid_in = true) {
   IntensityTaps t;
   bool valid;
   const float ws = sanitised(w, valid);
@@ -361,12 +450,13 @@ __device__ __forceinline__ IntensityTaps intensity_taps(const FMap& src, const R
   border = valid & !core;
   t.a = __builtin_amdgcn_fractf(xc); t.b = __builtin_amdgcn_fractf(yc);   // v_fract_f32: x - floor(x), kept below 1
   if (interp_mode == 1) { t.a = tex8_weight(t.a); t.b = tex8_weight(t.b); }
-  const unsigned off = src.row(cvt_flr(yc)) + ((unsigned)cvt_flr(xc) << 2);
+  const unsigned off = src.tap_off(cvt_flr(yc), cvt_flr(xc));
   t.p0 = src.at2_raw(off, 0u); t.p1 = src.at2_raw(off, src.pitch_b);
   return t;
 }
 // cold path of a pixel whose projection is not in the core: safely inside (farther than the band from the border), surely outside, or the oracle's predicate
-__device__ __forceinline__ bool intensity_fix_border(const FMap& src, const Ray& q, int x, int y, float w, const WarpParams& P, const Guard& G) {
+template <class MAP>
+__device__ __forceinline__ bool intensity_fix_border(const MAP& src, const Ray& q, int x, int y, float w, const WarpParams& P, const Guard& G) {
 #pragma clang fp contract(off)
   const Scaled Y = scaled_point(q, w, P);
   const float wc = rcp(Y.y2);
@@ -399,7 +489,8 @@ __device__ __forceinline__ float intensity_finish_m(const IntensityTaps& t, bool
 }
 
 // trafo3DKernelIntensityWithInvDepthGridStride (:465-501), one pixel; bilinear tap in the lerp form
-__device__ __forceinline__ float warp_intensity_px(const FMap& src, const Ray& q, int x, int y, float w, const WarpParams& P, const Guard& G, int interp_mode) {
+template <class MAP>
+__device__ __forceinline__ float warp_intensity_px(const MAP& src, const Ray& q, int x, int y, float w, const WarpParams& P, const Guard& G, int interp_mode) {
   bool border, nan_tap;
   IntensityTaps t = intensity_taps(src, q, w, P, G, interp_mode, border);
   if (__builtin_expect(border, 0)) t.ok = intensity_fix_border(src, q, x, y, w, P, G);

@@ -19,7 +19,7 @@ BATCHED_EXPORTS = [
     "rgbid_gn_fused_batched", "rgbid_build_system_batched", "rgbid_warp_pair_batched", "rgbid_lattice_pack_batched",
     "rgbid_lattice_residuals_batched", "rgbid_sigma_pair_batched", "rgbid_fuse_frame_batched", "rgbid_kf_maps_batched",
     "rgbid_visibility_pair_batched", "rgbid_prep_frame_batched", "rgbid_pyr_down_batched", "rgbid_compute_gradient_batched",
-    "rgbid_bilateral_filter_batched", "rgbid_gradient_keep_batched",
+    "rgbid_bilateral_filter_batched", "rgbid_gradient_keep_batched", "rgbid_lattice_residuals_raw_batched", "rgbid_frame_px_batched",
 ]
 
 
@@ -119,6 +119,26 @@ class Batched:
                                                      int(bool(fast)), C.c_void_p(kf_lat.data_ptr()) if kf_lat is not None else None,
                                                      C.c_size_t(kf_lat.stride(0) if kf_lat is not None else 0), C.c_void_p(res.data_ptr()),
                                                      C.c_size_t(res.stride(0)), C.byref(ms)))
+        return ms.value
+
+    def lattice_residuals_raw(self, Wcur, W0, Icur, I0, R_proj, t_proj, min_nsamples, res, kf_lat, fast=True, depth_u16=None, rgb=None, factor_depth=1.0,
+                              lane_on=None):
+        """lattice_residuals with a lane mask (int32 CUDA tensor [lanes], 1 = on) and, when depth_u16 / rgb are given, the current frame's samples
+        gathered from that raw frame instead of Wcur / Icur"""
+        lanes = W0.shape[0]
+        Rk, Rp = _f32(R_proj, lanes, 9); tk, tp = _f32(t_proj, lanes, 3)
+        ms = C.c_float()
+        raw = [C.byref(imgb(depth_u16)), C.byref(imgb(rgb))] if depth_u16 is not None else [None, None]
+        check(self.L.rgbid_lattice_residuals_raw_batched(self._h, lanes, *[C.byref(imgb(t)) for t in (Wcur, W0, Icur, I0)], Rp, tp, int(min_nsamples),
+                                                         int(bool(fast)), C.c_void_p(kf_lat.data_ptr()), C.c_size_t(kf_lat.stride(0)),
+                                                         C.c_void_p(res.data_ptr()), C.c_size_t(res.stride(0)), *raw, C.c_float(factor_depth),
+                                                         C.c_void_p(lane_on.data_ptr()) if lane_on is not None else None, C.byref(ms)))
+        return ms.value
+
+    def frame_px(self, depth_u16, rgb, iD, I_pair, I_single, factor_depth=1.0):
+        ms = C.c_float()
+        check(self.L.rgbid_frame_px_batched(self._h, iD.shape[0], *[C.byref(imgb(t)) for t in (depth_u16, rgb, iD, I_pair, I_single)],
+                                            C.c_float(factor_depth), C.byref(ms)))
         return ms.value
 
     def sigma_pair(self, res, n, mestimator=3):

@@ -118,6 +118,8 @@ def main():
         kf_lat = f32(B, 2 * ns); res = f32(B, 2 * ns)
         bt.lattice_pack(W[0], I[0], 10000, kf_lat)
         timed("lattice_residuals FAST (packed KF)", lambda: bt.lattice_residuals(W[1], W[0], I[1], I[0], Rs, ts, 10000, res, fast=True, kf_lat=kf_lat), 36 * ns)
+        # the same samples gathered from the raw frame W[1] / I[1] were converted from (booked at the same 36 B/sample: the reference unit)
+        timed("lattice_residuals FAST (raw frame)", lambda: bt.lattice_residuals_raw(W[1], W[0], I[1], I[0], Rs, ts, 10000, res, kf_lat, fast=True, depth_u16=d16[1], rgb=rgb[1]), 36 * ns)
         if want("sigma"):
             L = bt.L; ms = __import__("ctypes").c_float()
 
