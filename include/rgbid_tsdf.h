@@ -47,7 +47,8 @@
  *     the row's first edge: the normal points from inside to outside.  The swap depends on (tetrahedron, case) only; it is one constant
  *     table of 6 x 16 entries (case = sum of 1 << u over the inside vertices u).  Zero-area triangles (D_b = 0) are kept.
  *
- * Steps 13 - 23 (the volume ray-cast into camera views, a normal per vertex) and their calls are in rgbid_tsdf_raycast.h, included below.
+ * Steps 13 - 23 (the volume ray-cast into camera views, a normal per vertex) and their calls are in rgbid_tsdf_raycast.h, steps 24 - 33
+ * (depth frames aligned to the volume) in rgbid_tsdf_align.h, both included below.
  */
 #ifndef RGBID_TSDF_H_
 #define RGBID_TSDF_H_
@@ -117,4 +118,6 @@ int rgbid_tsdf_timing(rgbid_tsdf* v, int enable, float ms[3]);
 
 /* steps 13 - 23 and their calls: the volume ray-cast into camera views, and a normal per mesh vertex */
 #include "rgbid_tsdf_raycast.h"
+/* steps 24 - 33 and their calls: depth frames aligned to the volume */
+#include "rgbid_tsdf_align.h"
 #endif

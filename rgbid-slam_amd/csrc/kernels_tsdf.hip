@@ -1,7 +1,9 @@
 // kernels_tsdf.hip -- keyframes fused into a truncated signed distance volume, the volume's surface as a triangle mesh with a normal per
-// vertex, and the volume ray-cast into camera views (include/rgbid_tsdf.h and rgbid_tsdf_raycast.h, DESIGN.md sections 19 and 20).
+// vertex, the volume ray-cast into camera views, and depth frames aligned to the volume (include/rgbid_tsdf.h, rgbid_tsdf_raycast.h and
+// rgbid_tsdf_align.h, DESIGN.md sections 19 - 21).
 //
-// The judges are tests/tsdf_mirror.py and tests/raycast_mirror.py; state, counts, mesh, normals and views are byte-identical to them.
+// The judges are tests/tsdf_mirror.py, tests/raycast_mirror.py and tests/align_mirror.py; state, counts, mesh, normals, views and
+// alignment results are byte-identical to them.
 //   integrate  view table       per view 64 bytes in device memory: the twelve floats of rgbid_render_pose_cw, the plane and the colour
 //                               pointer; written on the host into pinned memory and copied on the stream
 //              k_tsdf_integrate one thread per voxel, x fastest, grid-strided; up to RGBID_TSDF_VIEW_CHUNK views per launch in an inner
@@ -20,6 +22,12 @@
 //   ray cast   pose table       per view twelve floats of rgbid_tsdf_pose_wc, through the view table's pinned buffer
 //              k_tsdf_raycast   one thread per pixel, a wave per 8 x 8 pixel tile, blockIdx.y the view; two bisections per axis give the
 //                               ray its n range, the march tests the 8 counts of a sample first and loads the 8 D of a defined one
+//   align      view table       per view 104 bytes: the 12 pose doubles and the plane; k_tsdf_align_init makes the result records and the
+//                               float32 pose rows of them
+//              k_tsdf_align_system  per Gauss-Newton iteration: one thread per lattice pixel, a wave per 8 x 8 tile, blockIdx.y the view; the
+//                               ray cast's sampler, 28 doubles per pixel, summed over the wave by xor butterflies; one row per tile
+//              k_tsdf_align_solve   one block per view: the upper levels of the sum tree, the 6 x 6 solve, the pose update and the
+//                               float32 pose row of the next launch; every iteration of every level is enqueued without a host wait
 // No atomic touches the state and no result depends on the order of threads or waves.
 //
 // Exact arithmetic: RGBID_FP_STRICT (common.h) opens every function that forms a float32 product followed by a sum, so no FMA is formed
@@ -31,6 +39,7 @@
 
 #include <cmath>
 #include <new>
+#include <vector>
 
 using namespace rgbid;
 
@@ -466,6 +475,262 @@ __global__ __launch_bounds__(VT) void k_tsdf_raycast(TsdfGrid g, TsdfState st, R
   }
 }
 
+// ---- alignment (include/rgbid_tsdf_align.h) -------------------------------------------------------------------
+constexpr int ALIGN_TERMS = RGBID_TSDF_ALIGN_TERMS;
+
+struct AlignView {                // one row of the alignment's view table: 104 bytes
+  double pose[12];                // R00 .. R22 tx ty tz of R_WC | t_WC, as given
+  const float* plane;             // [rows][cols] inverse depth
+};
+static_assert(sizeof(AlignView) == 104, "twelve doubles and a pointer");
+static_assert(sizeof(rgbid_tsdf_align_result) == 560, "step 33");
+
+struct AlignCam {
+  RayCam ray;                     // fx fy cx cy, z_min, hi_i hi_j hi_k, min_weight, rows, cols: what ray_cell and the rays of step 14 read
+  float z_max, huber;
+  unsigned stride, lw, lh;        // the level's lattice
+  unsigned tiles_x, tiles;        // 8 x 8 lattice tiles per tile row and per view
+  unsigned restart;               // the first iteration of a later level: CONVERGED views run again
+};
+
+struct AlignWork {                // the handle's workspace
+  double* a;                      // [V][28][a_stride] tile sums, term-major, and the third round of the upper tree
+  double* b;                      // [V][28][b_stride] the second and fourth round
+  unsigned* used;                 // [V][a_stride] used pixels per tile
+  size_t a_stride, b_stride;
+  float* pose32;                  // [V][12] step 24's roundings: what the next system launch reads
+};
+
+struct AlignRule {
+  double damping, eps;
+  unsigned min_pixels, tiles;
+  unsigned restart;
+};
+
+__device__ __forceinline__ int align_status(const rgbid_tsdf_align_result* res, unsigned view, unsigned restart) {
+  const int s = res[view].status;
+  return s == RGBID_TSDF_ALIGN_CONVERGED && restart ? RGBID_TSDF_ALIGN_RUNNING : s;
+}
+
+// step 28's tree64 over the wave: every lane ends with the sum
+__device__ __forceinline__ double tree64(double v) {
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) v = v + __shfl_xor(v, m);
+  return v;
+}
+
+__global__ __launch_bounds__(VT) void k_tsdf_align_init(const AlignView* __restrict__ views, int V, rgbid_tsdf_align_result* __restrict__ res,
+                                                        float* __restrict__ pose32) {
+  const int v = blockIdx.x * VT + threadIdx.x;
+  if (v >= V) return;
+  rgbid_tsdf_align_result& r = res[v];
+  for (int k = 0; k < 12; ++k) {
+    r.pose[k] = views[v].pose[k];
+    pose32[12 * v + k] = (float)views[v].pose[k];
+  }
+  r.status = RGBID_TSDF_ALIGN_RUNNING;
+  r.iterations = 0;
+  r.used[0] = r.used[1] = 0u;
+  for (int k = 0; k < ALIGN_TERMS; ++k) r.sums[0][k] = r.sums[1][k] = 0.0;
+}
+
+// One thread per lattice pixel; a wave is an 8 x 8 lattice tile, a block four tiles of the view blockIdx.y: the ray cast's shape, so the
+// corner gathers of neighbouring pixels fall on neighbouring voxels.  The pose row and the status are wave-uniform.  Lanes outside the
+// lattice and pixels that are not used stay in the wave with +0.0: the butterflies need all 64.  No LDS, no atomic.
+__global__ __launch_bounds__(VT) void k_tsdf_align_system(TsdfGrid g, TsdfState st, AlignCam cam, const AlignView* __restrict__ views,
+                                                          const float* __restrict__ pose32, const rgbid_tsdf_align_result* __restrict__ res,
+                                                          double* __restrict__ sums, unsigned* __restrict__ used, size_t a_stride) {
+  RGBID_FP_STRICT
+  const unsigned view = blockIdx.y;
+  if (align_status(res, view, cam.restart) != RGBID_TSDF_ALIGN_RUNNING) return;   // a stopped view's blocks leave at once
+  const unsigned tile = blockIdx.x * (VT / 64) + (threadIdx.x >> 6);
+  if (tile >= cam.tiles) return;                                // the whole wave
+  const unsigned lane = threadIdx.x & 63u;
+  const unsigned lx = (tile % cam.tiles_x) * 8u + (lane & 7u), ly = (tile / cam.tiles_x) * 8u + (lane >> 3);
+  double tm[ALIGN_TERMS];
+#pragma unroll
+  for (int k = 0; k < ALIGN_TERMS; ++k) tm[k] = 0.0;
+  bool is_used = false;
+  if (lx < cam.lw && ly < cam.lh) {                             // ragged tiles
+    const unsigned pu = lx * cam.stride, pv = ly * cam.stride;  // step 25: inside the image, the lattice is ceil(cols / stride) wide
+    const float mi = views[view].plane[(size_t)pv * (size_t)cam.ray.cols + pu];
+    const float z = 1.f / mi;
+    if (mi > 0.f && mi < INFINITY && z >= cam.ray.z_min && z <= cam.z_max) {   // measured (NaN fails), and the gate: z_max is finite
+      const float* __restrict__ m = pose32 + 12u * view;
+      const float dx = ((float)pu - cam.ray.cx) / cam.ray.fx, dy = ((float)pv - cam.ray.cy) / cam.ray.fy;
+      const float xc = dx * z, yc = dy * z;
+      const float px = rot_row(m, xc, yc, z) + m[9], py = rot_row(m + 3, xc, yc, z) + m[10], pz = rot_row(m + 6, xc, yc, z) + m[11];
+      const float gx = (px - g.ox) / g.voxel, gy = (py - g.oy) / g.voxel, gz = (pz - g.oz) / g.voxel;
+      unsigned base;
+      float fx_, fy_, fz_;
+      if (ray_cell(g, st, cam.ray, gx, gy, gz, base, fx_, fy_, fz_)) {   // the 8 counts first; D only for a defined sample
+        const unsigned sy = g.nx, sz = g.nx * g.ny;
+        float d[8];
+#pragma unroll
+        for (unsigned c = 0; c < 8; ++c) d[c] = st.D[base + (c & 1u) + ((c >> 1) & 1u) * sy + (c >> 2) * sz];
+        const float lx00 = lerp_strict(d[0], d[1], fx_), lx10 = lerp_strict(d[2], d[3], fx_);
+        const float lx01 = lerp_strict(d[4], d[5], fx_), lx11 = lerp_strict(d[6], d[7], fx_);
+        const float ly0 = lerp_strict(lx00, lx10, fy_), ly1 = lerp_strict(lx01, lx11, fy_);
+        const float f = lerp_strict(ly0, ly1, fz_);
+        if (fabsf(f) < g.trunc) {
+          is_used = true;
+          float J[6];
+          J[0] = lerp_strict(lerp_strict(d[1] - d[0], d[3] - d[2], fy_), lerp_strict(d[5] - d[4], d[7] - d[6], fy_), fz_) / g.voxel;
+          J[1] = lerp_strict(lx10 - lx00, lx11 - lx01, fz_) / g.voxel;
+          J[2] = (ly1 - ly0) / g.voxel;
+          J[3] = py * J[2] - pz * J[1];
+          J[4] = pz * J[0] - px * J[2];
+          J[5] = px * J[1] - py * J[0];
+          const float af = fabsf(f);
+          const float w = af <= cam.huber ? 1.f : cam.huber / af;
+          double a[6], Jd[6];
+#pragma unroll
+          for (int i = 0; i < 6; ++i) { a[i] = (double)(w * J[i]); Jd[i] = (double)J[i]; }
+          const double fd = (double)f;
+          int k = 0;
+#pragma unroll
+          for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int j = i; j < 6; ++j) tm[k++] = a[i] * Jd[j];   // exact: 24 x 24 bits
+#pragma unroll
+          for (int i = 0; i < 6; ++i) tm[21 + i] = a[i] * fd;
+          tm[27] = (double)(w * f) * fd;
+        }
+      }
+    }
+  }
+  const unsigned n_used = (unsigned)__popcll(__ballot(is_used));
+#pragma unroll
+  for (int k = 0; k < ALIGN_TERMS; ++k) tm[k] = tree64(tm[k]);
+  if (lane == 0) {
+    double* o = sums + (size_t)view * ALIGN_TERMS * a_stride + tile;
+#pragma unroll
+    for (int k = 0; k < ALIGN_TERMS; ++k) o[(size_t)k * a_stride] = tm[k];
+    used[(size_t)view * a_stride + tile] = n_used;
+  }
+}
+
+// One block per view: the upper rounds of step 28 between the two buffers, then thread 0 walks steps 29 - 32 in double.
+__global__ __launch_bounds__(VT) void k_tsdf_align_solve(AlignWork w, AlignRule rule, rgbid_tsdf_align_result* res) {
+  RGBID_FP_STRICT
+  __shared__ unsigned lds[VT / 64];
+  const unsigned view = blockIdx.x;
+  if (align_status(res, view, rule.restart) != RGBID_TSDF_ALIGN_RUNNING) return;   // the whole block
+  const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  // the used pixels: an integer sum, the same in any order
+  unsigned cnt = 0;
+  for (unsigned i = threadIdx.x; i < rule.tiles; i += VT) cnt += w.used[(size_t)view * w.a_stride + i];
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) cnt += __shfl_xor(cnt, m);
+  if (lane == 0) lds[wave] = cnt;
+  double* src = w.a + (size_t)view * ALIGN_TERMS * w.a_stride;
+  double* dst = w.b + (size_t)view * ALIGN_TERMS * w.b_stride;
+  size_t src_stride = w.a_stride, dst_stride = w.b_stride;
+  unsigned n = rule.tiles;
+  while (n > 1u) {
+    const unsigned groups = (n + 63u) / 64u;
+    for (unsigned item = wave; item < groups * ALIGN_TERMS; item += VT / 64) {
+      const unsigned term = item / groups, grp = item % groups, i = grp * 64u + lane;
+      const double s = tree64(i < n ? src[(size_t)term * src_stride + i] : 0.0);
+      if (lane == 0) dst[(size_t)term * dst_stride + grp] = s;
+    }
+    __syncthreads();                                            // the round's sums are written before the next round reads them
+    double* p = src; src = dst; dst = p;
+    const size_t q = src_stride; src_stride = dst_stride; dst_stride = q;
+    n = groups;
+  }
+  __syncthreads();
+  rgbid_tsdf_align_result& r = res[view];
+  const bool first = r.iterations == 0;
+  if (threadIdx.x < ALIGN_TERMS) {                              // step 33: the first and the last system built
+    const double s = src[(size_t)threadIdx.x * src_stride];
+    r.sums[1][threadIdx.x] = s;
+    if (first) r.sums[0][threadIdx.x] = s;
+  }
+  if (threadIdx.x != 0) return;
+  static_assert(VT / 64 == 4, "four waves left their counts");
+  const unsigned n_used = lds[0] + lds[1] + lds[2] + lds[3];
+  r.used[1] = n_used;
+  if (first) r.used[0] = n_used;
+  r.iterations += 1;
+  if (n_used < rule.min_pixels) { r.status = RGBID_TSDF_ALIGN_FEW; return; }          // step 29
+  // step 30
+  double H[6][6], L[6][6], b[6], y[6], x[6];
+  {
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = i; j < 6; ++j) { H[i][j] = H[j][i] = src[(size_t)k * src_stride]; ++k; }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) b[i] = src[(size_t)(21 + i) * src_stride];
+  }
+  const double damp = 1.0 + rule.damping;
+#pragma unroll
+  for (int j = 0; j < 6; ++j) H[j][j] = H[j][j] * damp;
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    double s = H[j][j];
+#pragma unroll
+    for (int k = 0; k < j; ++k) s = s - L[j][k] * L[j][k];
+    if (!(s > 0.0 && s < (double)INFINITY)) ok = false;         // NaN fails; a later column of a failed one is never used
+    L[j][j] = sqrt(s);
+#pragma unroll
+    for (int i = j + 1; i < 6; ++i) {
+      double q = H[i][j];
+#pragma unroll
+      for (int k = 0; k < j; ++k) q = q - L[i][k] * L[j][k];
+      L[i][j] = q / L[j][j];
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    double s = -b[i];
+#pragma unroll
+    for (int k = 0; k < i; ++k) s = s - L[i][k] * y[k];
+    y[i] = s / L[i][i];
+  }
+#pragma unroll
+  for (int i = 5; i >= 0; --i) {
+    double s = y[i];
+#pragma unroll
+    for (int k = i + 1; k < 6; ++k) s = s - L[k][i] * x[k];
+    x[i] = s / L[i][i];
+  }
+  double biggest = 0.0;
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    const double ax = fabs(x[i]);
+    if (!(ax < (double)INFINITY)) ok = false;                   // NaN and infinity
+    biggest = ax > biggest ? ax : biggest;
+  }
+  if (!ok) { r.status = RGBID_TSDF_ALIGN_SINGULAR; return; }
+  // step 31
+  const double hx = x[3] / 2.0, hy = x[4] / 2.0, hz = x[5] / 2.0;
+  const double nn = sqrt(1.0 + ((hx * hx + hy * hy) + hz * hz));
+  const double qw = 1.0 / nn, qx = hx / nn, qy = hy / nn, qz = hz / nn;
+  const double xx = qx * qx, yy = qy * qy, zz = qz * qz, xy = qx * qy, xz = qx * qz, yz = qy * qz, wx = qw * qx, wy = qw * qy, wz = qw * qz;
+  const double dR[9] = {1.0 - 2.0 * (yy + zz), 2.0 * (xy - wz), 2.0 * (xz + wy),
+                        2.0 * (xy + wz), 1.0 - 2.0 * (xx + zz), 2.0 * (yz - wx),
+                        2.0 * (xz - wy), 2.0 * (yz + wx), 1.0 - 2.0 * (xx + yy)};
+  double P[12], Q[12];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) P[k] = r.pose[k];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) Q[3 * i + j] = (dR[3 * i] * P[j] + dR[3 * i + 1] * P[3 + j]) + dR[3 * i + 2] * P[6 + j];
+    Q[9 + i] = ((dR[3 * i] * P[9] + dR[3 * i + 1] * P[10]) + dR[3 * i + 2] * P[11]) + x[i];
+  }
+#pragma unroll
+  for (int k = 0; k < 12; ++k) {
+    r.pose[k] = Q[k];
+    w.pose32[12u * view + k] = (float)Q[k];                     // step 24, for the next launch
+  }
+  r.status = biggest < rule.eps ? RGBID_TSDF_ALIGN_CONVERGED : RGBID_TSDF_ALIGN_RUNNING;   // step 32
+}
+
 // triangles of one tile of RUN_TILE cells (a cell is the voxel of its corner 0) -> bc[tile]; total: all of them in 64 bits
 __global__ __launch_bounds__(VT) void k_tsdf_tri_count(const unsigned char* __restrict__ ntri, unsigned n, unsigned* __restrict__ bc,
                                                        unsigned long long* __restrict__ total) {
@@ -586,6 +851,16 @@ struct rgbid_tsdf {
   Buffers buf;
   StageTimer<8> timer;
   void mark(int i) { timer.mark(i, ctx->stream); }
+  // alignment (rgbid_tsdf_align): the view table on the first call, the workspace grown to the largest call.  A buffer that is outgrown
+  // stays with the handle until it is destroyed (a launch may still read it), and the next one is at least twice as large
+  AlignView* align_views = nullptr;            // [cap_views]
+  AlignView* align_views_host = nullptr;       // pinned
+  AlignWork aw{};
+  size_t aw_a = 0, aw_b = 0, aw_used = 0;      // capacities in elements
+  // rgbid_tsdf_align_timing: an event before the first launch and after every launch of the last call
+  std::vector<hipEvent_t> align_ev;
+  int align_timed = 0;                         // iterations of the last call that were recorded
+  ~rgbid_tsdf() { for (hipEvent_t e : align_ev) if (e) (void)hipEventDestroy(e); }
   unsigned tiles() const { return (g.n + RUN_TILE - 1) / RUN_TILE; }
 };
 
@@ -864,6 +1139,138 @@ int rgbid_tsdf_timing(rgbid_tsdf* v, int enable, float ms[3]) {
       ms[k] = 0.f;
       if (v->timed[k]) RGBID_HIP(v->timer.elapsed(2 * k, 2 * k + 1, &ms[k]));
     }
+  return v->timer.enable(enable != 0);
+}
+
+}  // extern "C"
+
+namespace {
+
+template <class T>
+int grow(Buffers& buf, T** p, size_t& cap, size_t need) {
+  if (need <= cap) return RGBID_OK;
+  const size_t n = need > 2 * cap ? need : 2 * cap;
+  T* q = nullptr;
+  if (int r = buf.alloc(&q, sizeof(T) * n)) return r;
+  *p = q;
+  cap = n;
+  return RGBID_OK;
+}
+
+unsigned tiles_of(int rows, int cols, int stride, unsigned* tiles_x) {
+  const unsigned lw = ((unsigned)cols + stride - 1) / stride, lh = ((unsigned)rows + stride - 1) / stride;
+  *tiles_x = (lw + 7u) / 8u;
+  return *tiles_x * ((lh + 7u) / 8u);
+}
+
+}  // namespace
+
+extern "C" {
+
+int rgbid_tsdf_align(rgbid_tsdf* v, int V, const rgbid_tsdf_view* views, const float K[4], int rows, int cols, float z_min, float z_max,
+                     unsigned min_weight, float huber, double damping, double eps, unsigned min_pixels, int n_levels,
+                     const rgbid_tsdf_align_level* levels, rgbid_tsdf_align_result* result_dev) {
+  if (!v || !views || !K || !levels) return RGBID_E_INVALID;
+  if (V < 1 || V > v->cap_views) return RGBID_E_INVALID;
+  if (rows < 1 || cols < 1 || rows > RGBID_TSDF_MAX_DIM || cols > RGBID_TSDF_MAX_DIM) return RGBID_E_INVALID;
+  if ((unsigned long long)rows * (unsigned long long)cols * (unsigned long long)V >= (1ull << 31)) return RGBID_E_INVALID;
+  if (!(std::isfinite(z_min) && std::isfinite(z_max) && z_min > 0.f && z_min <= z_max)) return RGBID_E_INVALID;
+  if (min_weight < 1 || min_weight > MAX_W) return RGBID_E_INVALID;
+  if (!(std::isfinite(huber) && huber > 0.f)) return RGBID_E_INVALID;
+  if (!(std::isfinite(damping) && damping >= 0.0)) return RGBID_E_INVALID;
+  if (!(std::isfinite(eps) && eps > 0.0)) return RGBID_E_INVALID;
+  if (min_pixels < 6) return RGBID_E_INVALID;
+  if (n_levels < 1 || n_levels > RGBID_TSDF_ALIGN_MAX_LEVELS) return RGBID_E_INVALID;
+  int total = 0, finest = 8;
+  for (int l = 0; l < n_levels; ++l) {
+    const int s = levels[l].stride, it = levels[l].iterations;
+    if (s != 1 && s != 2 && s != 4 && s != 8) return RGBID_E_INVALID;
+    if (it < 1 || it > RGBID_TSDF_ALIGN_MAX_ITERATIONS) return RGBID_E_INVALID;
+    total += it;
+    finest = s < finest ? s : finest;
+  }
+  if (total > RGBID_TSDF_ALIGN_MAX_ITERATIONS) return RGBID_E_INVALID;
+  for (int k = 0; k < 4; ++k) if (!std::isfinite(K[k])) return RGBID_E_INVALID;
+  if (K[0] == 0.f || K[1] == 0.f) return RGBID_E_INVALID;
+  for (int i = 0; i < V; ++i) {
+    if (!finite_all(views[i].pose.R, 9) || !finite_all(views[i].pose.t, 3)) return RGBID_E_INVALID;
+    float wc[12];
+    rgbid_tsdf_pose_wc(&views[i].pose, wc);
+    for (int k = 0; k < 12; ++k) if (!std::isfinite(wc[k])) return RGBID_E_INVALID;
+    if (!views[i].depthinv_dev || !aligned4(views[i].depthinv_dev)) return RGBID_E_INVALID;
+  }
+  if (!result_dev || (((uintptr_t)result_dev) & 7)) return RGBID_E_INVALID;
+  (void)hipSetDevice(v->ctx->device);
+  hipStream_t s = v->ctx->stream;
+  // the workspace: the finest level has the most tiles
+  unsigned tx;
+  const size_t a_stride = tiles_of(rows, cols, finest, &tx), b_stride = (a_stride + 63) / 64;
+  if (!v->align_views) {
+    int r = v->buf.alloc(&v->align_views, sizeof(AlignView) * (size_t)v->cap_views);
+    if (!r) r = v->buf.alloc_host(&v->align_views_host, sizeof(AlignView) * (size_t)v->cap_views);
+    if (!r) r = v->buf.alloc(&v->aw.pose32, sizeof(float) * 12 * (size_t)v->cap_views);
+    if (r) { v->align_views = nullptr; return r; }
+  }
+  if (int r = grow(v->buf, &v->aw.a, v->aw_a, (size_t)V * ALIGN_TERMS * a_stride)) return r;
+  if (int r = grow(v->buf, &v->aw.b, v->aw_b, (size_t)V * ALIGN_TERMS * b_stride)) return r;
+  if (int r = grow(v->buf, &v->aw.used, v->aw_used, (size_t)V * a_stride)) return r;
+  v->aw.a_stride = a_stride; v->aw.b_stride = b_stride;
+  const bool timing = v->timer.on;
+  if (timing) {
+    if (v->align_ev.size() < (size_t)(2 * total + 1)) v->align_ev.resize(2 * total + 1, nullptr);
+    for (int k = 0; k < 2 * total + 1; ++k) if (!v->align_ev[k]) RGBID_HIP(hipEventCreate(&v->align_ev[k]));
+  }
+  RGBID_HIP(hipStreamSynchronize(s));   // the previous call's copy has read the pinned table
+  for (int i = 0; i < V; ++i) {
+    AlignView& vw = v->align_views_host[i];
+    for (int k = 0; k < 9; ++k) vw.pose[k] = views[i].pose.R[k];
+    for (int k = 0; k < 3; ++k) vw.pose[9 + k] = views[i].pose.t[k];
+    vw.plane = views[i].depthinv_dev;
+  }
+  AlignCam cam{};
+  cam.ray.fx = K[0]; cam.ray.fy = K[1]; cam.ray.cx = K[2]; cam.ray.cy = K[3]; cam.ray.z_min = z_min;
+  cam.ray.hi_i = float_below(v->g.nx - 2u); cam.ray.hi_j = float_below(v->g.ny - 2u); cam.ray.hi_k = float_below(v->g.nz - 2u);
+  cam.ray.min_weight = min_weight;
+  cam.ray.rows = rows; cam.ray.cols = cols;
+  cam.z_max = z_max; cam.huber = huber;
+  AlignRule rule{damping, eps, min_pixels, 0u, 0u};
+  v->align_timed = 0;
+  int e = 0;
+  RGBID_HIP(hipMemcpyAsync(v->align_views, v->align_views_host, sizeof(AlignView) * (size_t)V, hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_tsdf_align_init, dim3(((unsigned)V + VT - 1) / VT), dim3(VT), 0, s, v->align_views, V, result_dev, v->aw.pose32);
+  if (timing) (void)hipEventRecord(v->align_ev[e++], s);
+  for (int l = 0; l < n_levels; ++l) {
+    cam.stride = (unsigned)levels[l].stride;
+    cam.lw = ((unsigned)cols + cam.stride - 1u) / cam.stride;
+    cam.lh = ((unsigned)rows + cam.stride - 1u) / cam.stride;
+    cam.tiles = tiles_of(rows, cols, levels[l].stride, &cam.tiles_x);
+    rule.tiles = cam.tiles;
+    for (int it = 0; it < levels[l].iterations; ++it) {          // enqueued without waiting: the device decides who still runs
+      cam.restart = rule.restart = (l > 0 && it == 0) ? 1u : 0u;
+      hipLaunchKernelGGL(k_tsdf_align_system, dim3((cam.tiles + VT / 64 - 1) / (VT / 64), (unsigned)V), dim3(VT), 0, s, v->g, v->st, cam,
+                         v->align_views, v->aw.pose32, result_dev, v->aw.a, v->aw.used, a_stride);
+      if (timing) (void)hipEventRecord(v->align_ev[e++], s);
+      hipLaunchKernelGGL(k_tsdf_align_solve, dim3((unsigned)V), dim3(VT), 0, s, v->aw, rule, result_dev);
+      if (timing) (void)hipEventRecord(v->align_ev[e++], s);
+    }
+  }
+  RGBID_HIP(hipGetLastError());
+  v->align_timed = timing ? total : 0;
+  return RGBID_OK;
+}
+
+int rgbid_tsdf_align_timing(rgbid_tsdf* v, int enable, float ms[2]) {
+  if (!v) return RGBID_E_INVALID;
+  (void)hipSetDevice(v->ctx->device);
+  if (ms) {
+    ms[0] = ms[1] = 0.f;
+    for (int i = 0; i < v->align_timed; ++i) {
+      float a = 0.f, b = 0.f;
+      RGBID_HIP(hipEventElapsedTime(&a, v->align_ev[2 * i], v->align_ev[2 * i + 1]));
+      RGBID_HIP(hipEventElapsedTime(&b, v->align_ev[2 * i + 1], v->align_ev[2 * i + 2]));
+      ms[0] += a; ms[1] += b;
+    }
+  }
   return v->timer.enable(enable != 0);
 }
 

@@ -3,7 +3,9 @@
 `Volume.integrate` averages the inverse-depth planes (and colours) of keyframes, as `sequence.track_chunked(cloud=..., keyframe_depth=True,
 keyframe_colour=True)` leaves them on the device, into a dense voxel volume; `Volume.extract` cuts the volume's zero crossing with marching
 tetrahedra into vertices, vertex colours and index triples, byte-identical to the numpy restatement of the contract.
-`fuse` is the one-shot over the keyframes of a run and `write_mesh_ply` writes what any viewer opens.
+`fuse` is the one-shot over the keyframes of a run and `write_mesh_ply` writes what any viewer opens.  `Volume.raycast` reads the surface
+back at a pose (section 20), `Volume.align` proposes the pose at which a depth frame lies on it and `align_check` holds a run's keyframes
+against their own model (section 21).
 """
 import ctypes as C
 import math
@@ -26,6 +28,14 @@ STAGES = ("integrate", "scan", "emit")
 MAX_STEPS = 65536                       # RGBID_TSDF_MAX_STEPS: (z_max - z_min) / step at most
 RAYCAST_EXPORTS = ["rgbid_tsdf_pose_wc", "rgbid_tsdf_raycast", "rgbid_tsdf_raycast_timing", "rgbid_tsdf_extract_normals"]   # rgbid_tsdf_raycast.h
 RAYCAST_PLANES = ("depth", "normal", "colour")
+ALIGN_EXPORTS = ["rgbid_tsdf_align", "rgbid_tsdf_align_timing"]                                                                          # rgbid_tsdf_align.h
+ALIGN_STAGES = ("system", "solve")
+ALIGN_STATUS = ("running", "converged", "few", "singular")                                                                              # RGBID_TSDF_ALIGN_*
+ALIGN_STRIDES = (1, 2, 4, 8)
+ALIGN_MAX_LEVELS, ALIGN_MAX_ITERATIONS, ALIGN_TERMS = 4, 256, 28
+ALIGN_LEVELS = ((4, 10), (2, 10), (1, 10))
+# rgbid_tsdf_align_result: 560 bytes
+ALIGN_RESULT = np.dtype([("pose", "<f8", (12,)), ("status", "<i4"), ("iterations", "<i4"), ("used", "<u4", (2,)), ("sums", "<f8", (2, ALIGN_TERMS))])
 
 
 class View(C.Structure):
@@ -107,6 +117,62 @@ def raycast_outputs_arg(outputs):
     if not outs or any(o not in RAYCAST_PLANES for o in outs):
         raise ValueError(f"outputs: some of {RAYCAST_PLANES}, got {outputs!r}")
     return outs
+
+
+def _float64(name, v):
+    try:
+        f = float(v)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"{name}: a number, got {v!r}")
+    if isinstance(v, (bool, str)) or not math.isfinite(f):
+        raise ValueError(f"{name} must be a finite number, got {v!r}")
+    return f
+
+
+def align_levels_arg(levels):
+    """-> the levels as a tuple of (stride, iterations): 1 .. 4 pairs, stride out of 1, 2, 4, 8, iterations >= 1 and at most 256 in all
+    (ValueError otherwise)"""
+    try:
+        lv = [tuple(l) for l in levels]
+    except TypeError:
+        raise ValueError(f"levels: pairs (stride, iterations), got {levels!r}")
+    if not 1 <= len(lv) <= ALIGN_MAX_LEVELS or any(len(l) != 2 for l in lv):
+        raise ValueError(f"levels: 1 .. {ALIGN_MAX_LEVELS} pairs (stride, iterations), got {levels!r}")
+    lv = tuple((_integer("stride", s), _integer("iterations", n)) for s, n in lv)
+    if any(s not in ALIGN_STRIDES for s, _ in lv):
+        raise ValueError(f"a stride must be one of {ALIGN_STRIDES}, got {levels!r}")
+    if any(n < 1 for _, n in lv) or sum(n for _, n in lv) > ALIGN_MAX_ITERATIONS:
+        raise ValueError(f"every level needs at least 1 iteration and all together at most {ALIGN_MAX_ITERATIONS}, got {levels!r}")
+    return lv
+
+
+def align_params_arg(huber, damping, eps, min_pixels):
+    """-> (huber, damping, eps, min_pixels) as the library takes them: huber a finite float32 > 0, damping finite and >= 0, eps finite and
+    > 0, min_pixels an integer in 6 .. 2^32 - 1 (ValueError otherwise)"""
+    h, d, e, n = _float32("huber", huber), _float64("damping", damping), _float64("eps", eps), _integer("min_pixels", min_pixels)
+    if not h > 0:
+        raise ValueError(f"huber must be > 0, got {huber!r}")
+    if not d >= 0:
+        raise ValueError(f"damping must be >= 0, got {damping!r}")
+    if not e > 0:
+        raise ValueError(f"eps must be > 0, got {eps!r}")
+    if not 6 <= n < 1 << 32:
+        raise ValueError(f"min_pixels must be at least 6, got {min_pixels!r}")
+    return h, d, e, n
+
+
+def align_dict(res):
+    """the records of rgbid_tsdf_align (ALIGN_RESULT [V]) -> dict(R [V, 3, 3], t [V, 3], status, iterations [V], used [V, 2],
+    H [V, 2, 6, 6], b [V, 2, 6], error [V, 2]); index 0 of the pairs is the first system built, 1 the last"""
+    H = np.zeros((len(res), 2, 6, 6), np.float64)
+    k = 0
+    for i in range(6):
+        for j in range(i, 6):
+            H[:, :, i, j] = H[:, :, j, i] = res["sums"][:, :, k]
+            k += 1
+    return dict(R=res["pose"][:, :9].reshape(-1, 3, 3).copy(), t=res["pose"][:, 9:].copy(), status=res["status"].copy(),
+                iterations=res["iterations"].copy(), used=res["used"].copy(), H=H, b=res["sums"][:, :, 21:27].copy(),
+                error=res["sums"][:, :, 27].copy())
 
 
 def pose_wc(R, t):
@@ -197,6 +263,9 @@ class Volume(_lib.CtxHandle):
                                          C.c_void_p, C.c_void_p, C.c_void_p]
         L.rgbid_tsdf_raycast_timing.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.rgbid_tsdf_extract_normals.argtypes = [C.c_void_p, C.c_void_p, C.c_ulonglong]
+        L.rgbid_tsdf_align.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint, C.c_float,
+                                       C.c_double, C.c_double, C.c_uint, C.c_int, C.c_void_p, C.c_void_p]
+        L.rgbid_tsdf_align_timing.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         self._created(L.rgbid_tsdf_create(C.byref(self._h), ctx._h, C.c_ulonglong(self.max_voxels), self.max_views, int(self.colour)))
 
     @property
@@ -336,6 +405,56 @@ class Volume(_lib.CtxHandle):
         check(self.L.rgbid_tsdf_raycast_timing(self._h, int(enable), ms))
         return float(ms[0])
 
+    def _align_args(self, R, t, K, rows, cols, levels, huber, damping, eps, min_pixels, min_weight, z_min, z_max):
+        """the alignment's arguments as the library takes them (ValueError for what it would refuse)"""
+        R, t = poses(R, t)
+        rows, cols = image_size(rows, cols, len(R), (1 << 31) - 1)
+        if len(R) > self.max_views:
+            raise ValueError(f"{len(R)} views are more than the volume's {self.max_views}")
+        lo, hi = depth_range(z_min, z_max)
+        h, d, e, n = align_params_arg(self.trunc if huber is None else huber, damping, eps, min_pixels)
+        return R, t, intrinsics(K), rows, cols, align_levels_arg(levels), h, d, e, n, weight_arg(min_weight), lo, hi
+
+    def align_into(self, planes, R, t, K, rows, cols, levels, huber, damping, eps, min_pixels, min_weight, z_min, z_max, result):
+        """the raw call: checked arguments, the records written asynchronously on the context's stream into `result`, a contiguous CUDA
+        uint8 tensor of 560 bytes per view"""
+        R, t, k, rows, cols, lv, h, d, e, n, w, lo, hi = self._align_args(R, t, K, rows, cols, levels, huber, damping, eps, min_pixels, min_weight,
+                                                                           z_min, z_max)
+        V = len(R)
+        planes = planes_arg(planes, V, rows, cols, self.ctx.device)
+        if not (isinstance(result, torch.Tensor) and result.is_cuda and result.dtype == torch.uint8 and result.is_contiguous()
+                and result.numel() == V * ALIGN_RESULT.itemsize and result.device.index == self.ctx.device and result.data_ptr() % 8 == 0):
+            raise ValueError(f"result: a contiguous CUDA uint8 tensor of {V} x {ALIGN_RESULT.itemsize} bytes on device {self.ctx.device}")
+        views = (View * V)(*[View(Pose((C.c_double * 9)(*R[v].reshape(9)), (C.c_double * 3)(*t[v])), planes[v].data_ptr(), None) for v in range(V)])
+        lv_arr = (C.c_int * (2 * len(lv)))(*[x for l in lv for x in l])
+        check(self.L.rgbid_tsdf_align(self._h, V, views, (C.c_float * 4)(*k), rows, cols, C.c_float(lo), C.c_float(hi), w, C.c_float(h),
+                                      C.c_double(d), C.c_double(e), n, len(lv), lv_arr, C.c_void_p(result.data_ptr())))
+
+    def align(self, planes, R, t, K, rows, cols, levels=ALIGN_LEVELS, huber=None, damping=0.0, eps=1e-6, min_pixels=64, min_weight=1,
+              z_min=0.05, z_max=20.0):
+        """propose, for each view, the world pose at which its inverse-depth plane lies on the volume's surface: Gauss-Newton on the
+        interpolated signed distance of every measured pixel, from the poses R [V, 3, 3], t [V, 3], over the `levels` (stride,
+        iterations) in order, with the Huber threshold `huber` in metres (None: trunc), the damping H_jj (1 + damping), the step bound
+        `eps` that ends a level, and at least `min_pixels` used pixels -> dict(R [V, 3, 3], t [V, 3] float64, status [V] (an index into
+        ALIGN_STATUS), iterations [V], used [V, 2], H [V, 2, 6, 6], b [V, 2, 6], error [V, 2]: the normal equations H delta = -b for
+        delta = (v, omega) in the world frame and the weighted squared residual, of the first and of the last system built).  Nothing is
+        applied: the caller judges the proposal.  Synchronises."""
+        a = self._align_args(R, t, K, rows, cols, levels, huber, damping, eps, min_pixels, min_weight, z_min, z_max)
+        V = len(a[0])
+        planes_arg(planes, V, a[3], a[4], self.ctx.device)
+        result = torch.empty((V * ALIGN_RESULT.itemsize,), dtype=torch.uint8, device=self._dev)
+        self.ctx.wait_torch_stream()   # the planes and the result are torch's
+        self.align_into(planes, R, t, K, rows, cols, levels, huber, damping, eps, min_pixels, min_weight, z_min, z_max, result)
+        self.ctx.sync()
+        return align_dict(result.cpu().numpy().view(ALIGN_RESULT))
+
+    def align_timing(self, enable=True):
+        """record HIP events around every launch of the following alignments (the switch is `timing`'s); -> the device ms of the last
+        call, summed over its launches {stage: ms}"""
+        ms = (C.c_float * 2)()
+        check(self.L.rgbid_tsdf_align_timing(self._h, int(enable), ms))
+        return dict(zip(ALIGN_STAGES, ms[:]))
+
     def emit(self, vertices, colours, triangles):
         """write the last plan's mesh into CUDA tensors [>= nv, 3] float32, [>= nv, 3] uint8 or None, [>= nt, 3] int32.  Asynchronous."""
         assert vertices.is_cuda and vertices.dtype == torch.float32 and vertices.is_contiguous() and vertices.dim() == 2 and vertices.shape[1] == 3
@@ -423,6 +542,56 @@ def surface_agreement(vol, keyframes, K, rows, cols, step=None, min_weight=1, z_
             d = torch.sort((depth[j][both] - own[both]).abs()).values.cpu().numpy()
             out.append(dict(pixels=int(len(d)), median=rank_value(d, 5), p90=rank_value(d, 9)))
     return out
+
+
+def pose_correction(R0, t0, R1, t1):
+    """the rotation angle (rad) and the translation (m) that take the world pose (R0, t0) to (R1, t1)"""
+    dR = np.asarray(R1, np.float64) @ np.asarray(R0, np.float64).T
+    c = min(1.0, max(-1.0, (float(np.trace(dR)) - 1.0) / 2.0))
+    return math.acos(c), float(np.linalg.norm(np.asarray(t1, np.float64) - np.asarray(t0, np.float64)))
+
+
+def align_check(ctx, keyframes, K, rows, cols, bounds=None, voxel=0.02, trunc=None, levels=ALIGN_LEVELS, huber=None, damping=0.0, eps=1e-6,
+                min_pixels=64, min_weight=1, z_min=0.05, z_max=20.0, max_voxels=1 << 27, points=None, return_results=False):
+    """A consistency check of a run's keyframe poses against its own model: the even-numbered keyframes are fused (as `fuse` does, over
+    `bounds` or the box of `points`), every odd-numbered one is aligned to that model from its own pose -> per odd keyframe
+    dict(keyframe, rotation (rad), translation (m): the correction the alignment proposes, status (a word of ALIGN_STATUS), iterations,
+    used, rms_before, rms_after: sqrt(error / used) of the first and the last system, NaN without a used pixel); with return_results also
+    Volume.align's dict.  Nothing is applied.  A CPU prototype showed why: when a volume is fused from perturbed views and every view
+    is aligned to it and fused again, the poses get worse round by round, and tracking then integrating view by view doubled the
+    rotation error -- the surfaces here are near-planar, the model is thin and aligning a view to a model it is part of is biased.  The
+    corrections are a diagnostic of the trajectory, not a refinement of it."""
+    even, odd = keyframes[0::2], keyframes[1::2]
+    if not even or not odd:
+        raise ValueError("the check needs at least two keyframes")
+    mesh = fuse(ctx, even, K, rows, cols, bounds=bounds, voxel=voxel, trunc=trunc, min_weight=min_weight, z_min=z_min, z_max=z_max,
+                max_voxels=max_voxels, points=points, keep_volume=True)
+    vol = mesh[-1]
+    try:
+        out, results = [], []
+        for a in range(0, len(odd), vol.max_views):
+            kfs = odd[a:a + vol.max_views]
+            r = vol.align([k["depthinv"] for k in kfs], np.stack([np.asarray(k["R"]) for k in kfs]), np.stack([np.asarray(k["t"]) for k in kfs]), K,
+                          rows, cols, levels, huber, damping, eps, min_pixels, min_weight, z_min, z_max)
+            results.append(r)
+            for j, k in enumerate(kfs):
+                rot, tr = pose_correction(k["R"], k["t"], r["R"][j], r["t"][j])
+                with np.errstate(all="ignore"):
+                    rms = np.sqrt(r["error"][j] / r["used"][j].astype(np.float64))
+                out.append(dict(keyframe=2 * (a + j) + 1, rotation=rot, translation=tr, status=ALIGN_STATUS[int(r["status"][j])],
+                                iterations=int(r["iterations"][j]), used=int(r["used"][j][1]), rms_before=float(rms[0]), rms_after=float(rms[1])))
+        if return_results:
+            return out, {k: np.concatenate([r[k] for r in results]) for k in results[0]}
+        return out
+    finally:
+        vol.close()
+
+
+def align_check_summary(figures):
+    """align_check's figures -> dict(views, median and largest rotation and translation, counts per status word)"""
+    rot, tr = [f["rotation"] for f in figures], [f["translation"] for f in figures]
+    return dict(views=len(figures), rotation_median=float(np.median(rot)), rotation_max=float(max(rot)), translation_median=float(np.median(tr)),
+                translation_max=float(max(tr)), status={w: sum(f["status"] == w for f in figures) for w in ALIGN_STATUS})
 
 
 def _vertex_dtype(normals):

@@ -103,6 +103,11 @@ def main():
                     help="with --mesh: print how well the fused surface, ray-cast at each keyframe's pose, agrees with the depth the keyframe measured")
     ap.add_argument("--mesh-render-step", type=float, default=None, metavar="S",
                     help="with --mesh-render / --mesh-render-check: metres of camera depth between two samples of a ray (default: the voxel size)")
+    ap.add_argument("--mesh-align-check", action="store_true",
+                    help="with --mesh: fuse the even-numbered keyframes, align the odd-numbered ones to that model (DESIGN.md section 21) and print "
+                         "the corrections the alignment proposes; nothing is applied")
+    ap.add_argument("--mesh-align-iterations", type=int, default=None, metavar="N",
+                    help="with --mesh-align-check: Gauss-Newton iterations per level of the strides 4, 2, 1 (1 .. 85, default 10)")
     ap.add_argument("--optimise", nargs="?", const="auto", default=None, choices=["auto", "multilevel", "single"],
                     help="optimise the trajectory with the pose-graph back-end once over the run (single rank; DESIGN.md section 11)")
     ap.add_argument("--loops", default=None, choices=["auto", "appearance"],
@@ -165,6 +170,10 @@ def main():
         ap.error("--mesh-normals / --mesh-render / --mesh-render-check / --mesh-render-step need --mesh")
     if args.mesh_render_step is not None and not (args.mesh_render or args.mesh_render_check):
         ap.error("--mesh-render-step needs --mesh-render or --mesh-render-check")
+    if not args.mesh and (args.mesh_align_check or args.mesh_align_iterations is not None):
+        ap.error("--mesh-align-check / --mesh-align-iterations need --mesh")
+    if args.mesh_align_iterations is not None and not args.mesh_align_check:
+        ap.error("--mesh-align-iterations needs --mesh-align-check")
     if args.mesh:
         from rgbid import tsdf as TS
         try:
@@ -177,6 +186,9 @@ def main():
                 mesh["bounds"] = args.mesh_bounds
             if args.mesh_render_step is not None:
                 TS.step_arg(args.mesh_render_step, 0.05, 20.0)
+            if args.mesh_align_check:
+                n_it = 10 if args.mesh_align_iterations is None else args.mesh_align_iterations
+                align_levels = TS.align_levels_arg(tuple((s, n_it) for s in (4, 2, 1)))
         except ValueError as e:
             ap.error(str(e))
     if (args.cloud_radius is None) != (args.cloud_min_neighbours is None):
@@ -357,6 +369,15 @@ def main():
                     print(f"rank {rank}: {len(kfs_all)} ray-cast views of the volume -> {args.mesh_render}")
             finally:
                 volume.close()
+        if args.mesh_align_check:
+            try:
+                figures = TS.align_check(ctx, pc.keyframes, tuple(args.K), args.rows, args.cols, points=pc.points, levels=align_levels, **mesh)
+            except ValueError as e:
+                sys.exit(f"rank {rank}: --mesh-align-check: {e}")
+            run = TS.align_check_summary(figures)
+            print(f"rank {rank}: mesh align check: {run['views']} keyframes aligned to the model of the others: correction median "
+                  f"{run['rotation_median']:.6f} rad {run['translation_median']:.6f} m, largest {run['rotation_max']:.6f} rad {run['translation_max']:.6f} m; "
+                  + ", ".join(f"{n} {w}" for w, n in run["status"].items()))
     if comm is not None:
         comm.close()
     if rank == 0:
