@@ -95,6 +95,10 @@ def main():
     ap.add_argument("--mesh-bounds", type=float, nargs=6, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
                     help="with --mesh: the volume's box in world metres (default: the box of the keyframe cloud, padded by T)")
     ap.add_argument("--mesh-max-voxels", type=int, default=None, metavar="N", help="with --mesh: the largest volume to allocate (default 2^27 voxels)")
+    ap.add_argument("--mesh-min-component", type=int, default=None, metavar="N",
+                    help="with --mesh: drop the connected components of the mesh with fewer than N triangles (DESIGN.md section 22)")
+    ap.add_argument("--mesh-largest-components", type=int, default=None, metavar="K",
+                    help="with --mesh: keep only the K connected components of the mesh with the most triangles")
     ap.add_argument("--mesh-normals", action="store_true", help="with --mesh: the PLY also holds a unit normal per vertex (nx ny nz)")
     ap.add_argument("--mesh-render", default="", metavar="DIR",
                     help="with --mesh: ray-cast the fused volume at every exported keyframe's pose (DESIGN.md section 20) and write "
@@ -174,6 +178,9 @@ def main():
         ap.error("--mesh-align-check / --mesh-align-iterations need --mesh")
     if args.mesh_align_iterations is not None and not args.mesh_align_check:
         ap.error("--mesh-align-iterations needs --mesh-align-check")
+    if not args.mesh and (args.mesh_min_component is not None or args.mesh_largest_components is not None):
+        ap.error("--mesh-min-component / --mesh-largest-components need --mesh")
+    mesh_filter = {}
     if args.mesh:
         from rgbid import tsdf as TS
         try:
@@ -189,6 +196,8 @@ def main():
             if args.mesh_align_check:
                 n_it = 10 if args.mesh_align_iterations is None else args.mesh_align_iterations
                 align_levels = TS.align_levels_arg(tuple((s, n_it) for s in (4, 2, 1)))
+            if TS.component_filter_arg(args.mesh_min_component, args.mesh_largest_components) is not None:
+                mesh_filter = dict(min_component=args.mesh_min_component, largest_components=args.mesh_largest_components)
         except ValueError as e:
             ap.error(str(e))
     if (args.cloud_radius is None) != (args.cloud_min_neighbours is None):
@@ -337,14 +346,19 @@ def main():
         cast = bool(args.mesh_render or args.mesh_render_check)
         try:
             fused = TS.fuse(ctx, pc.keyframes, tuple(args.K), args.rows, args.cols, points=pc.points, return_volume=True, normals=args.mesh_normals,
-                            keep_volume=cast, **mesh)
+                            keep_volume=cast, **mesh, **mesh_filter)
         except ValueError as e:
             sys.exit(f"rank {rank}: --mesh: {e}")
         verts, cols, tris = fused[:3]
         vol = fused[4 if args.mesh_normals else 3]
         TS.write_mesh_ply(path, verts, cols, tris, fused[3] if args.mesh_normals else None)
+        flt = vol.get("filter")             # the line below tells the extraction's counts, the one after it what the filter left
         print(f"rank {rank}: mesh of {len(pc.keyframes)} keyframes: {vol['nx']} x {vol['ny']} x {vol['nz']} = {vol['voxels']} voxels of {mesh['voxel']:g} m "
-              f"(truncation {mesh['trunc']:g} m), {vol['touched']} touched, {verts.shape[0]} vertices, {tris.shape[0]} triangles -> {path}")
+              f"(truncation {mesh['trunc']:g} m), {vol['touched']} touched, {flt['vertices'] if flt else verts.shape[0]} vertices, "
+              f"{flt['triangles'] if flt else tris.shape[0]} triangles -> {path}")
+        if flt:
+            print(f"rank {rank}: mesh components: {flt['kept_components']} of {flt['components']} kept, {flt['vertices']} -> {flt['kept_vertices']} vertices, "
+                  f"{flt['triangles']} -> {flt['kept_triangles']} triangles")
         if cast:
             volume = fused[-1]
             try:
