@@ -10,6 +10,9 @@
  * (k ny + j) nx + i and the centre x = ox + (float)i voxel, y and z likewise: one product and one sum each.  Per voxel: D (float32 metres,
  * initially 0), the counts W and Cn (0 .. 65 535, initially 0) and three integer colour sums.  The state is exchanged as the planes
  * D float32 [nz][ny][nx], counts uint32 [nz][ny][nx] = W | Cn << 16, rgb_sum uint32 [3][nz][ny][nx].
+ * rgbid_tsdf_set_state checks no value, so every step below is defined for any bits: W and Cn up to 65 535 in any combination, any sums,
+ * and a D that is NaN, infinite, a signed zero, denormal or huge.  Denormals are not flushed, -0.0 is not < 0 and a NaN fails every
+ * comparison.
  *
  * Integrate.  V views (pose, inverse-depth plane float32 [rows][cols], optionally the colour area uint8 [rows][cols][3] of the keyframe's
  * export block: r g b per pixel, as rgbid_cloud reads it), one K = fx, fy, cx, cy, one depth gate 0 < z_min <= z_max.  Every voxel
@@ -23,8 +26,12 @@
  *  5. m = iD[pv][pu] is MEASURED iff it is finite and > 0 and z_m = 1.f / m (IEEE division) is finite; otherwise the view is skipped.
  *  6. s = z_m - Z.  If s < -trunc the voxel is hidden behind the surface and the view is skipped.
  *  7. A voxel whose W is 65 535 skips the view.  Otherwise d = fminf(s, trunc), D = (D (float)W + d) / (float)(W + 1) -- one product,
- *     one sum, one IEEE division -- and W += 1.
- *  8. If the view has colours, |s| <= trunc and Cn < 65 535: the pixel's r, g, b are added to the sums and Cn += 1.
+ *     one sum, one IEEE division -- and W += 1.  Cn and the sums of a voxel with a full W stay as well.  A D that is NaN stays NaN: the
+ *     stored bits are the operand's, sign and payload, with the quiet bit set, as the IEEE operations of the device and of the mirror's
+ *     host both return them (measured); an operation that has no NaN operand and is invalid (D infinite with W = 0) gives 0xFFC00000 on
+ *     both.  Nothing is canonicalised in the state.
+ *  8. If the view has colours, |s| <= trunc and Cn < 65 535: the pixel's r, g, b are added to the sums and Cn += 1.  The sums are
+ *     uint32 and the additions are modulo 2^32.  A full Cn does not stop W (step 7), and W never carries into Cn.
  *
  * Extract: marching tetrahedra on the Kuhn split of every cell.  Corner code c (0 .. 7) has the offset (c & 1, (c >> 1) & 1, (c >> 2) & 1).
  * The six tetrahedra of a cell are the monotone paths 0 -> e_a -> e_a + e_b -> 7 for the axis orders xyz, xzy, yxz, yzx, zxy, zyx, in
@@ -33,7 +40,9 @@
  *  9. A lattice edge is (voxel p, offset code c in 1 .. 7) with q = p + offset(c) inside the volume; it is ACTIVE iff p and q are valid
  *     and exactly one of them is inside.  Active edges are numbered by ascending linear(p) 7 + (c - 1): that rank is the vertex index.
  * 10. With a the inside end and b the other: t = D_a / (D_a - D_b) (IEEE division) and the position per component is
- *     p_a + t (p_b - p_a): one difference, one product, one sum of the ends' centres.
+ *     p_a + t (p_b - p_a): one difference, one product, one sum of the ends' centres.  A component that comes out NaN (D_a and D_b
+ *     infinite, or D_b NaN) is written with the bits RGBID_RENDER_NAN_BITS, as the render and the ray cast write theirs: the
+ *     arithmetic's own NaN differs between device and host (a - b turns the sign of a NaN b on the device).  D_b = +-0 gives t = 1.
  * 11. Colour: the mean of an end per channel is min((2 sum + Cn) / (2 Cn), 255) in 64-bit integers, absent when Cn = 0 (or when the handle
  *     holds no colour).  Both ends have one: fminf(fmaxf(floorf((c_a + t (c_b - c_a)) + 0.5f), 0.f), 255.f) with the means as float32
  *     (a NaN gives 0); one end has one: that mean; neither: 0.

@@ -43,7 +43,12 @@
  * 32. max |delta_i| < eps: the view is CONVERGED for this level.  A view that has stopped is skipped by the rest of the level.  The next
  *     level sets CONVERGED views RUNNING again.  FEW and SINGULAR are final, and the pose stays as it was before that iteration.  A view
  *     that has used all its iterations ends RUNNING.
- * 33. Result per view (device memory): rgbid_tsdf_align_result.
+ * 33. Result per view (device memory): rgbid_tsdf_align_result.  On any state (rgbid_tsdf.h): fabsf(f) < trunc fails for a NaN or
+ *     infinite f, and a fraction of 0 still multiplies its corner (0 inf and 0 NaN are NaN), so a D that is NaN or infinite never reaches a
+ *     used pixel.  A huge finite D can: beside a fraction of exactly 0 it leaves f alone and makes J infinite or NaN, the sums then hold
+ *     NaN and the view ends SINGULAR with its pose unchanged.  Every NaN among the doubles of the record (sums and pose) is written with
+ *     the bits RGBID_TSDF_ALIGN_NAN_BITS: the arithmetic's own NaN differs between device and host in its sign (measured: a float32
+ *     difference a - b turns the sign of a NaN b on the device).
  */
 #ifndef RGBID_TSDF_ALIGN_H_
 #define RGBID_TSDF_ALIGN_H_
@@ -59,6 +64,7 @@ extern "C" {
 #define RGBID_TSDF_ALIGN_MAX_LEVELS 4
 #define RGBID_TSDF_ALIGN_MAX_ITERATIONS 256     /* over all levels of a call */
 #define RGBID_TSDF_ALIGN_TERMS 28               /* 21 of H, 6 of b, the weighted squared residual */
+#define RGBID_TSDF_ALIGN_NAN_BITS 0x7FFFFFFFFFFFFFFFull   /* bits of every NaN among the doubles of a result record */
 
 enum {
   RGBID_TSDF_ALIGN_RUNNING = 0,                 /* every iteration was used and none met eps */

@@ -40,13 +40,16 @@
  * 21. Outputs (device memory, each may be NULL), view v at element offset v rows cols {1, 3, 3}: depth float32 [V][rows][cols], normal
  *     float32 [V][3][rows][cols], colour uint8 [V][rows][cols][3], the layouts of rgbid_render_views.  An empty pixel has depth NaN,
  *     normal NaN and colour 0.  Every NaN written has the bits RGBID_RENDER_NAN_BITS.
+ *     This holds on any state (rgbid_tsdf.h): a NaN f is neither a hit nor an exit's first half (f > 0 and f <= 0 both fail; !(f > 0)
+ *     holds), a Z* that is NaN is a hit whose re-sample is undefined, and the sampler masks Cn out of every count it compares.
  * The contract visits every n; the kernel skips the n whose sample it can prove undefined (DESIGN.md section 20 holds the proof).
  *
  * Vertex normals, world frame, at the vertex ranks of step 9, under the plan's min_weight.
  * 22. Voxel gradient, per axis with the neighbours p +- e; a neighbour counts iff it is inside the volume and valid.  Both count:
  *     D+ - D-.  Only p + e: 2.f (D+ - D).  Only p - e: 2.f (D - D-).  Neither: 0.
  * 23. Vertex of the active edge (a inside, b outside, t of step 10): g = g_a + t (g_b - g_a) per component, L as in step 19; the normal
- *     is g / L, or 0 0 0 when L is zero or not finite (not NaN: it goes into a PLY).
+ *     is g / L, or 0 0 0 when L is zero or not finite (not NaN: it goes into a PLY).  A NaN t or a D that is not finite makes L NaN or
+ *     infinite, so no normal component is ever NaN; the vertex itself may be (step 10).
  */
 #ifndef RGBID_TSDF_RAYCAST_H_
 #define RGBID_TSDF_RAYCAST_H_

@@ -128,7 +128,7 @@ __global__ __launch_bounds__(VT) void k_tsdf_integrate(TsdfGrid g, TsdfCam cam, 
     if (c != c_in) {                                            // a view touched the voxel: W grew
       st.D[i] = D;
       st.counts[i] = c;
-      if ((c ^ c_in) >> 16) {
+      if (st.rgb && ((c ^ c_in) >> 16)) {                       // Cn grows only with sums; the pointer is tested all the same
         st.rgb[i] += dr; st.rgb[st.stride + i] += dg; st.rgb[2 * st.stride + i] += db;
       }
     }
@@ -188,6 +188,9 @@ __device__ __forceinline__ float lerp_strict(float a, float b, float t) {
   return a + t * (b - a);
 }
 
+// every NaN that a vertex or a view receives has the bits of the render's
+__device__ __forceinline__ float canonical_nan(float x) { return x != x ? __uint_as_float(RGBID_RENDER_NAN_BITS) : x; }
+
 // step 11's mean of one voxel and channel; false when the voxel has none
 __device__ __forceinline__ bool voxel_mean(const TsdfState& st, unsigned i, unsigned cn, int ch, float& out) {
   if (!st.rgb || cn == 0) return false;
@@ -221,10 +224,10 @@ struct EdgeSrc {
     const unsigned bx = p_in ? ix + dx : ix, by = p_in ? iy + dy : iy, bz = p_in ? iz + dz : iz;
     const float Da = p_in ? Dp : Dq, Db = p_in ? Dq : Dp;
     const float t = Da / (Da - Db);
-    float* o = verts + 3 * (size_t)pos;
-    o[0] = lerp_strict(centre(g.ox, ax, g.voxel), centre(g.ox, bx, g.voxel), t);
-    o[1] = lerp_strict(centre(g.oy, ay, g.voxel), centre(g.oy, by, g.voxel), t);
-    o[2] = lerp_strict(centre(g.oz, az, g.voxel), centre(g.oz, bz, g.voxel), t);
+    float* o = verts + 3 * (size_t)pos;                         // step 10: a NaN component has the one bit pattern
+    o[0] = canonical_nan(lerp_strict(centre(g.ox, ax, g.voxel), centre(g.ox, bx, g.voxel), t));
+    o[1] = canonical_nan(lerp_strict(centre(g.oy, ay, g.voxel), centre(g.oy, by, g.voxel), t));
+    o[2] = canonical_nan(lerp_strict(centre(g.oz, az, g.voxel), centre(g.oz, bz, g.voxel), t));
     if (cols) {
       const unsigned a = p_in ? p : q, b = p_in ? q : p;
       const unsigned cna = st.counts[a] >> 16, cnb = st.counts[b] >> 16;
@@ -365,8 +368,6 @@ __device__ __forceinline__ float tri_value(const float d[8], float fx_, float fy
   const float ly1 = lerp_strict(lerp_strict(d[4], d[5], fx_), lerp_strict(d[6], d[7], fx_), fy_);
   return lerp_strict(ly0, ly1, fz_);
 }
-
-__device__ __forceinline__ float canonical_nan(float x) { return x != x ? __uint_as_float(RGBID_RENDER_NAN_BITS) : x; }
 
 // One thread per pixel; a wave is an 8 x 8 pixel tile, so that the corner gathers of neighbouring rays fall on neighbouring voxels; a
 // block holds four tiles of the view blockIdx.y, whose pose row is read with scalar loads.  No LDS, no atomic.
@@ -512,6 +513,9 @@ __device__ __forceinline__ int align_status(const rgbid_tsdf_align_result* res, 
   return s == RGBID_TSDF_ALIGN_CONVERGED && restart ? RGBID_TSDF_ALIGN_RUNNING : s;
 }
 
+// step 33: a NaN among the record's doubles has the one bit pattern (a - b turns the sign of a NaN b here and not on every host)
+__device__ __forceinline__ double canonical_nan64(double x) { return x != x ? __longlong_as_double((long long)RGBID_TSDF_ALIGN_NAN_BITS) : x; }
+
 // step 28's tree64 over the wave: every lane ends with the sum
 __device__ __forceinline__ double tree64(double v) {
 #pragma unroll
@@ -643,7 +647,7 @@ __global__ __launch_bounds__(VT) void k_tsdf_align_solve(AlignWork w, AlignRule 
   rgbid_tsdf_align_result& r = res[view];
   const bool first = r.iterations == 0;
   if (threadIdx.x < ALIGN_TERMS) {                              // step 33: the first and the last system built
-    const double s = src[(size_t)threadIdx.x * src_stride];
+    const double s = canonical_nan64(src[(size_t)threadIdx.x * src_stride]);
     r.sums[1][threadIdx.x] = s;
     if (first) r.sums[0][threadIdx.x] = s;
   }
@@ -725,7 +729,7 @@ __global__ __launch_bounds__(VT) void k_tsdf_align_solve(AlignWork w, AlignRule 
   }
 #pragma unroll
   for (int k = 0; k < 12; ++k) {
-    r.pose[k] = Q[k];
+    r.pose[k] = canonical_nan64(Q[k]);
     w.pose32[12u * view + k] = (float)Q[k];                     // step 24, for the next launch
   }
   r.status = biggest < rule.eps ? RGBID_TSDF_ALIGN_CONVERGED : RGBID_TSDF_ALIGN_RUNNING;   // step 32

@@ -15,6 +15,7 @@ D = np.float64
 RUNNING, CONVERGED, FEW, SINGULAR = 0, 1, 2, 3
 STATUS_NAMES = ("running", "converged", "few", "singular")
 TERMS = 28
+NAN_BITS = np.uint64(0x7FFFFFFFFFFFFFFF)                         # RGBID_TSDF_ALIGN_NAN_BITS
 PAIRS = [(i, j) for i in range(6) for j in range(i, 6)]          # the 21 products of step 27, row-major
 STRIDES = (1, 2, 4, 8)
 RESULT_DTYPE = np.dtype([("pose", "<f8", (12,)), ("status", "<i4"), ("iterations", "<i4"), ("used", "<u4", (2,)), ("sums", "<f8", (2, TERMS))])
@@ -165,6 +166,13 @@ def update(pose, delta):
     return np.array(Rn + tn, D)
 
 
+def one_nan(a):
+    """step 33: every NaN of a float64 array -> the bits NAN_BITS"""
+    b = np.ascontiguousarray(a, D).copy()
+    b.view(np.uint64)[np.isnan(b)] = NAN_BITS
+    return b
+
+
 def _run(system_fn, V, R, t, levels, damping, eps, min_pixels):
     out = np.zeros(V, RESULT_DTYPE)
     for v in range(V):
@@ -178,8 +186,8 @@ def _run(system_fn, V, R, t, levels, damping, eps, min_pixels):
                     break
                 used, sums = system_fn(v, pose32(pose), stride)
                 if its == 0:
-                    out[v]["used"][0], out[v]["sums"][0] = used, sums
-                out[v]["used"][1], out[v]["sums"][1] = used, sums
+                    out[v]["used"][0], out[v]["sums"][0] = used, one_nan(sums)
+                out[v]["used"][1], out[v]["sums"][1] = used, one_nan(sums)
                 its += 1
                 if used < min_pixels:
                     status = FEW
@@ -191,7 +199,7 @@ def _run(system_fn, V, R, t, levels, damping, eps, min_pixels):
                 pose = update(pose, delta)
                 if max(abs(x) for x in delta) < eps:
                     status = CONVERGED
-        out[v]["pose"], out[v]["status"], out[v]["iterations"] = pose, status, its
+        out[v]["pose"], out[v]["status"], out[v]["iterations"] = one_nan(pose), status, its
     return out
 
 

@@ -4,7 +4,7 @@ sums and every decision are integers and booleans.  `integrate` and `extract` ar
 `extract_loop` are the plain scalar loops of the same contract that the CPU tests hold them against."""
 import numpy as np
 
-from tests.render_mirror import pose_cw, rot_row
+from tests.render_mirror import one_nan, pose_cw, rot_row
 
 F = np.float32
 MAX_W = 65535
@@ -143,7 +143,8 @@ def integrate(vol, planes, colours, R, t, K, z_min=0.05, z_max=20.0):
         i, iu, iv, s = i[take], iu[take], iv[take], s[take]
         d = np.minimum(s, vol.trunc)
         w = W[i].astype(F)
-        D[i] = (D[i] * w + d) / (w + F(1))
+        with np.errstate(all="ignore"):                      # a D that is not finite, or a huge one, is walked like any other
+            D[i] = (D[i] * w + d) / (w + F(1))
         W[i] += np.uint32(1)
         if vol.colour and colours is not None and colours[v] is not None:
             c = np.abs(s) <= vol.trunc
@@ -245,6 +246,7 @@ def extract(vol, min_weight=1):
             mix = np.where(np.isnan(mix), F(0), mix)
             cols[:, ch] = np.where(both, mix, np.where(has[a], ca, np.where(has[b], cb, F(0)))).astype(np.uint8)
     assert verts.dtype == F and tt.dtype == F
+    verts = one_nan(verts)                                   # step 10: every NaN component has the one bit pattern
     # triangles: the cells whose 8 corners are valid, their 8-bit inside code, then per (tetrahedron, case) the table's rows
     C = (slice(0, nz - 1), slice(0, ny - 1), slice(0, nx - 1))
     allv = np.ones((nz - 1, ny - 1, nx - 1), bool)
@@ -301,14 +303,15 @@ def extract_loop(vol, min_weight):
                         a, b = ((i, j, k), (qi, qj, qk)) if inside(i, j, k) else ((qi, qj, qk), (i, j, k))
                         Da, Db = vol.D[a[2], a[1], a[0]], vol.D[b[2], b[1], b[0]]
                         tt = F(Da / F(Da - Db))
-                        verts.append([F(cen[x][a[x]] + F(tt * F(cen[x][b[x]] - cen[x][a[x]]))) for x in range(3)])
+                        verts.append(one_nan([F(cen[x][a[x]] + F(tt * F(cen[x][b[x]] - cen[x][a[x]]))) for x in range(3)]))
                         mean = []
                         for e in (a, b):
                             cn = int(vol.Cn[e[2], e[1], e[0]])
                             mean.append([min((2 * int(vol.rgb[ch, e[2], e[1], e[0]]) + cn) // (2 * cn), 255) for ch in range(3)]
                                         if cn and vol.colour else None)
                         if mean[0] and mean[1]:
-                            col = [int(min(max(np.floor(F(F(F(ma) + F(tt * F(F(mb) - F(ma)))) + F(0.5))), 0), 255)) for ma, mb in zip(*mean)]
+                            mix = [F(np.floor(F(F(F(ma) + F(tt * F(F(mb) - F(ma)))) + F(0.5)))) for ma, mb in zip(*mean)]
+                            col = [0 if x != x else int(min(max(x, 0), 255)) for x in mix]          # a NaN gives 0
                         else:
                             col = mean[0] or mean[1] or [0, 0, 0]
                         cols.append(col)
