@@ -420,6 +420,21 @@ struct SortWorkspace {
     return SortedPairs<K>{k[p], idx[p], idx[p ^ 1], k[p ^ 1]};
   }
 
+  // the same sort for keys that are no cell keys: the n pairs in buffer p by the lowest `bits` bits of their keys -> the buffer that
+  // holds them afterwards
+  template <typename K>
+  int sort_bits(hipStream_t s, unsigned n, int bits, int p) {
+    K* const k[2] = {reinterpret_cast<K*>(keys[0]), reinterpret_cast<K*>(keys[1])};
+    const unsigned ntiles = (n + SORT_TILE - 1) / SORT_TILE;
+    const int passes = (bits + 7) / 8;
+    for (int pass = 0; pass < passes; ++pass, p ^= 1) {
+      hipLaunchKernelGGL(k_vox_hist<K>, dim3(ntiles), dim3(VT), 0, s, k[p], n, 8 * pass, hist, ntiles);
+      hipLaunchKernelGGL(k_vox_scan_digits, dim3(RADIX), dim3(VT), 0, s, hist, ntiles, dtotal);
+      hipLaunchKernelGGL(k_vox_scatter<K>, dim3(ntiles), dim3(VT), 0, s, k[p], idx[p], k[p ^ 1], idx[p ^ 1], n, 8 * pass, hist, dtotal, ntiles);
+    }
+    return p;
+  }
+
   // The stable compaction of the flagged items of a source of at most `items` items, in two calls that may lie in different API calls.
   // count_scan: tile counts -> exclusive tile offsets in bc, the total in slots[slot]; with a tail, tail[total] = tail_val.
   template <class S>

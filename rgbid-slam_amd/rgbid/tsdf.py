@@ -108,6 +108,15 @@ def component_filter_arg(min_component, largest_components):
     return MS.min_triangles_arg(1 if min_component is None else min_component), MS.largest_arg(largest_components)
 
 
+def simplify_arg(simplify):
+    """-> None when simplify is None (no decimation), else the cell (c0, c1, c2) in metres as simplify.simplify_mesh takes it: a finite
+    scalar > 0 or three of them (ValueError otherwise)"""
+    if simplify is None:
+        return None
+    from . import simplify as SP
+    return SP.cell_arg(simplify)
+
+
 def step_arg(step, z_min, z_max):
     """-> the ray cast's sample spacing as the float32 value the library receives: finite, > 0 and with (z_max - z_min) / step <= 65 536
     for the gate's float32 values (ValueError otherwise)"""
@@ -343,14 +352,17 @@ class Volume(_lib.CtxHandle):
         check(self.L.rgbid_tsdf_set_state(self._h, d, c, s))
         self.ctx.sync()
 
-    def extract(self, min_weight=1, colours=True, normals=False, min_component=None, largest_components=None):
+    def extract(self, min_weight=1, colours=True, normals=False, min_component=None, largest_components=None, simplify=None):
         """the surface among the voxels of weight >= min_weight -> (vertices float32 [nv, 3], colours uint8 [nv, 3] or None, triangles
         int32 [nt, 3] holding the uint32 vertex indices) as CUDA tensors; with normals a fourth element, the vertices' world-frame unit
         normals float32 [nv, 3] (0 0 0 where the gradient vanishes).  With min_component (triangles a connected component needs to stay)
         or largest_components (only the k largest stay) the mesh goes through mesh.filter_components and
-        `last_filter` holds its figures; with both None nothing more is done.  Synchronises."""
+        `last_filter` holds its figures; with both None nothing more is done.  With simplify (the cell in metres, a scalar or three
+        values) the mesh, after that filter, is decimated by simplify.simplify_mesh and `last_simplify` holds its
+        figures; with None nothing more is done.  Synchronises."""
         w = weight_arg(min_weight)
         component_filter = component_filter_arg(min_component, largest_components)
+        cell = simplify_arg(simplify)
         nv, nt = C.c_ulonglong(), C.c_ulonglong()
         self.ctx.wait_torch_stream()
         check(self.L.rgbid_tsdf_extract_plan(self._h, w, C.byref(nv), C.byref(nt)))
@@ -366,6 +378,9 @@ class Volume(_lib.CtxHandle):
         if component_filter is not None:
             from . import mesh as MS
             verts, cols, tris, nrm, self.last_filter = MS.filter_components(self.ctx, verts, cols, tris, nrm, *component_filter)
+        if cell is not None:
+            from . import simplify as SP
+            verts, cols, tris, nrm, self.last_simplify = SP.simplify_mesh(self.ctx, verts, cols, tris, nrm, cell=cell)
         return (verts, cols, tris, nrm) if normals else (verts, cols, tris)
 
     def emit_normals(self, normals):
@@ -498,17 +513,19 @@ def cloud_bounds(points, pad=0.0):
 
 
 def fuse(ctx, keyframes, K, rows, cols, bounds=None, voxel=0.02, trunc=None, min_weight=1, z_min=0.05, z_max=20.0, max_voxels=1 << 27,
-         points=None, return_volume=False, normals=False, keep_volume=False, min_component=None, largest_components=None):
+         points=None, return_volume=False, normals=False, keep_volume=False, min_component=None, largest_components=None, simplify=None):
     """one-shot over the keyframes of a run (ChunkCloud.keyframes with `depthinv` and, for a coloured mesh, `colour`): a volume over
     `bounds` = x0 y0 z0 x1 y1 z1 (None: the box of the cloud `points`, padded by trunc) with voxels of `voxel` metres, every keyframe
     integrated in order with its world pose, the surface extracted -> (vertices, colours, triangles) as CUDA tensors, with normals
     also the vertex normals, with return_volume also a dict of the volume's figures (nx, ny, nz, origin, voxels, touched), with
     keep_volume also the open Volume, which the caller closes (in this order).  trunc defaults to 4 voxel.  min_component and
     largest_components are Volume.extract's: with one of them the mesh loses its small connected components and the volume's figures
-    gain `filter`, the components, vertices and triangles before and after."""
+    gain `filter`, the components, vertices and triangles before and after.  simplify is Volume.extract's too: the mesh is decimated by
+    vertex clustering with that cell and the volume's figures gain `simplify`."""
     trunc = 4.0 * voxel if trunc is None else trunc
     w = weight_arg(min_weight)
     component_filter_arg(min_component, largest_components)
+    simplify_arg(simplify)
     if not keyframes:
         raise ValueError("no keyframes to fuse")
     if bounds is None:
@@ -527,12 +544,14 @@ def fuse(ctx, keyframes, K, rows, cols, bounds=None, voxel=0.02, trunc=None, min
             vol.integrate([k["depthinv"] for k in kfs], [k["colour"] for k in kfs] if has_colour else None, np.stack([k["R"] for k in kfs]),
                           np.stack([k["t"] for k in kfs]), K, rows, cols, z_min, z_max)
         filtered = min_component is not None or largest_components is not None
-        mesh = vol.extract(w, colours=True, normals=normals, min_component=min_component, largest_components=largest_components)
+        mesh = vol.extract(w, colours=True, normals=normals, min_component=min_component, largest_components=largest_components, simplify=simplify)
         if return_volume:
             _, counts, _ = vol.state()
             mesh += (dict(nx=nx, ny=ny, nz=nz, origin=origin, voxels=nx * ny * nz, touched=int(((counts & 0xFFFF) != 0).sum().item())),)
             if filtered:
                 mesh[-1]["filter"] = vol.last_filter
+            if simplify is not None:
+                mesh[-1]["simplify"] = vol.last_simplify
         if keep_volume:
             mesh += (vol,)
             vol = None

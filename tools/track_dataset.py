@@ -99,6 +99,9 @@ def main():
                     help="with --mesh: drop the connected components of the mesh with fewer than N triangles (DESIGN.md section 22)")
     ap.add_argument("--mesh-largest-components", type=int, default=None, metavar="K",
                     help="with --mesh: keep only the K connected components of the mesh with the most triangles")
+    ap.add_argument("--mesh-simplify", type=float, default=None, metavar="CELL",
+                    help="with --mesh: decimate the mesh by vertex clustering with cells of CELL metres (DESIGN.md section 23); after the "
+                         "component options when both are given")
     ap.add_argument("--mesh-normals", action="store_true", help="with --mesh: the PLY also holds a unit normal per vertex (nx ny nz)")
     ap.add_argument("--mesh-render", default="", metavar="DIR",
                     help="with --mesh: ray-cast the fused volume at every exported keyframe's pose (DESIGN.md section 20) and write "
@@ -180,6 +183,8 @@ def main():
         ap.error("--mesh-align-iterations needs --mesh-align-check")
     if not args.mesh and (args.mesh_min_component is not None or args.mesh_largest_components is not None):
         ap.error("--mesh-min-component / --mesh-largest-components need --mesh")
+    if not args.mesh and args.mesh_simplify is not None:
+        ap.error("--mesh-simplify needs --mesh")
     mesh_filter = {}
     if args.mesh:
         from rgbid import tsdf as TS
@@ -198,6 +203,8 @@ def main():
                 align_levels = TS.align_levels_arg(tuple((s, n_it) for s in (4, 2, 1)))
             if TS.component_filter_arg(args.mesh_min_component, args.mesh_largest_components) is not None:
                 mesh_filter = dict(min_component=args.mesh_min_component, largest_components=args.mesh_largest_components)
+            if TS.simplify_arg(args.mesh_simplify) is not None:
+                mesh_filter["simplify"] = args.mesh_simplify
         except ValueError as e:
             ap.error(str(e))
     if (args.cloud_radius is None) != (args.cloud_min_neighbours is None):
@@ -353,12 +360,17 @@ def main():
         vol = fused[4 if args.mesh_normals else 3]
         TS.write_mesh_ply(path, verts, cols, tris, fused[3] if args.mesh_normals else None)
         flt = vol.get("filter")             # the line below tells the extraction's counts, the one after it what the filter left
+        simp = vol.get("simplify")          # ... and the third what the decimation made of that
+        first = flt or (dict(vertices=simp["vertices"], triangles=simp["triangles"]) if simp else None)
         print(f"rank {rank}: mesh of {len(pc.keyframes)} keyframes: {vol['nx']} x {vol['ny']} x {vol['nz']} = {vol['voxels']} voxels of {mesh['voxel']:g} m "
-              f"(truncation {mesh['trunc']:g} m), {vol['touched']} touched, {flt['vertices'] if flt else verts.shape[0]} vertices, "
-              f"{flt['triangles'] if flt else tris.shape[0]} triangles -> {path}")
+              f"(truncation {mesh['trunc']:g} m), {vol['touched']} touched, {first['vertices'] if first else verts.shape[0]} vertices, "
+              f"{first['triangles'] if first else tris.shape[0]} triangles -> {path}")
         if flt:
             print(f"rank {rank}: mesh components: {flt['kept_components']} of {flt['components']} kept, {flt['vertices']} -> {flt['kept_vertices']} vertices, "
                   f"{flt['triangles']} -> {flt['kept_triangles']} triangles")
+        if simp:
+            print(f"rank {rank}: mesh simplify: {simp['clusters']} clusters of {args.mesh_simplify:g} m, triangles {simp['lost']} lost, {simp['collapsed']} collapsed, "
+                  f"{simp['duplicate']} duplicate, {simp['kept']} kept, {simp['vertices']} -> {simp['out_vertices']} vertices")
         if cast:
             volume = fused[-1]
             try:
