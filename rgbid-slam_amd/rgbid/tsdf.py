@@ -117,6 +117,24 @@ def simplify_arg(simplify):
     return SP.cell_arg(simplify)
 
 
+def smooth_arg(smooth):
+    """-> None when smooth is None (no smoothing), else dict(iterations, lam, mu, pin_boundary) as smooth.smooth_mesh takes them: smooth an
+    iteration count in 0 .. 4096 or a dict with `iterations` and any of lam (0 < lam <= 1, default 0.5), mu (-2 <= mu <= 0, default -0.53),
+    pin_boundary (default False) (ValueError otherwise)"""
+    if smooth is None:
+        return None
+    from . import smooth as SO
+    kw = dict(smooth) if isinstance(smooth, dict) else dict(iterations=smooth)
+    unknown = sorted(set(kw) - {"iterations", "lam", "mu", "pin_boundary"})
+    if unknown or "iterations" not in kw:
+        raise ValueError(f"smooth: an iteration count or a dict with iterations and any of lam, mu, pin_boundary, got {smooth!r}")
+    lam, mu = SO.factors_arg(kw.get("lam", 0.5), kw.get("mu", -0.53))
+    pin = kw.get("pin_boundary", False)
+    if not isinstance(pin, (bool, np.bool_)):
+        raise ValueError(f"smooth: pin_boundary is True or False, got {pin!r}")
+    return dict(iterations=SO.iterations_arg(kw["iterations"]), lam=lam, mu=mu, pin_boundary=bool(pin))
+
+
 def step_arg(step, z_min, z_max):
     """-> the ray cast's sample spacing as the float32 value the library receives: finite, > 0 and with (z_max - z_min) / step <= 65 536
     for the gate's float32 values (ValueError otherwise)"""
@@ -352,17 +370,22 @@ class Volume(_lib.CtxHandle):
         check(self.L.rgbid_tsdf_set_state(self._h, d, c, s))
         self.ctx.sync()
 
-    def extract(self, min_weight=1, colours=True, normals=False, min_component=None, largest_components=None, simplify=None):
+    def extract(self, min_weight=1, colours=True, normals=False, min_component=None, largest_components=None, simplify=None,
+                smooth=None):
         """the surface among the voxels of weight >= min_weight -> (vertices float32 [nv, 3], colours uint8 [nv, 3] or None, triangles
         int32 [nt, 3] holding the uint32 vertex indices) as CUDA tensors; with normals a fourth element, the vertices' world-frame unit
         normals float32 [nv, 3] (0 0 0 where the gradient vanishes).  With min_component (triangles a connected component needs to stay)
         or largest_components (only the k largest stay) the mesh goes through mesh.filter_components and
         `last_filter` holds its figures; with both None nothing more is done.  With simplify (the cell in metres, a scalar or three
         values) the mesh, after that filter, is decimated by simplify.simplify_mesh and `last_simplify` holds its
-        figures; with None nothing more is done.  Synchronises."""
+        figures; with None nothing more is done.  With smooth (an iteration count, or a dict of iterations, lam, mu, pin_boundary) the
+        vertices of the mesh, after both, are moved by smooth.smooth_mesh (Taubin's filter), the normals are
+        recomputed from the smoothed triangles (area-weighted) and `last_smooth` holds its figures; with None nothing more is done.
+        Synchronises."""
         w = weight_arg(min_weight)
         component_filter = component_filter_arg(min_component, largest_components)
         cell = simplify_arg(simplify)
+        fairing = smooth_arg(smooth)
         nv, nt = C.c_ulonglong(), C.c_ulonglong()
         self.ctx.wait_torch_stream()
         check(self.L.rgbid_tsdf_extract_plan(self._h, w, C.byref(nv), C.byref(nt)))
@@ -381,6 +404,9 @@ class Volume(_lib.CtxHandle):
         if cell is not None:
             from . import simplify as SP
             verts, cols, tris, nrm, self.last_simplify = SP.simplify_mesh(self.ctx, verts, cols, tris, nrm, cell=cell)
+        if fairing is not None:
+            from . import smooth as SO
+            verts, nrm, self.last_smooth = SO.smooth_mesh(self.ctx, verts, tris, normals=normals, **fairing)
         return (verts, cols, tris, nrm) if normals else (verts, cols, tris)
 
     def emit_normals(self, normals):
@@ -513,7 +539,8 @@ def cloud_bounds(points, pad=0.0):
 
 
 def fuse(ctx, keyframes, K, rows, cols, bounds=None, voxel=0.02, trunc=None, min_weight=1, z_min=0.05, z_max=20.0, max_voxels=1 << 27,
-         points=None, return_volume=False, normals=False, keep_volume=False, min_component=None, largest_components=None, simplify=None):
+         points=None, return_volume=False, normals=False, keep_volume=False, min_component=None, largest_components=None, simplify=None,
+         smooth=None):
     """one-shot over the keyframes of a run (ChunkCloud.keyframes with `depthinv` and, for a coloured mesh, `colour`): a volume over
     `bounds` = x0 y0 z0 x1 y1 z1 (None: the box of the cloud `points`, padded by trunc) with voxels of `voxel` metres, every keyframe
     integrated in order with its world pose, the surface extracted -> (vertices, colours, triangles) as CUDA tensors, with normals
@@ -521,11 +548,13 @@ def fuse(ctx, keyframes, K, rows, cols, bounds=None, voxel=0.02, trunc=None, min
     keep_volume also the open Volume, which the caller closes (in this order).  trunc defaults to 4 voxel.  min_component and
     largest_components are Volume.extract's: with one of them the mesh loses its small connected components and the volume's figures
     gain `filter`, the components, vertices and triangles before and after.  simplify is Volume.extract's too: the mesh is decimated by
-    vertex clustering with that cell and the volume's figures gain `simplify`."""
+    vertex clustering with that cell and the volume's figures gain `simplify`.  smooth is Volume.extract's as well: the vertices are moved
+    by Taubin's filter last, the normals are those of the smoothed surface and the volume's figures gain `smooth`."""
     trunc = 4.0 * voxel if trunc is None else trunc
     w = weight_arg(min_weight)
     component_filter_arg(min_component, largest_components)
     simplify_arg(simplify)
+    smooth_arg(smooth)
     if not keyframes:
         raise ValueError("no keyframes to fuse")
     if bounds is None:
@@ -544,7 +573,8 @@ def fuse(ctx, keyframes, K, rows, cols, bounds=None, voxel=0.02, trunc=None, min
             vol.integrate([k["depthinv"] for k in kfs], [k["colour"] for k in kfs] if has_colour else None, np.stack([k["R"] for k in kfs]),
                           np.stack([k["t"] for k in kfs]), K, rows, cols, z_min, z_max)
         filtered = min_component is not None or largest_components is not None
-        mesh = vol.extract(w, colours=True, normals=normals, min_component=min_component, largest_components=largest_components, simplify=simplify)
+        mesh = vol.extract(w, colours=True, normals=normals, min_component=min_component, largest_components=largest_components, simplify=simplify,
+                           smooth=smooth)
         if return_volume:
             _, counts, _ = vol.state()
             mesh += (dict(nx=nx, ny=ny, nz=nz, origin=origin, voxels=nx * ny * nz, touched=int(((counts & 0xFFFF) != 0).sum().item())),)
@@ -552,6 +582,8 @@ def fuse(ctx, keyframes, K, rows, cols, bounds=None, voxel=0.02, trunc=None, min
                 mesh[-1]["filter"] = vol.last_filter
             if simplify is not None:
                 mesh[-1]["simplify"] = vol.last_simplify
+            if smooth is not None:
+                mesh[-1]["smooth"] = vol.last_smooth
         if keep_volume:
             mesh += (vol,)
             vol = None

@@ -102,6 +102,13 @@ def main():
     ap.add_argument("--mesh-simplify", type=float, default=None, metavar="CELL",
                     help="with --mesh: decimate the mesh by vertex clustering with cells of CELL metres (DESIGN.md section 23); after the "
                          "component options when both are given")
+    ap.add_argument("--mesh-smooth", type=int, default=None, metavar="N",
+                    help="with --mesh: move the vertices by N iterations of Taubin's filter (DESIGN.md section 24), after the component and "
+                         "simplify options; with --mesh-normals the normals are those of the smoothed surface")
+    ap.add_argument("--mesh-smooth-lambda", type=float, default=None, metavar="L", help="with --mesh-smooth: the positive factor, 0 < L <= 1 (default 0.5)")
+    ap.add_argument("--mesh-smooth-mu", type=float, default=None, metavar="M",
+                    help="with --mesh-smooth: the negative factor, -2 <= M <= 0 (default -0.53; 0: plain Laplacian smoothing)")
+    ap.add_argument("--mesh-smooth-pin-boundary", action="store_true", help="with --mesh-smooth: the vertices on a boundary of the mesh do not move")
     ap.add_argument("--mesh-normals", action="store_true", help="with --mesh: the PLY also holds a unit normal per vertex (nx ny nz)")
     ap.add_argument("--mesh-render", default="", metavar="DIR",
                     help="with --mesh: ray-cast the fused volume at every exported keyframe's pose (DESIGN.md section 20) and write "
@@ -185,6 +192,10 @@ def main():
         ap.error("--mesh-min-component / --mesh-largest-components need --mesh")
     if not args.mesh and args.mesh_simplify is not None:
         ap.error("--mesh-simplify needs --mesh")
+    if not args.mesh and args.mesh_smooth is not None:
+        ap.error("--mesh-smooth needs --mesh")
+    if args.mesh_smooth is None and (args.mesh_smooth_lambda is not None or args.mesh_smooth_mu is not None or args.mesh_smooth_pin_boundary):
+        ap.error("--mesh-smooth-lambda / --mesh-smooth-mu / --mesh-smooth-pin-boundary need --mesh-smooth")
     mesh_filter = {}
     if args.mesh:
         from rgbid import tsdf as TS
@@ -205,6 +216,10 @@ def main():
                 mesh_filter = dict(min_component=args.mesh_min_component, largest_components=args.mesh_largest_components)
             if TS.simplify_arg(args.mesh_simplify) is not None:
                 mesh_filter["simplify"] = args.mesh_simplify
+            if args.mesh_smooth is not None:
+                mesh_filter["smooth"] = TS.smooth_arg(dict(iterations=args.mesh_smooth, lam=0.5 if args.mesh_smooth_lambda is None else args.mesh_smooth_lambda,
+                                                           mu=-0.53 if args.mesh_smooth_mu is None else args.mesh_smooth_mu,
+                                                           pin_boundary=args.mesh_smooth_pin_boundary))
         except ValueError as e:
             ap.error(str(e))
     if (args.cloud_radius is None) != (args.cloud_min_neighbours is None):
@@ -371,6 +386,10 @@ def main():
         if simp:
             print(f"rank {rank}: mesh simplify: {simp['clusters']} clusters of {args.mesh_simplify:g} m, triangles {simp['lost']} lost, {simp['collapsed']} collapsed, "
                   f"{simp['duplicate']} duplicate, {simp['kept']} kept, {simp['vertices']} -> {simp['out_vertices']} vertices")
+        smo = vol.get("smooth")
+        if smo:
+            print(f"rank {rank}: mesh smooth: {smo['iterations']} iterations of lambda {smo['lam']:g}, mu {smo['mu']:g}, {smo['edges']} edges, "
+                  f"{smo['boundary_vertices']} boundary vertices, {'pinned' if smo['pin_boundary'] else 'not pinned'}")
         if cast:
             volume = fused[-1]
             try:
