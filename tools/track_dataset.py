@@ -117,6 +117,12 @@ def main():
                     help="with --mesh: print how well the fused surface, ray-cast at each keyframe's pose, agrees with the depth the keyframe measured")
     ap.add_argument("--mesh-render-step", type=float, default=None, metavar="S",
                     help="with --mesh-render / --mesh-render-check: metres of camera depth between two samples of a ray (default: the voxel size)")
+    ap.add_argument("--mesh-raster", default="", metavar="DIR",
+                    help="with --mesh: rasterise the mesh that is written, after all clean-up options, at every exported keyframe's pose "
+                         "(DESIGN.md section 25) and write mesh_NNNN.png (colour), mesh_NNNN_depth.png (16-bit, metres x 5000, empty = 0) and, with "
+                         "--mesh-normals, mesh_NNNN_shaded.png into DIR")
+    ap.add_argument("--mesh-raster-check", action="store_true",
+                    help="with --mesh: print how well the written mesh, rasterised at each keyframe's pose, agrees with the depth the keyframe measured")
     ap.add_argument("--mesh-align-check", action="store_true",
                     help="with --mesh: fuse the even-numbered keyframes, align the odd-numbered ones to that model (DESIGN.md section 21) and print "
                          "the corrections the alignment proposes; nothing is applied")
@@ -184,6 +190,8 @@ def main():
         ap.error("--mesh-normals / --mesh-render / --mesh-render-check / --mesh-render-step need --mesh")
     if args.mesh_render_step is not None and not (args.mesh_render or args.mesh_render_check):
         ap.error("--mesh-render-step needs --mesh-render or --mesh-render-check")
+    if not args.mesh and (args.mesh_raster or args.mesh_raster_check):
+        ap.error("--mesh-raster / --mesh-raster-check need --mesh")
     if not args.mesh and (args.mesh_align_check or args.mesh_align_iterations is not None):
         ap.error("--mesh-align-check / --mesh-align-iterations need --mesh")
     if args.mesh_align_iterations is not None and not args.mesh_align_check:
@@ -414,6 +422,39 @@ def main():
                     print(f"rank {rank}: {len(kfs_all)} ray-cast views of the volume -> {args.mesh_render}")
             finally:
                 volume.close()
+        if args.mesh_raster or args.mesh_raster_check:
+            from rgbid import raster as RS
+            from rgbid import render as RD
+            Kt, kfs_all = tuple(args.K), pc.keyframes
+            try:
+                if args.mesh_raster_check:
+                    figures = RS.mesh_agreement(ctx, verts, tris, kfs_all, Kt, args.rows, args.cols)
+                    for i, f in enumerate(figures):
+                        print(f"rank {rank}: mesh raster check: keyframe {i}: {f['pixels']} pixels, median {f['median']:.6f} m, 90 % {f['p90']:.6f} m")
+                    run = RD.agreement_summary(figures)
+                    print(f"rank {rank}: mesh raster check: {len(figures)} keyframes, {run['pixels']} pixels, median of medians {run['median']:.6f} m, "
+                          f"largest 90 % {run['p90']:.6f} m")
+                if args.mesh_raster:
+                    os.makedirs(args.mesh_raster, exist_ok=True)
+                    nrm = fused[3] if args.mesh_normals else None
+                    outs = ("depth", "colour", "normal") if args.mesh_normals else ("depth", "colour")
+                    rs = RS.Rasteriser(ctx, max(verts.shape[0], 1), max(tris.shape[0], 1), args.rows * args.cols * min(RS.VIEW_CHUNK, len(kfs_all)))
+                    try:
+                        for a in range(0, len(kfs_all), RS.VIEW_CHUNK):
+                            kfs = kfs_all[a:a + RS.VIEW_CHUNK]
+                            views = rs.render(verts, tris, np.stack([k["R"] for k in kfs]), np.stack([k["t"] for k in kfs]), Kt, args.rows, args.cols,
+                                              cols, nrm, outputs=outs)
+                            for j in range(len(kfs)):
+                                name = f"mesh_{a + j:04d}" if world == 1 else f"mesh_rank{rank}_{a + j:04d}"
+                                tum.write_png(os.path.join(args.mesh_raster, name + ".png"), views["colour"][j].cpu().numpy())
+                                tum.write_png(os.path.join(args.mesh_raster, name + "_depth.png"), RD.depth_png(views["depth"][j]))
+                                if args.mesh_normals:
+                                    tum.write_png(os.path.join(args.mesh_raster, name + "_shaded.png"), TS.shade(views["normal"][j]))
+                    finally:
+                        rs.close()
+                    print(f"rank {rank}: {len(kfs_all)} rasterised views of the mesh -> {args.mesh_raster}")
+            except ValueError as e:
+                sys.exit(f"rank {rank}: --mesh-raster: {e}")
         if args.mesh_align_check:
             try:
                 figures = TS.align_check(ctx, pc.keyframes, tuple(args.K), args.rows, args.cols, points=pc.points, levels=align_levels, **mesh)
