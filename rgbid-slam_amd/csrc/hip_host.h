@@ -1,5 +1,5 @@
 // hip_host.h -- the host-side plumbing every C-ABI handle shares: one status path, one allocation function, one owner of a handle's
-// buffers, one destroy, one stage timer.  Host code only; a new feature file takes these instead of writing its own.
+// buffers, one destroy, one stage timer and its read-out, one alignment test.  Host code only; a new feature file takes these instead of writing its own.
 #pragma once
 #include "../../include/rgbid.h"
 #include "ctx.h"
@@ -85,5 +85,22 @@ struct StageTimer {
   StageTimer& operator=(const StageTimer&) = delete;
   ~StageTimer() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
 };
+
+// the ms[] of a *_timing call: stage k is the time between the events of pairs[k] = {a, b, c, d}, [a, b] plus [c, d] where c < d; 0 for a
+// stage that the last call did not record
+template <int N, int S>
+int stage_times(const StageTimer<N>& t, const bool (&timed)[S], const int (&pairs)[S][4], float* ms) {
+  for (int k = 0; k < S; ++k) ms[k] = 0.f;
+  for (int k = 0; k < S; ++k)
+    for (int j = 0; j < 4 && timed[k] && pairs[k][j] < pairs[k][j + 1]; j += 2) {
+      float one = 0.f;
+      RGBID_HIP(t.elapsed(pairs[k][j], pairs[k][j + 1], &one));
+      ms[k] += one;
+    }
+  return RGBID_OK;
+}
+
+// what every C-ABI asks of a device array of 32-bit words; null passes (whether null is allowed is the caller's test)
+inline bool aligned4(const void* p) { return !(((uintptr_t)p) & 3); }
 
 }  // namespace rgbid

@@ -2,8 +2,8 @@
 // mask, and the kept part written out with renumbered indices (include/rgbid_mesh.h).
 //
 // The judge is tests/mesh_mirror.py; table, labels, counts and every emitted buffer are byte-identical to it.
-//   label   k_mesh_check      counts the triangles with an index >= n_v into a slot; every later kernel of the call reads that slot first
-//                             and does nothing when it is not 0
+//   label   k_mesh_check      mesh_device.h: counts the triangles with an index >= n_v into a slot; every later kernel of the call reads
+//                             that slot first and does nothing when it is not 0
 //           k_mesh_init       parent[v] = v, the counts per root = 0
 //           k_mesh_unite      one thread per triangle: unite(i0, i1), unite(i1, i2).  A lock-free union-find: find walks parent down to a
 //                             root (path splitting on the way), the larger of two roots is hooked under the smaller with one atomicCAS,
@@ -34,9 +34,7 @@
 #include "../../include/rgbid_mesh.h"
 #include "common.h"
 #include "hip_host.h"
-#include "voxel_device.h"   // flag compaction, the one-block scan, grid_of
-
-#include <new>
+#include "mesh_device.h"    // the index check, the argument test, the create; voxel_device.h's flag compaction, one-block scan, grid_of
 
 using namespace rgbid;
 
@@ -100,16 +98,6 @@ __device__ __forceinline__ void wave_add_by_key(unsigned* __restrict__ counts, b
 __device__ __forceinline__ bool well_formed(const unsigned* __restrict__ tri, size_t t, unsigned n_v, unsigned& i0, unsigned& i1, unsigned& i2) {
   i0 = tri[3 * t]; i1 = tri[3 * t + 1]; i2 = tri[3 * t + 2];
   return i0 < n_v && i1 < n_v && i2 < n_v;
-}
-
-__global__ __launch_bounds__(VT) void k_mesh_check(const unsigned* __restrict__ tri, unsigned n_t, unsigned n_v, unsigned* __restrict__ bad) {
-  unsigned c = 0;
-  for (size_t t = (size_t)blockIdx.x * VT + threadIdx.x; t < n_t; t += (size_t)gridDim.x * VT) {
-    unsigned i0, i1, i2;
-    if (!well_formed(tri, t, n_v, i0, i1, i2)) ++c;
-  }
-  c = wave_sum(c);
-  if ((threadIdx.x & 63) == 0 && c) atomicAdd(bad, c);
 }
 
 __global__ __launch_bounds__(VT) void k_mesh_init(unsigned n_v, unsigned* __restrict__ parent, unsigned* __restrict__ vcount, unsigned* __restrict__ tcount,
@@ -218,8 +206,7 @@ __global__ __launch_bounds__(VT) void k_mesh_mark(unsigned n_v, const unsigned* 
     remap[v] = keep ? 0u : DROPPED;
     if (keep && r == (unsigned)v) ++c;
   }
-  c = wave_sum(c);
-  if ((threadIdx.x & 63) == 0 && c) atomicAdd(kept_components, c);
+  wave_add_to(kept_components, c);
 }
 
 // stable compaction of the kept vertices: remap[v] = its rank, in place (a thread reads and writes its own entry only)
@@ -264,8 +251,6 @@ struct TriangleSrc {
   }
 };
 
-bool aligned4(const void* p) { return !(((uintptr_t)p) & 3); }
-
 }  // namespace
 
 struct rgbid_mesh {
@@ -295,29 +280,19 @@ struct rgbid_mesh {
 extern "C" {
 
 int rgbid_mesh_create(rgbid_mesh** out, rgbid_ctx* ctx, unsigned long long max_vertices, unsigned long long max_triangles) {
-  if (!out) return RGBID_E_INVALID;
-  *out = nullptr;
-  if (!ctx || max_vertices < 1 || max_vertices > RGBID_MESH_MAX_VERTICES) return RGBID_E_INVALID;
-  if (max_triangles < 1 || max_triangles > RGBID_MESH_MAX_TRIANGLES) return RGBID_E_INVALID;
-  (void)hipSetDevice(ctx->device);
-  rgbid_mesh* m = new (std::nothrow) rgbid_mesh;
-  if (!m) return RGBID_E_NOMEM;
-  m->ctx = ctx;
-  m->cap_v = max_vertices;
-  m->cap_t = max_triangles;
-  const size_t cv = (size_t)max_vertices;
-  int r = m->ws.alloc_compaction(m->buf, max_vertices);
-  m->bc_root = m->ws.bc;
-  if (!r) r = m->buf.alloc(&m->bc_vert, sizeof(unsigned) * ((cv + RUN_TILE - 1) / RUN_TILE));
-  if (!r) r = m->buf.alloc(&m->bc_tri, sizeof(unsigned) * (((size_t)max_triangles + RUN_TILE - 1) / RUN_TILE));
-  if (!r) r = m->buf.alloc(&m->parent, sizeof(unsigned) * cv);
-  if (!r) r = m->buf.alloc(&m->vcount, sizeof(unsigned) * cv);
-  if (!r) r = m->buf.alloc(&m->tcount, sizeof(unsigned) * cv);
-  if (!r) r = m->buf.alloc(&m->number, sizeof(unsigned) * cv);
-  if (!r) r = m->buf.alloc(&m->remap, sizeof(unsigned) * cv);
-  if (r) { rgbid_mesh_destroy(m); return r; }
-  *out = m;
-  return RGBID_OK;
+  return mesh_create(out, ctx, max_vertices, max_triangles, RGBID_MESH_MAX_VERTICES, RGBID_MESH_MAX_TRIANGLES, [&](rgbid_mesh* m) {
+    const size_t cv = (size_t)max_vertices;
+    int r = m->ws.alloc_compaction(m->buf, max_vertices);
+    m->bc_root = m->ws.bc;
+    if (!r) r = m->buf.alloc(&m->bc_vert, sizeof(unsigned) * ((cv + RUN_TILE - 1) / RUN_TILE));
+    if (!r) r = m->buf.alloc(&m->bc_tri, sizeof(unsigned) * (((size_t)max_triangles + RUN_TILE - 1) / RUN_TILE));
+    if (!r) r = m->buf.alloc(&m->parent, sizeof(unsigned) * cv);
+    if (!r) r = m->buf.alloc(&m->vcount, sizeof(unsigned) * cv);
+    if (!r) r = m->buf.alloc(&m->tcount, sizeof(unsigned) * cv);
+    if (!r) r = m->buf.alloc(&m->number, sizeof(unsigned) * cv);
+    if (!r) r = m->buf.alloc(&m->remap, sizeof(unsigned) * cv);
+    return r;
+  });
 }
 
 int rgbid_mesh_destroy(rgbid_mesh* m) { return destroy_handle(m); }   // a launch may still read the tables
@@ -326,8 +301,7 @@ int rgbid_mesh_label(rgbid_mesh* m, unsigned long long n_vertices, unsigned long
                      unsigned long long* n_components) {
   if (!m || !n_components) return RGBID_E_INVALID;
   *n_components = 0;
-  if (n_vertices > m->cap_v || n_triangles > m->cap_t) return RGBID_E_INVALID;
-  if (n_triangles && (!triangles_dev || !aligned4(triangles_dev) || n_vertices == 0)) return RGBID_E_INVALID;
+  if (!mesh_in_ok(n_vertices, n_triangles, triangles_dev, m->cap_v, m->cap_t)) return RGBID_E_INVALID;
   (void)hipSetDevice(m->ctx->device);
   hipStream_t s = m->ctx->stream;
   m->labelled = m->selected = false;
@@ -339,7 +313,7 @@ int rgbid_mesh_label(rgbid_mesh* m, unsigned long long n_vertices, unsigned long
   unsigned* bad = m->ws.slots + SLOT_BAD;
   m->mark(0);
   RGBID_HIP(hipMemsetAsync(m->ws.slots, 0, sizeof(unsigned) * SLOTS, s));
-  if (n_t) hipLaunchKernelGGL(k_mesh_check, dim3(gt), dim3(VT), 0, s, triangles_dev, n_t, n_v, bad);
+  if (n_t) check_triangles(s, triangles_dev, n_t, n_v, bad);
   hipLaunchKernelGGL(k_mesh_init, dim3(gv), dim3(VT), 0, s, n_v, m->parent, m->vcount, m->tcount, bad);
   if (n_t) hipLaunchKernelGGL(k_mesh_unite, dim3(gt), dim3(VT), 0, s, triangles_dev, n_t, n_v, m->parent, bad);
   if (n_t) hipLaunchKernelGGL(k_mesh_compress, dim3(gv), dim3(VT), 0, s, n_v, m->parent, bad);
@@ -433,11 +407,9 @@ int rgbid_mesh_emit(rgbid_mesh* m, const float* vertices_dev, const uint8_t* col
 int rgbid_mesh_timing(rgbid_mesh* m, int enable, float ms[3]) {
   if (!m) return RGBID_E_INVALID;
   (void)hipSetDevice(m->ctx->device);
+  static const int pairs[3][4] = {{0, 1}, {2, 3}, {4, 5}};
   if (ms)
-    for (int k = 0; k < 3; ++k) {
-      ms[k] = 0.f;
-      if (m->timed[k]) RGBID_HIP(m->timer.elapsed(2 * k, 2 * k + 1, &ms[k]));
-    }
+    if (int r = stage_times(m->timer, m->timed, pairs, ms)) return r;
   return m->timer.enable(enable != 0);
 }
 

@@ -165,7 +165,7 @@ int sort_and_count(rgbid_outlier* o, const float4* in, unsigned n, unsigned fini
   hipStream_t s = o->ctx->stream;
   SortWorkspace& w = o->ws;
   o->mark(2);
-  w.make_keys<K>(s, in, n, og.g);
+  w.make_keys<K>(s, RecordPoints{in}, n, og.g);
   const SortedPairs<K> sp = w.sort<K>(s, n, og.g);
   o->mark(3);
   hipLaunchKernelGGL(k_outlier_gather, dim3((finite + VT - 1) / VT), dim3(VT), 0, s, in, sp.idx, finite, o->spos);
@@ -223,7 +223,7 @@ int rgbid_outlier_plan(rgbid_outlier* o, const rgbid_cloud_point* in_dev, unsign
   const unsigned nu = (unsigned)n;
   o->plan_timed = false; o->emit_timed = false;
   o->mark(0);
-  o->ws.box(s, in, nu);
+  o->ws.box(s, RecordPoints{in}, nu);
   o->mark(1);
   unsigned finite;
   float lo[3], hi[3];

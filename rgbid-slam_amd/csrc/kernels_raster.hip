@@ -1,7 +1,7 @@
 // kernels_raster.hip -- an indexed triangle mesh seen from camera poses (include/rgbid_raster.h).
 //
 // The judge is tests/raster_mirror.py; every plane and the six counts per view are byte-identical to it.
-//   k_rast_check    counts the triangles with an index >= n_v into one slot, copied to the host: a bad index ends the call here
+//   k_mesh_check    mesh_device.h: counts the triangles with an index >= n_v into one slot, copied to the host: a bad index ends the call here
 //   k_rast_clear    the key buffer [V][rows][cols] of uint64 is set to all ones, 16 bytes per store
 // then per chunk of up to RGBID_RASTER_VIEW_CHUNK views, their twelve floats each in the kernel arguments:
 //   k_rast_project  one thread per vertex, the chunk's views in an inner loop: the 16-byte record xs, ys, Z, usable per (view, vertex)
@@ -20,10 +20,9 @@
 #include "../../include/rgbid_raster.h"
 #include "common.h"
 #include "hip_host.h"
-#include "voxel_device.h"   // VT, grid_of, the stable flag compaction
+#include "mesh_device.h"    // the index check, the argument test, the create; voxel_device.h's VT, grid_of, the stable flag compaction
 
 #include <cmath>
-#include <new>
 
 using namespace rgbid;
 
@@ -60,16 +59,6 @@ struct RasterVertex {                                       // the record of ste
   unsigned usable;
 };
 static_assert(sizeof(RasterVertex) == 16, "one 16-byte load");
-
-__global__ __launch_bounds__(VT) void k_rast_check(const unsigned* __restrict__ tri, unsigned n_t, unsigned n_v, unsigned* __restrict__ slots) {
-  unsigned bad = 0;
-  for (size_t t = (size_t)blockIdx.x * VT + threadIdx.x; t < n_t; t += (size_t)gridDim.x * VT) {
-    const unsigned a = tri[3 * t], b = tri[3 * t + 1], c = tri[3 * t + 2];
-    if (!(a < n_v && b < n_v && c < n_v)) ++bad;
-  }
-  bad = wave_sum(bad);
-  if ((threadIdx.x & 63) == 0 && bad) atomicAdd(slots + SLOT_BAD, bad);
-}
 
 __global__ __launch_bounds__(VT) void k_rast_clear(uint4* __restrict__ keys, size_t n16) {
   const size_t i = (size_t)blockIdx.x * VT + threadIdx.x;
@@ -273,8 +262,7 @@ __global__ __launch_bounds__(VT) void k_rast_large(const unsigned* __restrict__ 
       const int px = cx0 + (lane & (TILE - 1)), py = cy0 + (lane >> 3);
       if (px >= x0 && px <= x1 && py >= y0 && py <= y1) frags += raster_pixel(tr, t, px, py, view, cam.cols) ? 1u : 0u;
     }
-    frags = wave_sum(frags);
-    if (lane == 0 && frags) atomicAdd(count_line(counts, v) + C_FRAGMENTS, (unsigned long long)frags);
+    wave_add_to(count_line(counts, v) + C_FRAGMENTS, frags);
   }
 }
 
@@ -366,8 +354,6 @@ bool finite_all(const double* p, int n) {
   return true;
 }
 
-bool aligned4(const void* p) { return !(((uintptr_t)p) & 3); }
-
 constexpr int MARKS = 5;                                    // per chunk: project [0, 1], setup + small [1, 2], large [2, 3], resolve [3, 4]
 
 }  // namespace
@@ -391,30 +377,21 @@ extern "C" {
 
 int rgbid_raster_create(rgbid_raster** out, rgbid_ctx* ctx, unsigned long long max_vertices, unsigned long long max_triangles,
                         unsigned long long max_pixels_times_views) {
-  if (!out) return RGBID_E_INVALID;
-  *out = nullptr;
-  if (!ctx || max_vertices < 1 || max_vertices > RGBID_RASTER_MAX_VERTICES) return RGBID_E_INVALID;
-  if (max_triangles < 1 || max_triangles > RGBID_RASTER_MAX_TRIANGLES) return RGBID_E_INVALID;
+  if (out) *out = nullptr;                     // also when the pixel capacity is refused
   if (max_pixels_times_views == 0 || max_pixels_times_views > MAX_PIXEL_VIEWS) return RGBID_E_INVALID;
-  (void)hipSetDevice(ctx->device);
-  rgbid_raster* r = new (std::nothrow) rgbid_raster;
-  if (!r) return RGBID_E_NOMEM;
-  r->ctx = ctx;
-  r->cap_v = max_vertices;
-  r->cap_t = max_triangles;
-  r->cap_pix = max_pixels_times_views;
-  const size_t cv = (size_t)max_vertices, ct = (size_t)max_triangles;
-  const unsigned long long pairs = (unsigned long long)RGBID_RASTER_VIEW_CHUNK * max_triangles;   // a chunk is shortened to 2^32 - 1 pairs
-  int e = r->w.alloc_compaction(r->buf, pairs < 0xFFFFFFFFull ? pairs : 0xFFFFFFFFull);
-  if (!e) e = r->buf.alloc(&r->keys, sizeof(unsigned long long) * (size_t)((max_pixels_times_views + 1) & ~1ull));   // whole 16-byte stores
-  if (!e) e = r->buf.alloc(&r->rec, sizeof(RasterVertex) * RGBID_RASTER_VIEW_CHUNK * cv);
-  if (!e) e = r->buf.alloc(&r->flags, (size_t)RGBID_RASTER_VIEW_CHUNK * ct);
-  if (!e) e = r->buf.alloc(&r->list, sizeof(unsigned) * RGBID_RASTER_VIEW_CHUNK * ct);
-  if (!e) e = r->buf.alloc(&r->counts, sizeof(unsigned long long) * N_COUNTS * RGBID_RASTER_MAX_VIEWS);
-  if (!e) e = r->buf.alloc(&r->parts, sizeof(unsigned long long) * COUNT_LINE * COUNT_SLOTS * RGBID_RASTER_MAX_VIEWS);
-  if (e) { rgbid_raster_destroy(r); return e; }
-  *out = r;
-  return RGBID_OK;
+  return mesh_create(out, ctx, max_vertices, max_triangles, RGBID_RASTER_MAX_VERTICES, RGBID_RASTER_MAX_TRIANGLES, [&](rgbid_raster* r) {
+    r->cap_pix = max_pixels_times_views;
+    const size_t cv = (size_t)max_vertices, ct = (size_t)max_triangles;
+    const unsigned long long pairs = (unsigned long long)RGBID_RASTER_VIEW_CHUNK * max_triangles;   // a chunk is shortened to 2^32 - 1 pairs
+    int e = r->w.alloc_compaction(r->buf, pairs < 0xFFFFFFFFull ? pairs : 0xFFFFFFFFull);
+    if (!e) e = r->buf.alloc(&r->keys, sizeof(unsigned long long) * (size_t)((max_pixels_times_views + 1) & ~1ull));   // whole 16-byte stores
+    if (!e) e = r->buf.alloc(&r->rec, sizeof(RasterVertex) * RGBID_RASTER_VIEW_CHUNK * cv);
+    if (!e) e = r->buf.alloc(&r->flags, (size_t)RGBID_RASTER_VIEW_CHUNK * ct);
+    if (!e) e = r->buf.alloc(&r->list, sizeof(unsigned) * RGBID_RASTER_VIEW_CHUNK * ct);
+    if (!e) e = r->buf.alloc(&r->counts, sizeof(unsigned long long) * N_COUNTS * RGBID_RASTER_MAX_VIEWS);
+    if (!e) e = r->buf.alloc(&r->parts, sizeof(unsigned long long) * COUNT_LINE * COUNT_SLOTS * RGBID_RASTER_MAX_VIEWS);
+    return e;
+  });
 }
 
 int rgbid_raster_destroy(rgbid_raster* r) { return destroy_handle(r); }   // a resolve may still read the tables
@@ -430,9 +407,8 @@ int rgbid_raster_views(rgbid_raster* r, const float* vertices_dev, unsigned long
   if (!(std::isfinite(z_min) && std::isfinite(z_max) && z_min > 0.f && z_min <= z_max)) return RGBID_E_INVALID;
   for (int k = 0; k < 4; ++k) if (!std::isfinite(K[k])) return RGBID_E_INVALID;
   if (K[0] == 0.f || K[1] == 0.f) return RGBID_E_INVALID;
-  if (n_vertices > r->cap_v || n_triangles > r->cap_t) return RGBID_E_INVALID;
+  if (!mesh_in_ok(n_vertices, n_triangles, triangles_dev, r->cap_v, r->cap_t)) return RGBID_E_INVALID;
   if (n_vertices && (!vertices_dev || !aligned4(vertices_dev))) return RGBID_E_INVALID;
-  if (n_triangles && (!triangles_dev || !aligned4(triangles_dev) || n_vertices == 0)) return RGBID_E_INVALID;
   if (!aligned4(normals_dev) || !aligned4(index_dev) || !aligned4(depth_dev) || !aligned4(normal_dev)) return RGBID_E_INVALID;
   if (n_vertices && ((colour_dev && !colours_dev) || (normal_dev && !normals_dev))) return RGBID_E_INVALID;
   for (int v = 0; v < V; ++v) {
@@ -448,7 +424,7 @@ int rgbid_raster_views(rgbid_raster* r, const float* vertices_dev, unsigned long
   const unsigned n_v = (unsigned)n_vertices, n_t = (unsigned)n_triangles;
   RGBID_HIP(hipMemsetAsync(w.slots, 0, sizeof(unsigned) * SLOTS, st));
   if (n_t) {
-    hipLaunchKernelGGL(k_rast_check, dim3(grid_of(((unsigned long long)n_t + VT - 1) / VT)), dim3(VT), 0, st, triangles_dev, n_t, n_v, w.slots);
+    check_triangles(st, triangles_dev, n_t, n_v, w.slots + SLOT_BAD);
     RGBID_HIP(hipGetLastError());
     if (int e = w.read_slots(st)) return e;
     if (w.slots_host[SLOT_BAD]) return RGBID_E_INVALID;    // a triangle names a vertex that does not exist

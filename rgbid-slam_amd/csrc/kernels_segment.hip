@@ -122,8 +122,7 @@ __global__ __launch_bounds__(VT) void k_seg_edges(const char* const* __restrict_
       idx[e0 + nb] = (unsigned)(e0 + nb);
     }
   }
-  cnt = wave_sum(cnt);
-  if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(&ecount[k], cnt);   // integer count: exact in any order
+  wave_add_to(&ecount[k], cnt);   // integer count: exact in any order
 }
 
 __device__ __forceinline__ int find_root(int* par, int x) {

@@ -3,19 +3,19 @@
 // section 23).
 //
 // The judge is tests/simplify_mirror.py; grid, counts and every emitted buffer are byte-identical to it.
-//   plan  k_simp_check       counts the triangles with an index >= n_v into a slot
-//         k_simp_box         per-axis min / max and the count of the finite vertices (k_vox_box over 12-byte vertices), copied to the host
-//                            with that slot: a bad index ends the call here
+//   plan  k_mesh_check       mesh_device.h: counts the triangles with an index >= n_v into a slot
+//         k_vox_box          per-axis min / max and the count of the finite vertices (voxel_device.h, over VertexPoints), copied to the
+//                            host with that slot: a bad index ends the call here
 //         (host)             form_grid, the key width
-//         k_simp_keys        one (key, vertex) pair per vertex; a vertex that does not take part gets the sentinel (largest key + 1)
+//         k_vox_keys         one (key, vertex) pair per vertex; a vertex that does not take part gets the sentinel (largest key + 1)
 //         LSD radix sort     voxel_device.h, stable: the members of a cluster in ascending vertex order
 //         k_simp_runs        the flag compaction's write pass over the heads key[i] != key[i - 1] with one more store per item: a head
 //                            writes its position as the start of cluster `rank`, EVERY item writes cluster_of[vertex] = the heads up to
 //                            and including it - 1.  A scatter to distinct addresses
 //         k_simp_classes     one thread per triangle: lost / collapsed / candidate; the first two counted (one atomic per wave and
 //                            class), the third flagged as kept
-//         duplicate search   three stable sorts of (key, triangle) by s2, s1, s0, the sorted cluster numbers of a candidate (k_simp_tri_keys
-//                            recomputes the key of the next round from cluster_of and the triangle in the order the last round left;
+//         duplicate search   sort_rounds: three stable sorts of (key, triangle) by s2, s1, s0, the sorted cluster numbers of a candidate
+//                            (k_vox_round_keys over TriKey recomputes the key of the next round in the order the last round left;
 //                            lost and collapsed triangles carry the sentinel C and sort behind the candidates); k_simp_heads clears the
 //                            flag of a candidate whose predecessor has the same triple: equal triples are adjacent and in input order
 //         kept               flag count + scan over the flags
@@ -26,11 +26,11 @@
 #include "../../include/rgbid_simplify.h"
 #include "common.h"
 #include "hip_host.h"
-#include "voxel_device.h"   // grid, cell keys, radix sort, flag compaction; the sort workspace
+#include "mesh_device.h"    // the index check, the argument test, the create; voxel_device.h's box, grid, cell keys, radix sort, flag
+                            // compaction and unit vector; the sort workspace
 
 #include <cmath>
 #include <cstring>
-#include <new>
 
 using namespace rgbid;
 
@@ -41,54 +41,6 @@ enum { SLOT_BAD = 9, SLOT_LOST = 10, SLOT_COLLAPSED = 11, SLOT_DUPLICATE = 12, S
 static_assert(SLOT_VOXELS < SLOT_BAD && SLOT_KEPT < SLOTS, "the slots of this file lie behind the workspace's");
 
 // ---- vertices ---------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(VT) void k_simp_check(const unsigned* __restrict__ tri, unsigned n_t, unsigned n_v, unsigned* __restrict__ bad) {
-  unsigned c = 0;
-  for (size_t t = (size_t)blockIdx.x * VT + threadIdx.x; t < n_t; t += (size_t)gridDim.x * VT)
-    if (!(tri[3 * t] < n_v && tri[3 * t + 1] < n_v && tri[3 * t + 2] < n_v)) ++c;
-  c = wave_sum(c);
-  if ((threadIdx.x & 63) == 0 && c) atomicAdd(bad, c);
-}
-
-// k_vox_box over 12-byte vertices: min, max and count are exact in any order
-__global__ __launch_bounds__(VT) void k_simp_box(const float* __restrict__ in, unsigned n, float* __restrict__ part, unsigned* __restrict__ part_cnt) {
-  __shared__ float lds[VT / 64][6];
-  __shared__ unsigned ldc[VT / 64];
-  float v[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
-  unsigned cnt = 0;
-  for (size_t i = (size_t)blockIdx.x * VT + threadIdx.x; i < n; i += (size_t)gridDim.x * VT) {
-    const float x = in[3 * i], y = in[3 * i + 1], z = in[3 * i + 2];
-    if (finite3(x, y, z)) {
-      ++cnt;
-      v[0] = fminf(v[0], x); v[1] = fminf(v[1], y); v[2] = fminf(v[2], z);
-      v[3] = fmaxf(v[3], x); v[4] = fmaxf(v[4], y); v[5] = fmaxf(v[5], z);
-    }
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    for (int k = 0; k < 3; ++k) v[k] = fminf(v[k], __shfl_xor(v[k], o, 64));
-    for (int k = 3; k < 6; ++k) v[k] = fmaxf(v[k], __shfl_xor(v[k], o, 64));
-    cnt += __shfl_xor(cnt, o, 64);
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) { for (int k = 0; k < 6; ++k) lds[wave][k] = v[k]; ldc[wave] = cnt; }
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    const int k = threadIdx.x;
-    float r = lds[0][k];
-    for (int w = 1; w < VT / 64; ++w) r = k < 3 ? fminf(r, lds[w][k]) : fmaxf(r, lds[w][k]);
-    part[6 * blockIdx.x + k] = r;
-  }
-  if (threadIdx.x == 6) part_cnt[blockIdx.x] = ldc[0] + ldc[1] + ldc[2] + ldc[3];
-}
-
-template <typename K>
-__global__ __launch_bounds__(VT) void k_simp_keys(const float* __restrict__ in, unsigned n, VoxGrid g, K* __restrict__ keys, unsigned* __restrict__ idx) {
-  for (size_t i = (size_t)blockIdx.x * VT + threadIdx.x; i < n; i += (size_t)gridDim.x * VT) {
-    const float x = in[3 * i], y = in[3 * i + 1], z = in[3 * i + 2];
-    keys[i] = (K)(finite3(x, y, z) ? cell_key(x, y, z, g) : g.sentinel);
-    idx[i] = (unsigned)i;
-  }
-}
-
 // k_vox_flag_write over HeadSrc's flags, and the cluster number of every item: items of a tile in (round, wave, lane) order, the heads
 // before an item = tile offset + earlier rounds + lower waves + mbcnt
 template <typename K>
@@ -158,7 +110,7 @@ __global__ __launch_bounds__(VT) void k_simp_emit(const float* __restrict__ vert
   const unsigned b = starts[c], e = starts[c + 1];
   ClusterSum s;
   unsigned m = b;
-  for (; e - m >= 4; m += 4) {                   // the gathers of 4 members are issued before their adds
+  for (; e - m >= 4; m += 4) {                   // gather_in_order's loop, kept here: through it this kernel measured 1 % slower at 192 members
     unsigned id[4];
     Member mem[4];
 #pragma unroll
@@ -177,13 +129,7 @@ __global__ __launch_bounds__(VT) void k_simp_emit(const float* __restrict__ vert
     for (int a = 0; a < 3; ++a) cols_out[o + a] = (unsigned char)((2 * s.c[a] + cnt) / (2 * (unsigned long long)cnt));   // the rounded mean
   if (nrm_out) {
     float n[3] = {0.f, 0.f, 0.f};
-    if (s.normal) {
-      const double q = (s.n[0] * s.n[0] + s.n[1] * s.n[1]) + s.n[2] * s.n[2];
-      if (q != 0.0 && isfinite(q)) {
-        const double l = sqrt(q);
-        for (int a = 0; a < 3; ++a) n[a] = (float)(s.n[a] / l);
-      }
-    }
+    if (s.normal) unit_of(s.n, n);
     for (int a = 0; a < 3; ++a) nrm_out[o + a] = n[a];
   }
   if (members_out) members_out[c] = cnt;
@@ -229,29 +175,24 @@ __global__ __launch_bounds__(VT) void k_simp_classes(TriView view, unsigned n_t,
     collapsed += k == TRI_COLLAPSED;
     kept[t] = k == TRI_CANDIDATE;
   }
-  lost = wave_sum(lost);
-  collapsed = wave_sum(collapsed);
-  if ((threadIdx.x & 63) == 0) {
-    if (lost) atomicAdd(slots + SLOT_LOST, lost);
-    if (collapsed) atomicAdd(slots + SLOT_COLLAPSED, collapsed);
-  }
+  wave_add_to(slots + SLOT_LOST, lost);
+  wave_add_to(slots + SLOT_COLLAPSED, collapsed);
 }
 
-// the key of sort round r (2, 1, 0) for the triangle at position m of the order the last round left (order == null: the input order,
-// and the indices are written too): s_r of a candidate, the sentinel n_c of every other triangle
-__global__ __launch_bounds__(VT) void k_simp_tri_keys(TriView view, unsigned n_t, int r, unsigned n_c, const unsigned* __restrict__ order,
-                                                      unsigned* __restrict__ keys, unsigned* __restrict__ idx) {
-  for (size_t m = (size_t)blockIdx.x * VT + threadIdx.x; m < n_t; m += (size_t)gridDim.x * VT) {
-    const unsigned t = order ? order[m] : (unsigned)m;
+// sort_rounds' key of round r (2, 1, 0) for triangle t: s_r of a candidate, the sentinel n_c of every other triangle
+struct TriKey {
+  TriView view;
+  unsigned n_t, n_c;
+  __device__ __forceinline__ unsigned size() const { return n_t; }
+  __device__ __forceinline__ unsigned operator()(unsigned t, int r) const {
     unsigned c[3], key = n_c;
     if (t < n_t) {
       view.clusters(t, c);
       if (tri_class(c) == TRI_CANDIDATE) { sort3(c); key = c[r]; }
     }
-    keys[m] = key;
-    if (!order) idx[m] = (unsigned)m;
+    return key;
   }
-}
+};
 
 // after the three rounds the candidates come first, equal triples are adjacent and in input order: a candidate whose predecessor has
 // its triple is a duplicate and loses its flag (a store to its own input index)
@@ -270,8 +211,7 @@ __global__ __launch_bounds__(VT) void k_simp_heads(TriView view, unsigned n_t, c
     sort3(d);
     if (c[0] == d[0] && c[1] == d[1] && c[2] == d[2]) { kept[t] = 0; ++dup; }
   }
-  dup = wave_sum(dup);
-  if ((threadIdx.x & 63) == 0 && dup) atomicAdd(slots + SLOT_DUPLICATE, dup);
+  wave_add_to(slots + SLOT_DUPLICATE, dup);
 }
 
 // stable compaction of the kept triangles: t' at the rank; out == null only counts
@@ -289,8 +229,6 @@ struct KeptTriSrc {
     o[0] = c[0]; o[1] = c[1]; o[2] = c[2];
   }
 };
-
-bool aligned4(const void* p) { return !(((uintptr_t)p) & 3); }
 
 }  // namespace
 
@@ -323,8 +261,7 @@ int vertex_stage(rgbid_simplify* h, unsigned finite, const VoxGrid& g) {
   hipStream_t s = h->ctx->stream;
   SortWorkspace& w = h->wv;
   const unsigned n_v = h->n_v;
-  hipLaunchKernelGGL(k_simp_keys<K>, dim3(grid_of(((unsigned long long)n_v + VT - 1) / VT)), dim3(VT), 0, s, h->verts, n_v, g,
-                     reinterpret_cast<K*>(w.keys[0]), w.idx[0]);
+  w.make_keys<K>(s, VertexPoints{h->verts}, n_v, g);
   const SortedPairs<K> sp = w.sort<K>(s, n_v, g);
   w.count_scan(s, HeadSrc<K>{sp.keys, finite, sp.starts}, finite, SLOT_RUNS, sp.starts, finite);
   hipLaunchKernelGGL(k_simp_runs<K>, dim3((finite + RUN_TILE - 1) / RUN_TILE), dim3(VT), 0, s, sp.keys, sp.idx, finite, n_v, w.bc, sp.starts,
@@ -342,13 +279,7 @@ int triangle_stage(rgbid_simplify* h, bool keep_duplicates) {
   const TriView view{h->tri, h->cluster_of, h->n_v};
   hipLaunchKernelGGL(k_simp_classes, dim3(gt), dim3(VT), 0, s, view, n_t, h->kept, w.slots);
   if (!keep_duplicates) {
-    const int bits = bitlen(h->n_c);             // the sentinel n_c is the largest key
-    int p = 0;
-    for (int r = 2; r >= 0; --r) {
-      unsigned* keys = reinterpret_cast<unsigned*>(w.keys[p]);
-      hipLaunchKernelGGL(k_simp_tri_keys, dim3(gt), dim3(VT), 0, s, view, n_t, r, h->n_c, r == 2 ? nullptr : w.idx[p], keys, w.idx[p]);
-      p = w.sort_bits<unsigned>(s, n_t, bits, p);
-    }
+    const int p = w.sort_rounds(s, TriKey{view, n_t, h->n_c}, h->n_c, n_t, {2, 1, 0});
     hipLaunchKernelGGL(k_simp_heads, dim3(gt), dim3(VT), 0, s, view, n_t, w.idx[p], h->kept, w.slots);
   }
   w.count_scan(s, KeptTriSrc{n_t, view, h->kept, nullptr}, n_t, SLOT_KEPT);
@@ -361,25 +292,15 @@ int triangle_stage(rgbid_simplify* h, bool keep_duplicates) {
 extern "C" {
 
 int rgbid_simplify_create(rgbid_simplify** out, rgbid_ctx* ctx, unsigned long long max_vertices, unsigned long long max_triangles) {
-  if (!out) return RGBID_E_INVALID;
-  *out = nullptr;
-  if (!ctx || max_vertices < 1 || max_vertices > RGBID_SIMPLIFY_MAX_VERTICES) return RGBID_E_INVALID;
-  if (max_triangles < 1 || max_triangles > RGBID_SIMPLIFY_MAX_TRIANGLES) return RGBID_E_INVALID;
-  (void)hipSetDevice(ctx->device);
-  rgbid_simplify* h = new (std::nothrow) rgbid_simplify;
-  if (!h) return RGBID_E_NOMEM;
-  h->ctx = ctx;
-  h->cap_v = max_vertices;
-  h->cap_t = max_triangles;
-  int r = h->wv.alloc(h->buf, max_vertices);
-  if (!r) r = h->wt.alloc(h->buf, max_triangles);
-  if (!r) r = h->buf.alloc(&h->cluster_of, sizeof(unsigned) * (size_t)max_vertices);
-  if (!r) r = h->buf.alloc(&h->kept, (size_t)max_triangles);
-  if (r) { rgbid_simplify_destroy(h); return r; }
-  h->wt.slots = h->wv.slots;           // one slot area, one read-back
-  h->wt.slots_host = h->wv.slots_host;
-  *out = h;
-  return RGBID_OK;
+  return mesh_create(out, ctx, max_vertices, max_triangles, RGBID_SIMPLIFY_MAX_VERTICES, RGBID_SIMPLIFY_MAX_TRIANGLES, [&](rgbid_simplify* h) {
+    int r = h->wv.alloc(h->buf, max_vertices);
+    if (!r) r = h->wt.alloc(h->buf, max_triangles);
+    if (!r) r = h->buf.alloc(&h->cluster_of, sizeof(unsigned) * (size_t)max_vertices);
+    if (!r) r = h->buf.alloc(&h->kept, (size_t)max_triangles);
+    h->wt.slots = h->wv.slots;         // one slot area, one read-back
+    h->wt.slots_host = h->wv.slots_host;
+    return r;
+  });
 }
 
 int rgbid_simplify_destroy(rgbid_simplify* h) { return destroy_handle(h); }   // an emit may still read the tables
@@ -387,9 +308,8 @@ int rgbid_simplify_destroy(rgbid_simplify* h) { return destroy_handle(h); }   //
 int rgbid_simplify_plan(rgbid_simplify* h, unsigned long long n_vertices, const float* vertices_dev, unsigned long long n_triangles,
                         const uint32_t* triangles_dev, const float cell[3], uint32_t flags, long long grid[6], unsigned long long counts[6]) {
   if (!h || !cell || (flags & ~RGBID_SIMPLIFY_KEEP_DUPLICATES)) return RGBID_E_INVALID;
-  if (n_vertices > h->cap_v || n_triangles > h->cap_t) return RGBID_E_INVALID;
+  if (!mesh_in_ok(n_vertices, n_triangles, triangles_dev, h->cap_v, h->cap_t)) return RGBID_E_INVALID;
   if (n_vertices && (!vertices_dev || !aligned4(vertices_dev))) return RGBID_E_INVALID;
-  if (n_triangles && (!triangles_dev || !aligned4(triangles_dev) || n_vertices == 0)) return RGBID_E_INVALID;
   for (int a = 0; a < 3; ++a) if (!(std::isfinite(cell[a]) && cell[a] > 0.f)) return RGBID_E_INVALID;
   if (grid) for (int i = 0; i < 6; ++i) grid[i] = 0;
   if (counts) for (int i = 0; i < 6; ++i) counts[i] = 0;
@@ -404,12 +324,8 @@ int rgbid_simplify_plan(rgbid_simplify* h, unsigned long long n_vertices, const 
   SortWorkspace& w = h->wv;
   h->mark(0);
   RGBID_HIP(hipMemsetAsync(w.slots, 0, sizeof(unsigned) * SLOTS, s));
-  if (n_t) hipLaunchKernelGGL(k_simp_check, dim3(grid_of(((unsigned long long)n_t + VT - 1) / VT)), dim3(VT), 0, s, triangles_dev, n_t, n_v, w.slots + SLOT_BAD);
-  {
-    const unsigned nb = grid_of(((unsigned long long)n_v + VT - 1) / VT);
-    hipLaunchKernelGGL(k_simp_box, dim3(nb), dim3(VT), 0, s, vertices_dev, n_v, w.box_part, w.box_cnt);
-    hipLaunchKernelGGL(k_vox_box_final, dim3(1), dim3(64), 0, s, w.box_part, w.box_cnt, (int)nb, w.slots);
-  }
+  if (n_t) check_triangles(s, triangles_dev, n_t, n_v, w.slots + SLOT_BAD);
+  w.box(s, VertexPoints{vertices_dev}, n_v);
   h->mark(1);
   unsigned finite;
   float lo[3], hi[3];
@@ -477,17 +393,9 @@ int rgbid_simplify_emit(rgbid_simplify* h, const uint8_t* colours_dev, const flo
 int rgbid_simplify_timing(rgbid_simplify* h, int enable, float ms[3]) {
   if (!h) return RGBID_E_INVALID;
   (void)hipSetDevice(h->ctx->device);
-  if (ms) {
-    ms[0] = ms[1] = ms[2] = 0.f;
-    if (h->timed[0]) {
-      float box = 0.f;
-      RGBID_HIP(h->timer.elapsed(0, 1, &box));
-      RGBID_HIP(h->timer.elapsed(2, 3, &ms[0]));
-      ms[0] += box;
-    }
-    if (h->timed[1]) RGBID_HIP(h->timer.elapsed(4, 5, &ms[1]));
-    if (h->timed[2]) RGBID_HIP(h->timer.elapsed(6, 7, &ms[2]));
-  }
+  static const int pairs[3][4] = {{0, 1, 2, 3}, {4, 5}, {6, 7}};   // the vertex stage: the box and the rest
+  if (ms)
+    if (int r = stage_times(h->timer, h->timed, pairs, ms)) return r;
   return h->timer.enable(enable != 0);
 }
 

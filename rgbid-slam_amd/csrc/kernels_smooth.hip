@@ -2,11 +2,11 @@
 // of its vertices, and area-weighted vertex normals from its triangles (include/rgbid_smooth.h).
 //
 // The judge is tests/smooth_mirror.py; counts, CSR, boundary bytes, positions and normals are byte-identical to it.
-//   plan  k_smooth_check     counts the triangles with an index >= n_v and the corner pairs with equal ends into two slots, copied to the
-//                            host: a bad index ends the call here, the other count gives the number M of pairs that stay
-//         k_smooth_pair_keys one (key, item) pair per ordered corner pair 6 t + c; a pair with equal ends gets the sentinel n_v
-//         LSD radix sort     voxel_device.h, stable, two rounds: by u, then by v with the keys recomputed in the order the first round
-//                            left.  Equal (v, u) are adjacent, the dropped pairs last
+//   plan  k_mesh_check<true> mesh_device.h: counts the triangles with an index >= n_v and the corner pairs with equal ends into two slots,
+//                            copied to the host: a bad index ends the call here, the other count gives the number M of pairs that stay
+//         sort_rounds        voxel_device.h: k_vox_round_keys over PairKey, one (key, item) pair per ordered corner pair 6 t + c (a pair
+//                            with equal ends gets the sentinel n_v), and the stable LSD radix sort, two rounds: by u, then by v with the
+//                            keys recomputed in the order the first round left.  Equal (v, u) are adjacent, the dropped pairs last
 //         k_smooth_ends      the u of the sorted items beside their v
 //         flag compaction    over the heads (v, u)[m] != (v, u)[m - 1]: heads[rank] = m, heads[P] = M
 //         k_smooth_rows      neighbours[r] = u, incidences[r] = heads[r + 1] - heads[r]
@@ -19,11 +19,11 @@
 #include "../../include/rgbid_smooth.h"
 #include "common.h"
 #include "hip_host.h"
-#include "voxel_device.h"   // radix sort, flag compaction; the sort workspace
+#include "mesh_device.h"    // the index check, the argument test, the create; voxel_device.h's sort_rounds, flag compaction and ordered
+                            // gather; the sort workspace
 
 #include <cmath>
 #include <cstring>
-#include <new>
 
 using namespace rgbid;
 
@@ -34,21 +34,6 @@ enum { SLOT_BAD = 9, SLOT_DROPPED = 10, SLOT_BPAIRS = 11, SLOT_BVERTS = 12, SLOT
 static_assert(SLOT_VOXELS < SLOT_BAD && SLOT_NONMANIFOLD < SLOTS, "the slots of this file lie behind the workspace's");
 
 // ---- adjacency --------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(VT) void k_smooth_check(const unsigned* __restrict__ tri, unsigned n_t, unsigned n_v, unsigned* __restrict__ slots) {
-  unsigned bad = 0, dropped = 0;
-  for (size_t t = (size_t)blockIdx.x * VT + threadIdx.x; t < n_t; t += (size_t)gridDim.x * VT) {
-    const unsigned a = tri[3 * t], b = tri[3 * t + 1], c = tri[3 * t + 2];
-    if (!(a < n_v && b < n_v && c < n_v)) ++bad;
-    dropped += 2u * ((a == b) + (b == c) + (c == a));
-  }
-  bad = wave_sum(bad);
-  dropped = wave_sum(dropped);
-  if ((threadIdx.x & 63) == 0) {
-    if (bad) atomicAdd(slots + SLOT_BAD, bad);
-    if (dropped) atomicAdd(slots + SLOT_DROPPED, dropped);
-  }
-}
-
 // the mesh as the pair kernels see it: item 6 t + c is the c-th of (i0,i1) (i1,i0) (i1,i2) (i2,i1) (i2,i0) (i0,i2)
 struct PairView {
   const unsigned* tri;
@@ -65,18 +50,16 @@ struct PairView {
   }
 };
 
-// the key of sort round r (0: u, 1: v) for the item at position m of the order the last round left (order == null: the input order, and
-// the items are written too); the sentinel n_v for a pair that is dropped
-__global__ __launch_bounds__(VT) void k_smooth_pair_keys(PairView view, int r, const unsigned* __restrict__ order, unsigned* __restrict__ keys,
-                                                         unsigned* __restrict__ idx) {
-  for (size_t m = (size_t)blockIdx.x * VT + threadIdx.x; m < view.items; m += (size_t)gridDim.x * VT) {
-    const unsigned item = order ? order[m] : (unsigned)m;
+// sort_rounds' key of round r (0: u, 1: v) for an item; the sentinel n_v for a pair that is dropped
+struct PairKey {
+  PairView view;
+  __device__ __forceinline__ unsigned long long size() const { return view.items; }
+  __device__ __forceinline__ unsigned operator()(unsigned item, int r) const {
     unsigned v, u;
     const bool ok = view.ends(item, v, u);
-    keys[m] = ok ? (r ? v : u) : view.n_v;
-    if (!order) idx[m] = (unsigned)m;
+    return ok ? (r ? v : u) : view.n_v;
   }
-}
+};
 
 // after the two rounds: the u of the first n_pairs sorted items
 __global__ __launch_bounds__(VT) void k_smooth_ends(PairView view, const unsigned* __restrict__ order, unsigned n_pairs, unsigned* __restrict__ us) {
@@ -147,7 +130,7 @@ __global__ __launch_bounds__(VT) void k_smooth_rowstats(const unsigned* __restri
   deg0 = wave_sum(deg0);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) deg = max(deg, (unsigned)__shfl_xor(deg, o, 64));
-  if ((threadIdx.x & 63) == 0) {
+  if ((threadIdx.x & 63) == 0) {     // five counts behind one branch: four wave_add_to would make four
     if (bpairs) atomicAdd(slots + SLOT_BPAIRS, bpairs);
     if (bverts) atomicAdd(slots + SLOT_BVERTS, bverts);
     if (nonmanifold) atomicAdd(slots + SLOT_NONMANIFOLD, nonmanifold);
@@ -157,6 +140,7 @@ __global__ __launch_bounds__(VT) void k_smooth_rowstats(const unsigned* __restri
 }
 
 // ---- corner table -----------------------------------------------------------------------------------------------------------------
+// one round, so not sort_rounds': k_vox_round_keys' test of the order and its round argument would make this stream half as long again
 __global__ __launch_bounds__(VT) void k_smooth_corner_keys(const unsigned* __restrict__ tri, unsigned long long corners, unsigned n_v,
                                                            unsigned* __restrict__ keys, unsigned* __restrict__ idx) {
   for (size_t i = (size_t)blockIdx.x * VT + threadIdx.x; i < corners; i += (size_t)gridDim.x * VT) {
@@ -181,12 +165,17 @@ __device__ __forceinline__ Pos pos_load(const float* __restrict__ in, unsigned i
   return q;
 }
 
+struct PosSum {
+  double s[3] = {0, 0, 0};
+  unsigned k = 0;                    // the finite neighbours
+};
+
 // one neighbour, in order; the pragma keeps every add a separate rounding
-__device__ __forceinline__ void pos_add(double s[3], unsigned& k, const Pos& q) {
+__device__ __forceinline__ void pos_add(PosSum& sum, const Pos& q) {
   RGBID_FP_STRICT
   if (finite3(q.p[0], q.p[1], q.p[2])) {
-    for (int a = 0; a < 3; ++a) s[a] += (double)q.p[a];
-    ++k;
+    for (int a = 0; a < 3; ++a) sum.s[a] += (double)q.p[a];
+    ++sum.k;
   }
 }
 
@@ -199,29 +188,15 @@ __global__ __launch_bounds__(VT) void k_smooth_pass(const float* __restrict__ in
   const unsigned* words = reinterpret_cast<const unsigned*>(in);
   const unsigned w[3] = {words[o], words[o + 1], words[o + 2]};
   const float x[3] = {__uint_as_float(w[0]), __uint_as_float(w[1]), __uint_as_float(w[2])};
-  double s[3] = {0, 0, 0};
-  unsigned k = 0;
-  if (finite3(x[0], x[1], x[2]) && !(pinned && pinned[v])) {
-    const unsigned b = offsets[v], e = offsets[v + 1];
-    unsigned m = b;
-    for (; e - m >= 4; m += 4) {                   // the gathers of 4 neighbours are issued before their adds
-      unsigned id[4];
-      Pos q[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) id[u] = nbr[m + u];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) q[u] = pos_load(in, id[u], n_v);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) pos_add(s, k, q[u]);
-    }
-    for (; m < e; ++m) pos_add(s, k, pos_load(in, nbr[m], n_v));
-  }
+  PosSum sum;
+  if (finite3(x[0], x[1], x[2]) && !(pinned && pinned[v]))
+    gather_in_order(nbr, offsets[v], offsets[v + 1], sum, [&](unsigned id) { return pos_load(in, id, n_v); }, pos_add);
   unsigned* wout = reinterpret_cast<unsigned*>(out);
-  if (k) {
-    const double dk = (double)k;
+  if (sum.k) {
+    const double dk = (double)sum.k;
     for (int a = 0; a < 3; ++a) {
       const double xa = (double)x[a];
-      const double mean = s[a] / dk;
+      const double mean = sum.s[a] / dk;
       const double d = mean - xa;
       const double step = f * d;
       out[o + a] = (float)(xa + step);
@@ -273,30 +248,12 @@ __global__ __launch_bounds__(VT) void k_smooth_normals(const float* __restrict__
   RGBID_FP_STRICT
   const size_t v = (size_t)blockIdx.x * VT + threadIdx.x;
   if (v >= n_v) return;
-  const unsigned b = corner_offsets[v], e = corner_offsets[v + 1];
   double s[3] = {0, 0, 0};
-  unsigned m = b;
-  for (; e - m >= 4; m += 4) {                     // the gathers of 4 triangles are issued before their adds
-    unsigned c[4];
-    TriPos q[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) c[u] = corners[m + u];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) q[u] = tri_load(pos, tri, c[u], n_t, n_v);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) tri_add(s, q[u]);
-  }
-  for (; m < e; ++m) tri_add(s, tri_load(pos, tri, corners[m], n_t, n_v));
-  float n[3] = {0.f, 0.f, 0.f};
-  const double q = (s[0] * s[0] + s[1] * s[1]) + s[2] * s[2];
-  if (q != 0.0 && isfinite(q)) {
-    const double l = sqrt(q);
-    for (int a = 0; a < 3; ++a) n[a] = (float)(s[a] / l);
-  }
+  gather_in_order(corners, corner_offsets[v], corner_offsets[v + 1], s, [&](unsigned c) { return tri_load(pos, tri, c, n_t, n_v); }, tri_add);
+  float n[3];
+  unit_of(s, n);
   for (int a = 0; a < 3; ++a) out[3 * v + a] = n[a];
 }
-
-bool aligned4(const void* p) { return !(((uintptr_t)p) & 3); }
 
 }  // namespace
 
@@ -334,17 +291,10 @@ int adjacency_stage(rgbid_smooth* h, unsigned n_pairs) {
   const unsigned* heads = nullptr;
   if (n_pairs) {
     const PairView view{h->tri, h->n_t, n_v, 6ull * h->n_t};
-    const unsigned items = (unsigned)view.items, gi = grid_of((view.items + VT - 1) / VT);
-    const int bits = bitlen(n_v);                  // the sentinel n_v is the largest key
-    int p = 0;
-    for (int r = 0; r < 2; ++r) {
-      unsigned* keys = reinterpret_cast<unsigned*>(w.keys[p]);
-      hipLaunchKernelGGL(k_smooth_pair_keys, dim3(gi), dim3(VT), 0, s, view, r, r ? w.idx[p] : nullptr, keys, w.idx[p]);
-      p = w.sort_bits<unsigned>(s, items, bits, p);
-    }
-    unsigned* u_out = reinterpret_cast<unsigned*>(w.keys[p ^ 1]);
+    const int p = w.sort_rounds(s, PairKey{view}, n_v, (unsigned)view.items, {0, 1});   // by u, then by v
+    unsigned* u_out = w.keys_as<unsigned>(p ^ 1);
     hipLaunchKernelGGL(k_smooth_ends, dim3(grid_of(((unsigned long long)n_pairs + VT - 1) / VT)), dim3(VT), 0, s, view, w.idx[p], n_pairs, u_out);
-    vs = reinterpret_cast<const unsigned*>(w.keys[p]);
+    vs = w.keys_as<unsigned>(p);
     us = u_out;
     const PairHeadSrc src{vs, us, n_pairs, w.idx[p ^ 1]};
     w.count_scan(s, src, n_pairs, SLOT_RUNS, w.idx[p ^ 1], n_pairs);
@@ -369,10 +319,9 @@ int corner_stage(rgbid_smooth* h) {
   const unsigned long long corners = 3ull * h->n_t;
   const unsigned* keys = nullptr;
   if (corners) {
-    hipLaunchKernelGGL(k_smooth_corner_keys, dim3(grid_of((corners + VT - 1) / VT)), dim3(VT), 0, s, h->tri, corners, n_v,
-                       reinterpret_cast<unsigned*>(w.keys[0]), w.idx[0]);
+    hipLaunchKernelGGL(k_smooth_corner_keys, dim3(grid_of((corners + VT - 1) / VT)), dim3(VT), 0, s, h->tri, corners, n_v, w.keys_as<unsigned>(0), w.idx[0]);
     const int p = w.sort_bits<unsigned>(s, (unsigned)corners, bitlen(n_v), 0);
-    keys = reinterpret_cast<const unsigned*>(w.keys[p]);
+    keys = w.keys_as<unsigned>(p);
     RGBID_HIP(hipMemcpyAsync(h->corners, w.idx[p], sizeof(unsigned) * (size_t)corners, hipMemcpyDeviceToDevice, s));
   }
   hipLaunchKernelGGL(k_smooth_offsets, dim3(grid_of(((unsigned long long)n_v + 1 + VT - 1) / VT)), dim3(VT), 0, s, keys, (const unsigned*)nullptr,
@@ -386,28 +335,18 @@ int corner_stage(rgbid_smooth* h) {
 extern "C" {
 
 int rgbid_smooth_create(rgbid_smooth** out, rgbid_ctx* ctx, unsigned long long max_vertices, unsigned long long max_triangles) {
-  if (!out) return RGBID_E_INVALID;
-  *out = nullptr;
-  if (!ctx || max_vertices < 1 || max_vertices > RGBID_SMOOTH_MAX_VERTICES) return RGBID_E_INVALID;
-  if (max_triangles < 1 || max_triangles > RGBID_SMOOTH_MAX_TRIANGLES) return RGBID_E_INVALID;
-  (void)hipSetDevice(ctx->device);
-  rgbid_smooth* h = new (std::nothrow) rgbid_smooth;
-  if (!h) return RGBID_E_NOMEM;
-  h->ctx = ctx;
-  h->cap_v = max_vertices;
-  h->cap_t = max_triangles;
-  const size_t cv = (size_t)max_vertices, ct = (size_t)max_triangles;
-  int r = h->w.alloc(h->buf, 6ull * max_triangles);
-  if (!r) r = h->buf.alloc(&h->offsets, sizeof(unsigned) * (cv + 1));
-  if (!r) r = h->buf.alloc(&h->nbr, sizeof(unsigned) * 6 * ct);
-  if (!r) r = h->buf.alloc(&h->inc, sizeof(unsigned) * 6 * ct);
-  if (!r) r = h->buf.alloc(&h->boundary, cv);
-  if (!r) r = h->buf.alloc(&h->corner_offsets, sizeof(unsigned) * (cv + 1));
-  if (!r) r = h->buf.alloc(&h->corners, sizeof(unsigned) * 3 * ct);
-  if (!r) r = h->buf.alloc(&h->spare, sizeof(float) * 3 * cv);
-  if (r) { rgbid_smooth_destroy(h); return r; }
-  *out = h;
-  return RGBID_OK;
+  return mesh_create(out, ctx, max_vertices, max_triangles, RGBID_SMOOTH_MAX_VERTICES, RGBID_SMOOTH_MAX_TRIANGLES, [&](rgbid_smooth* h) {
+    const size_t cv = (size_t)max_vertices, ct = (size_t)max_triangles;
+    int r = h->w.alloc(h->buf, 6ull * max_triangles);
+    if (!r) r = h->buf.alloc(&h->offsets, sizeof(unsigned) * (cv + 1));
+    if (!r) r = h->buf.alloc(&h->nbr, sizeof(unsigned) * 6 * ct);
+    if (!r) r = h->buf.alloc(&h->inc, sizeof(unsigned) * 6 * ct);
+    if (!r) r = h->buf.alloc(&h->boundary, cv);
+    if (!r) r = h->buf.alloc(&h->corner_offsets, sizeof(unsigned) * (cv + 1));
+    if (!r) r = h->buf.alloc(&h->corners, sizeof(unsigned) * 3 * ct);
+    if (!r) r = h->buf.alloc(&h->spare, sizeof(float) * 3 * cv);
+    return r;
+  });
 }
 
 int rgbid_smooth_destroy(rgbid_smooth* h) { return destroy_handle(h); }   // a pass may still read the tables
@@ -415,8 +354,7 @@ int rgbid_smooth_destroy(rgbid_smooth* h) { return destroy_handle(h); }   // a p
 int rgbid_smooth_plan(rgbid_smooth* h, unsigned long long n_vertices, unsigned long long n_triangles, const uint32_t* triangles_dev, uint32_t flags,
                       unsigned long long counts[8]) {
   if (!h || (flags & ~RGBID_SMOOTH_PLAN_NORMALS)) return RGBID_E_INVALID;
-  if (n_vertices > h->cap_v || n_triangles > h->cap_t) return RGBID_E_INVALID;
-  if (n_triangles && (!triangles_dev || !aligned4(triangles_dev) || n_vertices == 0)) return RGBID_E_INVALID;
+  if (!mesh_in_ok(n_vertices, n_triangles, triangles_dev, h->cap_v, h->cap_t)) return RGBID_E_INVALID;
   if (counts) for (int i = 0; i < 8; ++i) counts[i] = 0;
   h->planned = h->has_corners = false;
   h->timed[0] = false;
@@ -435,7 +373,7 @@ int rgbid_smooth_plan(rgbid_smooth* h, unsigned long long n_vertices, unsigned l
   }
   h->mark(0);
   RGBID_HIP(hipMemsetAsync(w.slots, 0, sizeof(unsigned) * SLOTS, s));
-  if (n_t) hipLaunchKernelGGL(k_smooth_check, dim3(grid_of(((unsigned long long)n_t + VT - 1) / VT)), dim3(VT), 0, s, triangles_dev, n_t, n_v, w.slots);
+  if (n_t) check_triangles<true>(s, triangles_dev, n_t, n_v, w.slots + SLOT_BAD, w.slots + SLOT_DROPPED);
   h->mark(1);
   RGBID_HIP(hipGetLastError());
   if (int r = w.read_slots(s)) return r;
@@ -529,17 +467,9 @@ int rgbid_smooth_normals(rgbid_smooth* h, const float* vertices_dev, float* norm
 int rgbid_smooth_timing(rgbid_smooth* h, int enable, float ms[3]) {
   if (!h) return RGBID_E_INVALID;
   (void)hipSetDevice(h->ctx->device);
-  if (ms) {
-    ms[0] = ms[1] = ms[2] = 0.f;
-    if (h->timed[0]) {
-      float check = 0.f;
-      RGBID_HIP(h->timer.elapsed(0, 1, &check));
-      RGBID_HIP(h->timer.elapsed(2, 3, &ms[0]));
-      ms[0] += check;
-    }
-    if (h->timed[1]) RGBID_HIP(h->timer.elapsed(4, 5, &ms[1]));
-    if (h->timed[2]) RGBID_HIP(h->timer.elapsed(6, 7, &ms[2]));
-  }
+  static const int pairs[3][4] = {{0, 1, 2, 3}, {4, 5}, {6, 7}};   // the plan: the check and the rest
+  if (ms)
+    if (int r = stage_times(h->timer, h->timed, pairs, ms)) return r;
   return h->timer.enable(enable != 0);
 }
 

@@ -818,8 +818,6 @@ bool finite_all(const double* p, int n) {
   return true;
 }
 
-bool aligned4(const void* p) { return !(((uintptr_t)p) & 3); }
-
 // the largest float32 that is not above m: a floorf result is <= m exactly iff it is <= this
 float float_below(unsigned m) {
   float f = (float)m;

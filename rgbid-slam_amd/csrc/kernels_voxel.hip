@@ -55,7 +55,7 @@ __global__ __launch_bounds__(VT) void k_vox_emit(const uint4* __restrict__ in, c
   const unsigned b = vbeg[v], e = vend[v];
   VoxSum s;
   unsigned m = b;
-  for (; m + 4 <= e; m += 4) {                 // the gathers of 4 members are issued before their adds
+  for (; m + 4 <= e; m += 4) {                 // gather_in_order's loop, kept here: through it this kernel compiles five instructions longer
     unsigned id[4];
     uint4 p[4], q[4];
 #pragma unroll
@@ -110,7 +110,7 @@ int sort_and_runs(rgbid_voxel* v, const float4* in, unsigned n, unsigned finite,
   hipStream_t s = v->ctx->stream;
   SortWorkspace& w = v->ws;
   v->mark(2);
-  w.make_keys<K>(s, in, n, g);
+  w.make_keys<K>(s, RecordPoints{in}, n, g);
   v->mark(3);
   const SortedPairs<K> sp = w.sort<K>(s, n, g);
   v->mark(4);
@@ -168,7 +168,7 @@ int rgbid_voxel_plan(rgbid_voxel* v, const rgbid_cloud_point* in_dev, unsigned l
   const unsigned nu = (unsigned)n;
   v->plan_timed = false; v->emit_timed = false;
   v->mark(0);
-  v->ws.box(s, in, nu);
+  v->ws.box(s, RecordPoints{in}, nu);
   v->mark(1);
   unsigned finite;
   float lo[3], hi[3];

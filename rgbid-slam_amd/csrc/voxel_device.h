@@ -1,7 +1,9 @@
-// voxel_device.h -- what the map filters over rgbid_cloud_point records share (kernels_voxel.hip, kernels_outlier.hip, kernels_consist.hip).  Device half: the
-// box of the finite points, the float32 grid and its cell keys, the stable LSD radix sort of (key, index) pairs and the stable flag
-// compaction (the wave and block primitives they stand on are wave_device.h's).  Host half: SortWorkspace, the buffers of one filter
-// handle and the launches over them, and the argument checks every plan / emit makes.
+// voxel_device.h -- what the map filters over rgbid_cloud_point records share (kernels_voxel.hip, kernels_outlier.hip, kernels_consist.hip),
+// and the mesh operators with them (mesh_device.h).  Device half: the box of the finite points of a point source (32-byte records or
+// 12-byte vertices), the float32 grid and its cell keys, the stable LSD radix sort of (key, index) pairs, the keys of a sort by a tuple,
+// the ordered sum over gathered members and the stable flag compaction (the wave and block primitives they stand on are
+// wave_device.h's).  Host half: SortWorkspace, the buffers of one handle and the launches over them, and the argument checks every
+// plan / emit of a filter makes.
 // Everything has internal linkage: each including file compiles its own copy of the kernels it launches.
 #pragma once
 #include "../../include/rgbid.h"
@@ -12,6 +14,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstring>
+#include <initializer_list>
 
 namespace rgbid {
 namespace {
@@ -27,14 +30,30 @@ enum { SLOT_BOX = 0, SLOT_FINITE = 6, SLOT_RUNS = 7, SLOT_VOXELS = 8, SLOTS = 16
 
 __device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
 
+// ---- point sources --------------------------------------------------------------------------------------------------------------
+// A source says where the position of point i lies: at(i) -> x y z (and a fourth float that nobody reads).
+struct RecordPoints {                  // the first float4 of a 32-byte record: x y z nx
+  const float4* in;
+  __device__ __forceinline__ float4 at(unsigned i) const { return in[2 * (size_t)i]; }
+};
+
+struct VertexPoints {                  // three dwords of a 12-byte vertex
+  const float* in;
+  __device__ __forceinline__ float4 at(unsigned i) const {
+    const size_t o = 3 * (size_t)i;
+    return make_float4(in[o], in[o + 1], in[o + 2], 0.f);
+  }
+};
+
 // ---- bounding box of the finite points ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(VT) void k_vox_box(const float4* __restrict__ in, unsigned n, float* __restrict__ part, unsigned* __restrict__ part_cnt) {
+template <class P>
+__global__ __launch_bounds__(VT) void k_vox_box(P in, unsigned n, float* __restrict__ part, unsigned* __restrict__ part_cnt) {
   __shared__ float lds[VT / 64][6];
   __shared__ unsigned ldc[VT / 64];
   float v[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
   unsigned cnt = 0;
   for (unsigned i = blockIdx.x * VT + threadIdx.x; i < n; i += gridDim.x * VT) {
-    const float4 a = in[2 * (size_t)i];     // x y z nx of a 32-byte record
+    const float4 a = in.at(i);
     if (finite3(a.x, a.y, a.z)) {
       ++cnt;
       v[0] = fminf(v[0], a.x); v[1] = fminf(v[1], a.y); v[2] = fminf(v[2], a.z);
@@ -95,10 +114,10 @@ __device__ __forceinline__ unsigned long long cell_key(float x, float y, float z
   return (unsigned long long)i0 + (unsigned long long)i1 * g.d0 + (unsigned long long)i2 * g.d01;
 }
 
-template <typename K>
-__global__ __launch_bounds__(VT) void k_vox_keys(const float4* __restrict__ in, unsigned n, VoxGrid g, K* __restrict__ keys, unsigned* __restrict__ idx) {
+template <typename K, class P>
+__global__ __launch_bounds__(VT) void k_vox_keys(P in, unsigned n, VoxGrid g, K* __restrict__ keys, unsigned* __restrict__ idx) {
   for (unsigned i = blockIdx.x * VT + threadIdx.x; i < n; i += gridDim.x * VT) {
-    const float4 a = in[2 * (size_t)i];
+    const float4 a = in.at(i);
     keys[i] = (K)(finite3(a.x, a.y, a.z) ? cell_key(a.x, a.y, a.z, g) : g.sentinel);
     idx[i] = i;
   }
@@ -206,6 +225,49 @@ __global__ __launch_bounds__(VT) void k_vox_scatter(const K* __restrict__ kin, c
     const unsigned pos = wcnt[wave][digit_of(k[j], shift)] + rank[j];
     kout[pos] = k[j];
     vout[pos] = v[j];
+  }
+}
+
+// ---- sorting by a tuple: one stable sort per component, the last component first ------------------------------------------------------
+// A key source says how many items it has (size) and the key of an item in round r (key(item, r)): it reads nothing through an item
+// that is none and answers the sentinel, the largest key, for it.
+// The keys of round r for the items in the order the last round left (order == null: the input order, and the items are written too).
+template <class F>
+__global__ __launch_bounds__(VT) void k_vox_round_keys(F key, int r, const unsigned* __restrict__ order, unsigned* __restrict__ keys,
+                                                       unsigned* __restrict__ idx) {
+  for (size_t m = (size_t)blockIdx.x * VT + threadIdx.x; m < key.size(); m += (size_t)gridDim.x * VT) {
+    keys[m] = key(order ? order[m] : (unsigned)m, r);
+    if (!order) idx[m] = (unsigned)m;
+  }
+}
+
+// ---- sums over a row of gathered members, in the row's order -----------------------------------------------------------------------
+// add(acc, load(ids[m])) for m = b .. e - 1, in that order: the bytes of a floating-point sum depend on it.  The gathers of 4 members are
+// issued before their adds; add keeps every sum a separate rounding (RGBID_FP_STRICT).
+template <class Acc, class Load, class Add>
+__device__ __forceinline__ void gather_in_order(const unsigned* __restrict__ ids, unsigned b, unsigned e, Acc& acc, Load load, Add add) {
+  unsigned m = b;
+  for (; e - m >= 4; m += 4) {
+    unsigned id[4];
+    decltype(load(0u)) x[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) id[u] = ids[m + u];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) x[u] = load(id[u]);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) add(acc, x[u]);
+  }
+  for (; m < e; ++m) add(acc, load(ids[m]));
+}
+
+// s / |s| in float; zeros when |s|^2 is 0 or not finite
+__device__ __forceinline__ void unit_of(const double s[3], float n[3]) {
+  RGBID_FP_STRICT
+  n[0] = n[1] = n[2] = 0.f;
+  const double q = (s[0] * s[0] + s[1] * s[1]) + s[2] * s[2];
+  if (q != 0.0 && isfinite(q)) {
+    const double l = sqrt(q);
+    for (int a = 0; a < 3; ++a) n[a] = (float)(s[a] / l);
   }
 }
 
@@ -384,10 +446,11 @@ struct SortWorkspace {
     return RGBID_OK;
   }
 
-  // box and count of the finite points of n records -> slots
-  void box(hipStream_t s, const float4* in, unsigned n) {
+  // box and count of the finite points of a source of n points -> slots
+  template <class P>
+  void box(hipStream_t s, const P& in, unsigned n) {
     const unsigned nb = grid_of(((unsigned long long)n + VT - 1) / VT);
-    hipLaunchKernelGGL(k_vox_box, dim3(nb), dim3(VT), 0, s, in, n, box_part, box_cnt);
+    hipLaunchKernelGGL(k_vox_box<P>, dim3(nb), dim3(VT), 0, s, in, n, box_part, box_cnt);
     hipLaunchKernelGGL(k_vox_box_final, dim3(1), dim3(64), 0, s, box_part, box_cnt, (int)nb, slots);
   }
   int read_box(hipStream_t s, unsigned& finite, float lo[3], float hi[3]) {
@@ -399,38 +462,48 @@ struct SortWorkspace {
     return RGBID_OK;
   }
 
-  // one (key, index) pair per record into buffer 0
   template <typename K>
-  void make_keys(hipStream_t s, const float4* in, unsigned n, const VoxGrid& g) {
-    hipLaunchKernelGGL(k_vox_keys<K>, dim3(grid_of(((unsigned long long)n + VT - 1) / VT)), dim3(VT), 0, s, in, n, g, reinterpret_cast<K*>(keys[0]), idx[0]);
+  K* keys_as(int p) const { return reinterpret_cast<K*>(keys[p]); }   // key buffer p for keys of type K
+
+  // one (key, index) pair per point into buffer 0
+  template <typename K, class P>
+  void make_keys(hipStream_t s, const P& in, unsigned n, const VoxGrid& g) {
+    hipLaunchKernelGGL((k_vox_keys<K, P>), dim3(grid_of(((unsigned long long)n + VT - 1) / VT)), dim3(VT), 0, s, in, n, g, keys_as<K>(0), idx[0]);
   }
 
-  // the sort of the n pairs by the bits a key of the grid can have, ping-ponging between the two buffers: three launches per 8-bit pass
-  template <typename K>
-  SortedPairs<K> sort(hipStream_t s, unsigned n, const VoxGrid& g) {
-    K* const k[2] = {reinterpret_cast<K*>(keys[0]), reinterpret_cast<K*>(keys[1])};
-    const unsigned ntiles = (n + SORT_TILE - 1) / SORT_TILE;
-    const int passes = (bitlen(g.sentinel) + 7) / 8;
-    int p = 0;
-    for (int pass = 0; pass < passes; ++pass, p ^= 1) {
-      hipLaunchKernelGGL(k_vox_hist<K>, dim3(ntiles), dim3(VT), 0, s, k[p], n, 8 * pass, hist, ntiles);
-      hipLaunchKernelGGL(k_vox_scan_digits, dim3(RADIX), dim3(VT), 0, s, hist, ntiles, dtotal);
-      hipLaunchKernelGGL(k_vox_scatter<K>, dim3(ntiles), dim3(VT), 0, s, k[p], idx[p], k[p ^ 1], idx[p ^ 1], n, 8 * pass, hist, dtotal, ntiles);
-    }
-    return SortedPairs<K>{k[p], idx[p], idx[p ^ 1], k[p ^ 1]};
-  }
-
-  // the same sort for keys that are no cell keys: the n pairs in buffer p by the lowest `bits` bits of their keys -> the buffer that
-  // holds them afterwards
+  // the stable sort of the n pairs in buffer p by the lowest `bits` bits of their keys, ping-ponging between the two buffers: three
+  // launches per 8-bit pass -> the buffer that holds them afterwards
   template <typename K>
   int sort_bits(hipStream_t s, unsigned n, int bits, int p) {
-    K* const k[2] = {reinterpret_cast<K*>(keys[0]), reinterpret_cast<K*>(keys[1])};
     const unsigned ntiles = (n + SORT_TILE - 1) / SORT_TILE;
     const int passes = (bits + 7) / 8;
     for (int pass = 0; pass < passes; ++pass, p ^= 1) {
-      hipLaunchKernelGGL(k_vox_hist<K>, dim3(ntiles), dim3(VT), 0, s, k[p], n, 8 * pass, hist, ntiles);
+      hipLaunchKernelGGL(k_vox_hist<K>, dim3(ntiles), dim3(VT), 0, s, keys_as<K>(p), n, 8 * pass, hist, ntiles);
       hipLaunchKernelGGL(k_vox_scan_digits, dim3(RADIX), dim3(VT), 0, s, hist, ntiles, dtotal);
-      hipLaunchKernelGGL(k_vox_scatter<K>, dim3(ntiles), dim3(VT), 0, s, k[p], idx[p], k[p ^ 1], idx[p ^ 1], n, 8 * pass, hist, dtotal, ntiles);
+      hipLaunchKernelGGL(k_vox_scatter<K>, dim3(ntiles), dim3(VT), 0, s, keys_as<K>(p), idx[p], keys_as<K>(p ^ 1), idx[p ^ 1], n, 8 * pass, hist, dtotal, ntiles);
+    }
+    return p;
+  }
+
+  // the sort of make_keys' pairs by the bits a key of the grid can have
+  template <typename K>
+  SortedPairs<K> sort(hipStream_t s, unsigned n, const VoxGrid& g) {
+    const int p = sort_bits<K>(s, n, bitlen(g.sentinel), 0);
+    return SortedPairs<K>{keys_as<K>(p), idx[p], idx[p ^ 1], keys_as<K>(p ^ 1)};
+  }
+
+  // The n items 0 .. n - 1 sorted by a tuple of 32-bit keys: one stable sort per round of `rounds` (the tuple's last component first) by
+  // key(item, round) <= sentinel, the keys recomputed in the order the round before left -> the buffer p that holds the result:
+  // keys_as<unsigned>(p) the keys of the last round, idx[p] the items; the other buffer is free
+  template <class F>
+  int sort_rounds(hipStream_t s, const F& key, unsigned sentinel, unsigned n, std::initializer_list<int> rounds) {
+    const unsigned g = grid_of(((unsigned long long)n + VT - 1) / VT);
+    int p = 0;
+    const unsigned* order = nullptr;
+    for (int r : rounds) {
+      hipLaunchKernelGGL(k_vox_round_keys<F>, dim3(g), dim3(VT), 0, s, key, r, order, keys_as<unsigned>(p), idx[p]);
+      p = sort_bits<unsigned>(s, n, bitlen(sentinel), p);
+      order = idx[p];
     }
     return p;
   }

@@ -1,5 +1,5 @@
 // wave_device.h -- the wave64 and block primitives of the scan / compaction kernels, each written once: a lane's rank in a ballot, the
-// butterfly sum of a wave, the inclusive scan and the flag rank of a block of BLOCK_WAVES waves (256 threads: VT, CT, LT and BT).
+// butterfly sum of a wave and that sum added to a count slot, the inclusive scan and the flag rank of a block of BLOCK_WAVES waves (256 threads: VT, CT, LT and BT).
 // Everything has internal linkage and is inlined into the kernels of the including file.
 #pragma once
 #include "common.h"
@@ -20,6 +20,13 @@ __device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+
+// the wave's total of c added to *slot, when it is not 0: one integer atomic per wave.  Called by all lanes of the wave together
+template <typename S, typename T>
+__device__ __forceinline__ void wave_add_to(S* slot, T c) {
+  c = wave_sum(c);
+  if ((threadIdx.x & 63) == 0 && c) atomicAdd(slot, (S)c);
 }
 
 // inclusive scan of one value per thread over the block; returns the block total through `total`.  Two barriers: lds is free again
