@@ -108,6 +108,11 @@ int rgbid_frame_px_batched(rgbid_ctx*, int lanes, const rgbid_imgb* depth_u16, c
 typedef struct rgbid_scale_pair { float bias_depthinv, sigma_depthinv, nu_depthinv, bias_int, sigma_int, nu_int; } rgbid_scale_pair;
 int rgbid_sigma_pair_batched(rgbid_ctx*, int lanes, const float* res_dev, size_t res_lane_stride, int n, int mestimator,
                              rgbid_scale_pair* out, float* ms);
+/* the same estimate with the residual lattice (W1 - W0) | (I1 - I0) sampled straight from four stored maps (computeErrorGridStride :701-765 inside the
+ * kernel: what the engine's unfused path launches).  Same samples, same thread assignment and same arithmetic as rgbid_sigma_pair_batched on the two
+ * lattice arrays of these maps: the results are bit-identical. */
+int rgbid_sigma_pair_maps_batched(rgbid_ctx*, int lanes, const rgbid_imgb* W1, const rgbid_imgb* W0, const rgbid_imgb* I1, const rgbid_imgb* I0,
+                                  int min_nsamples, int mestimator, rgbid_scale_pair* out, float* ms);
 
 /* ---- keyframe fusion / maps / covisibility -------------------------------------------------------------------------------------------- */
 /* warpInvDepthWithTrafo3DWeighted + integrateWarpedFrame (warping_registration.cu:549-669) in one pass: kf_depthinv / kf_weight updated

@@ -289,6 +289,25 @@ int rgbid_sigma_pair_batched(rgbid_ctx* c, int lanes, const float* res_dev, size
   return RGBID_OK;
 }
 
+int rgbid_sigma_pair_maps_batched(rgbid_ctx* c, int lanes, const rgbid_imgb* W1, const rgbid_imgb* W0, const rgbid_imgb* I1, const rgbid_imgb* I0, int min_nsamples,
+                                  int mestimator, rgbid_scale_pair* out, float* ms) {
+  const rgbid_imgb* all[4] = {W1, W0, I1, I0};
+  if (!c || lanes < 1 || !out || mestimator < RGBID_LSQ || mestimator > RGBID_STUDENT) return RGBID_E_INVALID;
+  for (int i = 0; i < 4; ++i) if (!ok_b(all[i], lanes) || !same_b(all[i], W0)) return RGBID_E_INVALID;
+  hipSetDevice(c->device);
+  int e = ctx_reserve_lane(c, sizeof(SysParams) * lanes);
+  if (e) return e;
+  SysParams* sp = reinterpret_cast<SysParams*>(c->lane_dev);
+  RGBID_HIP(hipMemsetAsync(sp, 0, sizeof(SysParams) * lanes, c->stream));
+  Call call(c, ms);
+  launch_sigma_pair(c->stream, lanes, BB(W1, lanes), BB(W0, lanes), BB(I1, lanes), BB(I0, lanes), min_nsamples, sp, mestimator, ALL);
+  e = call.finish(sp, sizeof(SysParams) * lanes, 0);
+  if (e) return e;
+  const SysParams* h = reinterpret_cast<const SysParams*>(c->lane_host);
+  for (int l = 0; l < lanes; ++l) out[l] = rgbid_scale_pair{h[l].bias_d, h[l].sigma_d, h[l].nu_d, h[l].bias_i, h[l].sigma_i, h[l].nu_i};
+  return RGBID_OK;
+}
+
 int rgbid_fuse_frame_batched(rgbid_ctx* c, int lanes, const rgbid_imgb* cur, const rgbid_imgb* kf, const rgbid_imgb* kfw, const rgbid_imgb* wweight,
                              const float* R, const float* t, int numerics, float* ms) {
   const rgbid_imgb* all[4] = {cur, kf, kfw, wweight};

@@ -95,6 +95,15 @@ struct Samples {
   }
   // number of slots the passes visit, as the float the count sums add up to (exact)
   __device__ __forceinline__ float slots() const { return (float)cnt; }
+  // Register path: every slot this thread visits is invalid or padding.  Its sums are then cnt f(0) - cnt f(0), which fp32 cancels only to rounding (3 f(0), 5 f(0),
+  // ... are not representable; a pair's shared logarithm is not twice a single one), and the residue is the SAME in every such thread: at n = 64 some 450
+  // threads add it up against the sums of a few dozen valid samples (measured: bias and sigma 1.1e-4 sigma off the oracle in computeSigmaPdf at 6 valid samples,
+  // 2.5e-5 at 45).  Such a thread contributes exact zeros instead (zero_sums): one compare and four selects per thread and pass.
+  __device__ __forceinline__ bool all_invalid() const { return REG && neg_ninv == -(float)cnt; }
+  template <class A>
+  __device__ __forceinline__ void zero_sums(A (&a)[4]) const { RGBID_FP_STRICT
+    if (all_invalid()) { a[0] = 0; a[1] = 0; a[2] = 0; a[3] = 0; }
+  }
   // After the last moments pass the residuals themselves are no longer needed: the nu bisection only uses en^2 = ((e - bias)/sigma)^2,
   // the same for every candidate nu, so the register copy is overwritten with it once (no extra VGPRs, 3 instructions less per
   // sample and pass).  The streaming path recomputes it on the fly.
@@ -232,6 +241,7 @@ __device__ __forceinline__ void pass_moments(const SM& S, float bias, float sigm
       acc(er, weight * mv, is_valid * mv);
     });
   }
+  S.zero_sums(a);
   double t[4];
   float af[4] = {(float)a[0], (float)a[1], (float)a[2], (float)a[3]};
   block_sum4(af, t, sm);
@@ -278,13 +288,13 @@ __device__ __forceinline__ float func_weights_nu(const SM& S, float bias, float 
   }
   a[0] = (typename SM::Acc)0.69314718055994531 * a[0] + (typename SM::Acc)__logf(nup1) * a[2];
   a[1] *= nup1;
+  S.zero_sums(a);
   double t[4];
   float af[4] = {(float)a[0], (float)a[1], (float)a[2], 0.f};
   block_sum4(af, t, sm);
   // No valid sample at all (a keyframe pair whose second inverse-depth map is empty): the reference's sums are exactly 0 and its mean is 0 / 0 = NaN, which
-  // fails every comparison of the bisection and leaves nu = 9.75.  The register path's sums cancel only to a few ulp there (sum over all slots minus
-  // n_invalid times the slot's value, the pair sharing one logarithm), and residue / 0 = +-inf walked the bisection to some other nu.
-  if (t[2] == 0.0) return qnan();
+  // fails every comparison of the bisection and leaves nu = 9.75.  Here every thread is all_invalid() then and the three sums are exact zeros as well
+  // (before zero_sums the register path's residue / 0 = +-inf walked the bisection to some other nu, and a guard on t[2] == 0 stood here).
   return ((float)t[0] - (float)t[1]) / (float)t[2];
 }
 

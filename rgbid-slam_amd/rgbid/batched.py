@@ -20,6 +20,7 @@ BATCHED_EXPORTS = [
     "rgbid_lattice_residuals_batched", "rgbid_sigma_pair_batched", "rgbid_fuse_frame_batched", "rgbid_kf_maps_batched",
     "rgbid_visibility_pair_batched", "rgbid_prep_frame_batched", "rgbid_pyr_down_batched", "rgbid_compute_gradient_batched",
     "rgbid_bilateral_filter_batched", "rgbid_gradient_keep_batched", "rgbid_lattice_residuals_raw_batched", "rgbid_frame_px_batched",
+    "rgbid_sigma_pair_maps_batched",
 ]
 
 
@@ -147,6 +148,16 @@ class Batched:
         ms = C.c_float()
         check(self.L.rgbid_sigma_pair_batched(self._h, lanes, C.c_void_p(res.data_ptr()), C.c_size_t(res.stride(0)), int(n), int(mestimator), out,
                                               C.byref(ms)))
+        return [dict(bias_depthinv=o.bias_depthinv, sigma_depthinv=o.sigma_depthinv, nu_depthinv=o.nu_depthinv, bias_int=o.bias_int,
+                     sigma_int=o.sigma_int, nu_int=o.nu_int) for o in out]
+
+    def sigma_pair_maps(self, W1, W0, I1, I0, min_nsamples, mestimator=3):
+        """sigma_pair with the residual lattice sampled from the four maps inside the kernel"""
+        lanes = W0.shape[0]
+        out = (ScalePair * lanes)()
+        ms = C.c_float()
+        check(self.L.rgbid_sigma_pair_maps_batched(self._h, lanes, *[C.byref(imgb(t)) for t in (W1, W0, I1, I0)], int(min_nsamples), int(mestimator), out,
+                                                   C.byref(ms)))
         return [dict(bias_depthinv=o.bias_depthinv, sigma_depthinv=o.sigma_depthinv, nu_depthinv=o.nu_depthinv, bias_int=o.bias_int,
                      sigma_int=o.sigma_int, nu_int=o.nu_int) for o in out]
 

@@ -217,12 +217,13 @@ def build_system(W0, I0, gWx, gWy, gIx, gIy, W1, I1, K, sigma_d, sigma_i, bias_d
     return A, b
 
 
-def sigma_nu_student(err, bias, sigma, mestimator=3):
+def sigma_nu_student(err, bias, sigma, mestimator=3, trace=None):
     """computeSigmaAndNuStudent, src/cuda/sigmaFuncs.cu:858-1066 with partialBiasAndSigmaStudent :281-332, finalReductionBiasAndSigma :361-407,
     partialFuncWeightsNu :410-468 and its final reduction :471-512.  Returns (bias, sigma, nu).
     IRLS: first pass least squares, then Student weights with nu = 5, at most 10 passes, stop when sigma changes by < 10 %;
     nu: bisection of C(nu) = -psi(nu/2) + ln(nu/2) + mean(ln w - w) + 1 + psi((nu+1)/2) - ln((nu+1)/2) on [2, 10], at most 5 steps,
-    stopping when the bracket is below 1; returns the last midpoint."""
+    stopping when the bracket is below 1; returns the last midpoint.
+    trace (optional list) receives |s - s_prev| / s_prev of every pass that evaluates the stop test."""
     from scipy.special import digamma
     e = np.asarray(err, np.float64)
     e = e[np.isfinite(e)]
@@ -238,8 +239,12 @@ def sigma_nu_student(err, bias, sigma, mestimator=3):
         s = np.sqrt((swsr - 2.0 * b * swr + b * b * sw) / n)
         prev = sh_sigma
         sh_bias, sh_sigma, mest = b, s, mestimator
-        if i > 0 and abs(s - prev) / prev < 0.1:
-            break
+        if i > 0:
+            ratio = abs(s - prev) / prev
+            if trace is not None:
+                trace.append(ratio)
+            if ratio < 0.1:
+                break
 
     return sh_bias, sh_sigma, _nu_bisection(e, sh_bias, sh_sigma)
 
@@ -666,10 +671,10 @@ def _m_weight(en, mest):
     return w, ok
 
 
-def sigma_pdf(err, bias, sigma, mestimator=3):
+def sigma_pdf(err, bias, sigma, mestimator=3, trace=None):
     """computeSigmaPdf, src/cuda/sigmaFuncs.cu:773-854 with partialBiasAndSigma :179-255: IRLS bias / scale with a fixed M-estimator (first pass
     least squares), at most 10 passes, stop when sigma changes by < 10 % -- here the comparison is against the PREVIOUS pass's sigma and the
-    returned values are those of the last pass."""
+    returned values are those of the last pass.  trace (optional list) receives |s - s_prev| / s_prev of every pass that evaluates the stop test."""
     e = np.asarray(err, np.float64); e = e[np.isfinite(e)]
     sh_b, sh_s, mest = float(bias), float(sigma), 0
     b = s = None
@@ -678,8 +683,12 @@ def sigma_pdf(err, bias, sigma, mestimator=3):
         swr, swsr, sw, n = (e * w).sum(), (e * e * w).sum(), w.sum(), ok.sum()
         b = swr / sw
         s = np.sqrt((swsr - 2.0 * b * swr + b * b * sw) / n)
-        if i > 0 and abs(s - sh_s) / sh_s < 0.1:
-            break
+        if i > 0:
+            ratio = abs(s - sh_s) / sh_s
+            if trace is not None:
+                trace.append(ratio)
+            if ratio < 0.1:
+                break
         sh_b, sh_s, mest = b, s, mestimator
     return b, s
 
