@@ -149,6 +149,20 @@ int rgbid_gradient_keep_batched(rgbid_ctx*, int lanes, const rgbid_imgb* src, co
 /* bilateralFilter (filters.cu:139-162); numerics FAST = the engine's v_exp_f32 kernel */
 int rgbid_bilateral_filter_batched(rgbid_ctx*, int lanes, const rgbid_imgb* src, const rgbid_imgb* dst, float sigma_floatmap,
                                    int numerics, float* ms);
+/* The two-map launches the engine and the keyframe aligner issue -- the intensity and the inverse-depth map of one pyramid level in ONE launch
+ * instead of two -- as calls of their own, so that tests reach them directly.  Every map passes the checks of its one-map sibling above; each
+ * call's results are those of the two one-map calls bit for bit.  Two maps of unlike geometry are legal: the launcher then takes the one-map
+ * path for each.  rgbid_gradient_keep_pair_batched refuses (RGBID_E_INVALID) a map off the 16-byte path like its sibling; the outputs of a
+ * refused call are unspecified. */
+int rgbid_pyr_down_pair_batched(rgbid_ctx*, int lanes, const rgbid_imgb* src0, const rgbid_imgb* dst0, const rgbid_imgb* src1,
+                                const rgbid_imgb* dst1, float* ms);
+int rgbid_gradient_pair_batched(rgbid_ctx*, int lanes, const rgbid_imgb* src0, const rgbid_imgb* dst_hor0, const rgbid_imgb* dst_vert0,
+                                const rgbid_imgb* src1, const rgbid_imgb* dst_hor1, const rgbid_imgb* dst_vert1, float* ms);
+int rgbid_gradient_keep_pair_batched(rgbid_ctx*, int lanes, const rgbid_imgb* src0, const rgbid_imgb* dst_hor0, const rgbid_imgb* dst_vert0,
+                                     const rgbid_imgb* keep0, const rgbid_imgb* src1, const rgbid_imgb* dst_hor1,
+                                     const rgbid_imgb* dst_vert1, const rgbid_imgb* keep1, float* ms);
+int rgbid_bilateral_pair_batched(rgbid_ctx*, int lanes, const rgbid_imgb* src0, const rgbid_imgb* dst0, float sigma_floatmap0,
+                                 const rgbid_imgb* src1, const rgbid_imgb* dst1, float sigma_floatmap1, int numerics, float* ms);
 
 #ifdef __cplusplus
 }

@@ -412,4 +412,55 @@ int rgbid_bilateral_filter_batched(rgbid_ctx* c, int lanes, const rgbid_imgb* sr
   return call.finish();
 }
 
+// ---- the two-map launches the engine and kfalign.hip issue (intensity + inverse depth of one level in ONE launch), as calls of their own: each map
+// passes its one-map sibling's checks; maps of unlike geometry are legal (the launcher then takes the one-map path twice)
+int rgbid_pyr_down_pair_batched(rgbid_ctx* c, int lanes, const rgbid_imgb* src0, const rgbid_imgb* dst0, const rgbid_imgb* src1, const rgbid_imgb* dst1, float* ms) {
+  if (!c || lanes < 1 || !ok_b(src0, lanes) || !ok_b(dst0, lanes) || dst0->rows != src0->rows / 2 || dst0->cols != src0->cols / 2 || !ok_b(src1, lanes) ||
+      !ok_b(dst1, lanes) || dst1->rows != src1->rows / 2 || dst1->cols != src1->cols / 2)
+    return RGBID_E_INVALID;
+  hipSetDevice(c->device);
+  Call call(c, ms);
+  launch_pyr_down2(c->stream, lanes, BB(src0, lanes), BB(dst0, lanes), BB(src1, lanes), BB(dst1, lanes), ALL);
+  return call.finish();
+}
+
+int rgbid_gradient_pair_batched(rgbid_ctx* c, int lanes, const rgbid_imgb* src0, const rgbid_imgb* gx0, const rgbid_imgb* gy0, const rgbid_imgb* src1,
+                                const rgbid_imgb* gx1, const rgbid_imgb* gy1, float* ms) {
+  if (!c || lanes < 1 || !ok_b(src0, lanes) || !ok_b(gx0, lanes) || !ok_b(gy0, lanes) || !same_b(src0, gx0) || !same_b(src0, gy0) || !ok_b(src1, lanes) ||
+      !ok_b(gx1, lanes) || !ok_b(gy1, lanes) || !same_b(src1, gx1) || !same_b(src1, gy1))
+    return RGBID_E_INVALID;
+  hipSetDevice(c->device);
+  Call call(c, ms);
+  launch_gradient2(c->stream, lanes, BB(src0, lanes), BB(gx0, lanes), BB(gy0, lanes), BB(src1, lanes), BB(gx1, lanes), BB(gy1, lanes), ALL);
+  return call.finish();
+}
+
+int rgbid_gradient_keep_pair_batched(rgbid_ctx* c, int lanes, const rgbid_imgb* src0, const rgbid_imgb* gx0, const rgbid_imgb* gy0, const rgbid_imgb* keep0,
+                                     const rgbid_imgb* src1, const rgbid_imgb* gx1, const rgbid_imgb* gy1, const rgbid_imgb* keep1, float* ms) {
+  if (!c || lanes < 1 || !ok_b(src0, lanes) || !ok_b(gx0, lanes) || !ok_b(gy0, lanes) || !ok_b(keep0, lanes) || !same_b(src0, gx0) || !same_b(src0, gy0) ||
+      !same_b(src0, keep0) || src0->data == keep0->data || !ok_b(src1, lanes) || !ok_b(gx1, lanes) || !ok_b(gy1, lanes) || !ok_b(keep1, lanes) ||
+      !same_b(src1, gx1) || !same_b(src1, gy1) || !same_b(src1, keep1) || src1->data == keep1->data)
+    return RGBID_E_INVALID;
+  hipSetDevice(c->device);
+  Call call(c, ms);
+  const ImgB s0 = BB(src0, lanes), x0 = BB(gx0, lanes), y0 = BB(gy0, lanes), k0 = BB(keep0, lanes), s1 = BB(src1, lanes), x1 = BB(gx1, lanes), y1 = BB(gy1, lanes),
+             k1 = BB(keep1, lanes);
+  // as the engine does: the two-map launch, else each map on its own; a map off the 16-byte path is refused like rgbid_gradient_keep_batched refuses it
+  bool launched = launch_gradient_keep2(c->stream, lanes, s0, x0, y0, k0, s1, x1, y1, k1, ALL);
+  if (!launched) launched = launch_gradient_keep(c->stream, lanes, s0, x0, y0, k0, ALL) && launch_gradient_keep(c->stream, lanes, s1, x1, y1, k1, ALL);
+  const int r = call.finish();
+  return launched ? r : RGBID_E_INVALID;
+}
+
+int rgbid_bilateral_pair_batched(rgbid_ctx* c, int lanes, const rgbid_imgb* src0, const rgbid_imgb* dst0, float sigma0, const rgbid_imgb* src1, const rgbid_imgb* dst1,
+                                 float sigma1, int numerics, float* ms) {
+  if (!c || lanes < 1 || !ok_b(src0, lanes) || !ok_b(dst0, lanes) || !same_b(src0, dst0) || src0->data == dst0->data || !ok_b(src1, lanes) || !ok_b(dst1, lanes) ||
+      !same_b(src1, dst1) || src1->data == dst1->data || !numerics_ok(numerics) || !(sigma0 > 0.f) || !(sigma1 > 0.f))
+    return RGBID_E_INVALID;
+  hipSetDevice(c->device);
+  Call call(c, ms);
+  launch_bilateral2(c->stream, lanes, BB(src0, lanes), BB(dst0, lanes), sigma0, BB(src1, lanes), BB(dst1, lanes), sigma1, ALL, numerics == RGBID_NUMERICS_FAST);
+  return call.finish();
+}
+
 }  // extern "C"

@@ -20,7 +20,8 @@ BATCHED_EXPORTS = [
     "rgbid_lattice_residuals_batched", "rgbid_sigma_pair_batched", "rgbid_fuse_frame_batched", "rgbid_kf_maps_batched",
     "rgbid_visibility_pair_batched", "rgbid_prep_frame_batched", "rgbid_pyr_down_batched", "rgbid_compute_gradient_batched",
     "rgbid_bilateral_filter_batched", "rgbid_gradient_keep_batched", "rgbid_lattice_residuals_raw_batched", "rgbid_frame_px_batched",
-    "rgbid_sigma_pair_maps_batched",
+    "rgbid_sigma_pair_maps_batched", "rgbid_pyr_down_pair_batched", "rgbid_gradient_pair_batched", "rgbid_gradient_keep_pair_batched",
+    "rgbid_bilateral_pair_batched",
 ]
 
 
@@ -210,4 +211,27 @@ class Batched:
         ms = C.c_float()
         check(self.L.rgbid_bilateral_filter_batched(self._h, src.shape[0], C.byref(imgb(src)), C.byref(imgb(dst)), C.c_float(sigma_floatmap),
                                                     int(bool(fast)), C.byref(ms)))
+        return ms.value
+
+    # ---- the engine's two-map launches (two maps of one pyramid level in one launch), each the bits of its two one-map calls ----
+    def pyr_down_pair(self, src0, dst0, src1, dst1):
+        ms = C.c_float()
+        check(self.L.rgbid_pyr_down_pair_batched(self._h, src0.shape[0], *[C.byref(imgb(t)) for t in (src0, dst0, src1, dst1)], C.byref(ms)))
+        return ms.value
+
+    def gradient_pair(self, src0, gx0, gy0, src1, gx1, gy1):
+        ms = C.c_float()
+        check(self.L.rgbid_gradient_pair_batched(self._h, src0.shape[0], *[C.byref(imgb(t)) for t in (src0, gx0, gy0, src1, gx1, gy1)], C.byref(ms)))
+        return ms.value
+
+    def gradient_keep_pair(self, src0, gx0, gy0, keep0, src1, gx1, gy1, keep1):
+        ms = C.c_float()
+        check(self.L.rgbid_gradient_keep_pair_batched(self._h, src0.shape[0], *[C.byref(imgb(t)) for t in (src0, gx0, gy0, keep0, src1, gx1, gy1, keep1)],
+                                                      C.byref(ms)))
+        return ms.value
+
+    def bilateral_pair(self, src0, dst0, sigma0, src1, dst1, sigma1, fast=False):
+        ms = C.c_float()
+        check(self.L.rgbid_bilateral_pair_batched(self._h, src0.shape[0], C.byref(imgb(src0)), C.byref(imgb(dst0)), C.c_float(sigma0), C.byref(imgb(src1)),
+                                                  C.byref(imgb(dst1)), C.c_float(sigma1), int(bool(fast)), C.byref(ms)))
         return ms.value
