@@ -123,6 +123,15 @@ def main():
                          "--mesh-normals, mesh_NNNN_shaded.png into DIR")
     ap.add_argument("--mesh-raster-check", action="store_true",
                     help="with --mesh: print how well the written mesh, rasterised at each keyframe's pose, agrees with the depth the keyframe measured")
+    ap.add_argument("--mesh-deviation", type=float, default=None, metavar="D",
+                    help="with --mesh and at least one of --mesh-min-component / --mesh-largest-components / --mesh-simplify / --mesh-smooth: print how far "
+                         "the written mesh lies from the mesh as extracted, without those options, and the other way round (DESIGN.md section 26): "
+                         "the distances of the vertices of one to the surface of the other, truncated at D metres")
+    ap.add_argument("--mesh-reference", default="", metavar="MODEL.ply",
+                    help="with --mesh: print how far the written mesh lies from the triangle mesh MODEL.ply (a PLY as --mesh writes it, in the "
+                         "world frame) and the other way round")
+    ap.add_argument("--mesh-reference-distance", type=float, default=None, metavar="D",
+                    help="with --mesh-reference: the truncation distance in metres (default: the volume's truncation distance)")
     ap.add_argument("--mesh-align-check", action="store_true",
                     help="with --mesh: fuse the even-numbered keyframes, align the odd-numbered ones to that model (DESIGN.md section 21) and print "
                          "the corrections the alignment proposes; nothing is applied")
@@ -204,6 +213,13 @@ def main():
         ap.error("--mesh-smooth needs --mesh")
     if args.mesh_smooth is None and (args.mesh_smooth_lambda is not None or args.mesh_smooth_mu is not None or args.mesh_smooth_pin_boundary):
         ap.error("--mesh-smooth-lambda / --mesh-smooth-mu / --mesh-smooth-pin-boundary need --mesh-smooth")
+    if not args.mesh and (args.mesh_deviation is not None or args.mesh_reference or args.mesh_reference_distance is not None):
+        ap.error("--mesh-deviation / --mesh-reference / --mesh-reference-distance need --mesh")
+    if args.mesh_reference_distance is not None and not args.mesh_reference:
+        ap.error("--mesh-reference-distance needs --mesh-reference")
+    if args.mesh_deviation is not None and (args.mesh_min_component is None and args.mesh_largest_components is None and args.mesh_simplify is None
+                                            and args.mesh_smooth is None):
+        ap.error("--mesh-deviation needs at least one of --mesh-min-component / --mesh-largest-components / --mesh-simplify / --mesh-smooth")
     mesh_filter = {}
     if args.mesh:
         from rgbid import tsdf as TS
@@ -228,6 +244,18 @@ def main():
                 mesh_filter["smooth"] = TS.smooth_arg(dict(iterations=args.mesh_smooth, lam=0.5 if args.mesh_smooth_lambda is None else args.mesh_smooth_lambda,
                                                            mu=-0.53 if args.mesh_smooth_mu is None else args.mesh_smooth_mu,
                                                            pin_boundary=args.mesh_smooth_pin_boundary))
+            reference = None
+            if args.mesh_deviation is not None or args.mesh_reference:
+                from rgbid import meshdist as MD
+                if args.mesh_deviation is not None:
+                    MD.distance_arg(args.mesh_deviation)
+                if args.mesh_reference:
+                    reference_distance = MD.distance_arg(mesh["trunc"] if args.mesh_reference_distance is None else args.mesh_reference_distance)
+                    try:
+                        with open(args.mesh_reference, "rb") as f:
+                            reference = TS.read_mesh_ply(f.read())
+                    except (OSError, ValueError, IndexError, UnicodeDecodeError) as e:
+                        raise ValueError(f"--mesh-reference: cannot read {args.mesh_reference}: {e}") from None
         except ValueError as e:
             ap.error(str(e))
     if (args.cloud_radius is None) != (args.cloud_min_neighbours is None):
@@ -374,9 +402,10 @@ def main():
         if not pc.keyframes:
             sys.exit(f"rank {rank}: --mesh: the run exported no keyframe")
         cast = bool(args.mesh_render or args.mesh_render_check)
+        keep = cast or args.mesh_deviation is not None          # the deviation extracts the volume once more, without the clean-up options
         try:
             fused = TS.fuse(ctx, pc.keyframes, tuple(args.K), args.rows, args.cols, points=pc.points, return_volume=True, normals=args.mesh_normals,
-                            keep_volume=cast, **mesh, **mesh_filter)
+                            keep_volume=keep, **mesh, **mesh_filter)
         except ValueError as e:
             sys.exit(f"rank {rank}: --mesh: {e}")
         verts, cols, tris = fused[:3]
@@ -398,6 +427,23 @@ def main():
         if smo:
             print(f"rank {rank}: mesh smooth: {smo['iterations']} iterations of lambda {smo['lam']:g}, mu {smo['mu']:g}, {smo['edges']} edges, "
                   f"{smo['boundary_vertices']} boundary vertices, {'pinned' if smo['pin_boundary'] else 'not pinned'}")
+        if args.mesh_deviation is not None or args.mesh_reference:
+            dev = lambda x: torch.from_numpy(np.ascontiguousarray(x.view(np.int32) if x.dtype == np.uint32 else x)).to(verts.device)
+            try:
+                if args.mesh_deviation is not None:
+                    raw = fused[-1].extract(mesh["min_weight"], colours=False)
+                    figures = MD.mesh_deviation(ctx, verts, tris, raw[0], raw[2], args.mesh_deviation)
+                    print(f"rank {rank}: mesh deviation: written -> extracted: {MD.summary_line(figures['a_to_b'])}")
+                    print(f"rank {rank}: mesh deviation: extracted -> written: {MD.summary_line(figures['b_to_a'])}")
+                if reference is not None:
+                    figures = MD.mesh_deviation(ctx, verts, tris, dev(reference[0]), dev(reference[2]), reference_distance)
+                    print(f"rank {rank}: mesh reference: written -> {args.mesh_reference}: {MD.summary_line(figures['a_to_b'])}")
+                    print(f"rank {rank}: mesh reference: {args.mesh_reference} -> written: {MD.summary_line(figures['b_to_a'])}")
+            except (ValueError, RuntimeError) as e:
+                sys.exit(f"rank {rank}: --mesh-deviation / --mesh-reference: {e}")
+            finally:
+                if keep and not cast:                       # otherwise the ray casts below close the volume
+                    fused[-1].close()
         if cast:
             volume = fused[-1]
             try:
