@@ -7,6 +7,8 @@ import ctypes as C
 import os
 import subprocess
 
+from . import _args
+
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ROOT = os.path.dirname(_PKG)
 # RGBID_HIP_LIB: an alternative build of the same library (A/B experiments with other -D flags: tools/kernel_bench.py); never a CPU path
@@ -56,17 +58,54 @@ def check(err):
         raise RgbidError(f"rgbid error {err}: {lib().rgbid_error_string(err).decode()}")
 
 
+# what a signature table is written in: pointer (or array), int, unsigned, long long, unsigned long long, float, double
+vp, ci, cu, i64, u64, f32, f64 = C.c_void_p, C.c_int, C.c_uint, C.c_longlong, C.c_ulonglong, C.c_float, C.c_double
+_bound = set()
+
+
+def bind(table):
+    """-> the library, with the argument types of `table` (C function -> tuple of ctypes, a module's SIGNATURES) set: once per process
+    and table, for every instance and every module-level call.  tests/test_abi.py holds the tables to the prototypes of include/."""
+    L = lib()
+    if id(table) not in _bound:
+        for name, types in table.items():
+            getattr(L, name).argtypes = list(types)
+        _bound.add(id(table))
+    return L
+
+
 class CtxHandle:
     """A C-ABI handle created on a device.Context: it uses the context's device and stream, so it is destroyed before the context is
-    (Context.close() closes its dependents first) and never after it."""
-    _destroy = None   # name of the C destroy function
+    (Context.close() closes its dependents first) and never after it.  A binding takes from here what every handle needs: the library
+    bound to its module's table (_signatures), the device string, the device pointers and the read-out of its stage timing."""
+    _destroy = None      # name of the C destroy function
+    _signatures = {}     # the module's SIGNATURES
+    _timing = None       # name of the C function behind timing(), and the stages it reports
+    _stages = ()
+    ptr, opt_ptr = staticmethod(_args.ptr), staticmethod(_args.opt_ptr)
 
     def __init__(self, ctx):
-        self.ctx, self.L, self._h = ctx, lib(), C.c_void_p()
+        self.ctx, self.L, self._h = ctx, bind(self._signatures), C.c_void_p()
 
     def _created(self, err):
         check(err)
         self.ctx._dependents.add(self)
+
+    @property
+    def _dev(self):
+        return f"cuda:{self.ctx.device}"
+
+    def _stage_ms(self, function, stages, *switch):
+        """the read-out of a stage timer: the C function `function`(handle, *switch, float ms[len(stages)]) -> {stage: ms}"""
+        ms = (f32 * len(stages))()
+        check(getattr(self.L, function)(self._h, *switch, ms))
+        return dict(zip(stages, ms[:]))
+
+    def timing(self, enable=True):
+        """record HIP events around the stages of the following calls; -> the device ms of the last ones {stage: ms}"""
+        if self._timing is None:
+            raise AttributeError(f"{type(self).__name__} has no stage timing")
+        return self._stage_ms(self._timing, self._stages, int(enable))
 
     def close(self):
         if self._h:

@@ -13,23 +13,33 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import check
+from ._lib import check, ci, vp
 
 ENTRY_DTYPE = np.dtype([("word", "<u4"), ("value", "<u4")])
 assert ENTRY_DTYPE.itemsize == 8
 MAX_K, MAX_DEPTH, MAX_LEAVES, MAX_ITERS, MAX_SHORTLIST = 16, 6, 1 << 20, 64, 64
 ONE = 1 << 30                  # what the values of a vector sum to (at most)
-EXPORTS = ["rgbid_bow_create", "rgbid_bow_destroy", "rgbid_bow_max_nodes", "rgbid_bow_train", "rgbid_bow_set_weights", "rgbid_bow_export",
-           "rgbid_bow_import", "rgbid_bow_transform", "rgbid_bow_score", "rgbid_bow_shortlist", "rgbid_bow_timing"]
+SIGNATURES = {
+    "rgbid_bow_create": (vp, vp, ci, ci),
+    "rgbid_bow_destroy": (vp,),
+    "rgbid_bow_max_nodes": (ci, ci, vp),
+    "rgbid_bow_train": (vp, vp, vp, ci, ci, ci),
+    "rgbid_bow_set_weights": (vp, vp, vp, ci, ci),
+    "rgbid_bow_export": (vp, vp, vp, vp, vp),
+    "rgbid_bow_import": (vp, ci, vp, vp, vp),
+    "rgbid_bow_transform": (vp, vp, vp, ci, ci, vp, vp, vp),
+    "rgbid_bow_score": (vp, vp, vp, ci, ci, vp, ci, vp),
+    "rgbid_bow_shortlist": (vp, vp, vp, ci, ci, ci, ci, vp, vp),
+    "rgbid_bow_timing": (vp, ci, vp),
+}
+EXPORTS = list(SIGNATURES)
 STAGES = ("train", "transform", "score", "shortlist")
 
 
 def max_nodes(k, depth):
     """rgbid_bow_max_nodes: the nodes a full tree has; RgbidError outside the limits.  Needs no device."""
-    L = _lib.lib()
-    L.rgbid_bow_max_nodes.argtypes = [C.c_int, C.c_int, C.c_void_p]
     n = C.c_int32(0)
-    check(L.rgbid_bow_max_nodes(int(k), int(depth), C.byref(n)))
+    check(_lib.bind(SIGNATURES).rgbid_bow_max_nodes(int(k), int(depth), C.byref(n)))
     return int(n.value)
 
 
@@ -51,36 +61,18 @@ class Bow:
 
 class Vocabulary(_lib.CtxHandle):
     """A vocabulary tree of branching factor k and depth `depth` on the context's stream; untrained it is the root alone."""
-    _destroy = "rgbid_bow_destroy"
+    _destroy, _signatures, _timing, _stages = "rgbid_bow_destroy", SIGNATURES, "rgbid_bow_timing", STAGES
 
     def __init__(self, ctx, k=10, depth=4):
         super().__init__(ctx)
         self.k, self.depth = int(k), int(depth)
-        L = self.L
-        vp, ci = C.c_void_p, C.c_int
-        L.rgbid_bow_create.argtypes = [vp, vp, ci, ci]
-        L.rgbid_bow_destroy.argtypes = [vp]
-        L.rgbid_bow_train.argtypes = [vp, vp, vp, ci, ci, ci]
-        L.rgbid_bow_set_weights.argtypes = [vp, vp, vp, ci, ci]
-        L.rgbid_bow_export.argtypes = [vp, vp, vp, vp, vp]
-        L.rgbid_bow_import.argtypes = [vp, C.c_int32, vp, vp, vp]
-        L.rgbid_bow_transform.argtypes = [vp, vp, vp, ci, ci, vp, vp, vp]
-        L.rgbid_bow_score.argtypes = [vp, vp, vp, ci, ci, vp, ci, vp]
-        L.rgbid_bow_shortlist.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp, vp]
-        L.rgbid_bow_timing.argtypes = [vp, ci, vp]
-        self._created(L.rgbid_bow_create(C.byref(self._h), ctx._h, self.k, self.depth))
-        self.dev = f"cuda:{ctx.device}"
+        self._created(self.L.rgbid_bow_create(C.byref(self._h), ctx._h, self.k, self.depth))
+        self.dev = self._dev
 
     @staticmethod
     def _feat_args(feats):
         n = len(feats)
         return (feats.kps.data_ptr() if n else None, feats.counts.data_ptr() if n else None, n, int(feats.kps.shape[1]))
-
-    def timing(self, enable=True):
-        """record HIP events around the stages of the following calls; -> the device ms of the last ones {stage: ms}"""
-        ms = (C.c_float * 4)()
-        check(self.L.rgbid_bow_timing(self._h, int(enable), ms))
-        return dict(zip(STAGES, ms[:]))
 
     def train(self, feats, iters=10):
         """train on the descriptors of `feats` (loopfeat.Features) in (keyframe, slot) order and set the weights from them.  Synchronises."""

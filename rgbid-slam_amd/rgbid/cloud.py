@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import check
+from ._lib import check, ci, u64, vp
 
 ALL, NOVEL_ONLY = 0, 1
 FLAG_NOVEL = 1
@@ -22,7 +22,14 @@ POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"),
                         ("r", "u1"), ("g", "u1"), ("b", "u1"), ("flags", "u1")])
 assert POINT_DTYPE.itemsize == 32
 
-EXPORTS = ["rgbid_cloud_create", "rgbid_cloud_destroy", "rgbid_cloud_kinv", "rgbid_cloud_plan", "rgbid_cloud_emit"]
+SIGNATURES = {
+    "rgbid_cloud_create": (vp, vp, ci, ci, ci),
+    "rgbid_cloud_destroy": (vp,),
+    "rgbid_cloud_kinv": (vp, vp),
+    "rgbid_cloud_plan": (vp, ci, vp, vp, ci, vp),
+    "rgbid_cloud_emit": (vp, vp, u64),
+}
+EXPORTS = list(SIGNATURES)
 
 
 class Source(C.Structure):
@@ -39,7 +46,7 @@ def kinv(K):
     """The inverse of K = [fx 0 cx; 0 fy cy; 0 0 1] the library uses (Eigen's cofactor form on the float K widened to double), [3, 3]."""
     k = (C.c_float * 4)(*[float(v) for v in K])
     out = (C.c_double * 9)()
-    check(_lib.lib().rgbid_cloud_kinv(k, out))
+    check(_lib.bind(SIGNATURES).rgbid_cloud_kinv(k, out))
     return np.array(out[:], np.float64).reshape(3, 3)
 
 
@@ -65,7 +72,7 @@ def as_numpy(points):
 
 class Cloud(_lib.CtxHandle):
     """Point-cloud builder for keyframes of rows x cols pixels, up to max_keyframes per build, on the context's stream."""
-    _destroy = "rgbid_cloud_destroy"
+    _destroy, _signatures = "rgbid_cloud_destroy", SIGNATURES
 
     def __init__(self, ctx, rows, cols, max_keyframes):
         super().__init__(ctx)
@@ -84,14 +91,13 @@ class Cloud(_lib.CtxHandle):
     def emit(self, out):
         """write the points of the last plan into `out` (CUDA uint8 tensor [>= M, 32]).  Asynchronous on the context's stream."""
         records_out(out)
-        self.L.rgbid_cloud_emit.argtypes = [C.c_void_p, C.c_void_p, C.c_ulonglong]
-        check(self.L.rgbid_cloud_emit(self._h, C.c_void_p(out.data_ptr() if out.numel() else 0), C.c_ulonglong(out.shape[0])))
+        check(self.L.rgbid_cloud_emit(self._h, self.ptr(out), C.c_ulonglong(out.shape[0])))
 
     def build(self, sources, K, mode="novel"):
         """-> (points: CUDA uint8 [M, 32] of rgbid_cloud_point records, offsets: uint64 [n + 1]); as_numpy(points) is the structured view.
         The source blocks must stay valid and unchanged until this returns (it synchronises)."""
         offsets = self.plan(sources, K, mode)
-        out = torch.empty((int(offsets[-1]), 32), dtype=torch.uint8, device=f"cuda:{self.ctx.device}")
+        out = torch.empty((int(offsets[-1]), 32), dtype=torch.uint8, device=self._dev)
         self.ctx.wait_torch_stream()   # the output is torch's allocation
         self.emit(out)
         self.ctx.sync()

@@ -13,8 +13,9 @@ import math
 import numpy as np
 import torch
 
+from . import _args as A
 from . import _lib
-from ._lib import check
+from ._lib import check, ci, u64, vp
 from .cloud import records, records_out
 from .render import Pose, depth_range, image_size, intrinsics, poses
 
@@ -23,8 +24,15 @@ MAX_VIEWS = 65535
 MAX_WINDOW = 2
 MAX_DIM = 1 << 20
 VIEW_CHUNK = 16                         # RGBID_CONSIST_VIEW_CHUNK: more views than this are counted in chunks of it
-EXPORTS = ["rgbid_consist_create", "rgbid_consist_destroy", "rgbid_consist_plan", "rgbid_consist_counts", "rgbid_consist_emit",
-           "rgbid_consist_timing"]
+SIGNATURES = {
+    "rgbid_consist_create": (vp, vp, u64, ci),
+    "rgbid_consist_destroy": (vp,),
+    "rgbid_consist_plan": (vp, vp, u64, ci, vp, vp, vp, ci, ci, vp, vp, vp),
+    "rgbid_consist_counts": (vp, vp),
+    "rgbid_consist_emit": (vp, vp, u64),
+    "rgbid_consist_timing": (vp, ci, vp),
+}
+EXPORTS = list(SIGNATURES)
 STAGES = ("count", "scan", "emit")
 
 
@@ -39,19 +47,9 @@ class Params(C.Structure):
                 ("min_support", C.c_uint), ("max_conflicts", C.c_uint)]
 
 
-def _integer(name, v):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-        raise ValueError(f"{name}: an integer, got {v!r}")
-    return int(v)
-
-
 def tolerances(tol_rel, tol_abs=0.0):
     """-> (tol_rel, tol_abs) as the float32 values the library receives: finite and >= 0 (ValueError otherwise)"""
-    try:
-        with np.errstate(over="ignore"):
-            r, a = float(np.float32(tol_rel)), float(np.float32(tol_abs))
-    except (TypeError, ValueError, OverflowError):
-        raise ValueError(f"tol_rel, tol_abs: numbers, got {tol_rel!r}, {tol_abs!r}")
+    r, a = (A.float32(x, f"tol_rel, tol_abs: numbers, got {tol_rel!r}, {tol_abs!r}") for x in (tol_rel, tol_abs))
     if not (math.isfinite(r) and math.isfinite(a) and r >= 0 and a >= 0):
         raise ValueError(f"tol_rel, tol_abs must be finite and >= 0, got {tol_rel!r}, {tol_abs!r}")
     return r, a
@@ -59,15 +57,12 @@ def tolerances(tol_rel, tol_abs=0.0):
 
 def window_arg(window):
     """-> the window half-width: an integer in 0 .. 2 (ValueError otherwise)"""
-    w = _integer("window", window)
-    if not 0 <= w <= MAX_WINDOW:
-        raise ValueError(f"window must lie in [0, {MAX_WINDOW}], got {window!r}")
-    return w
+    return A.integer_in("window", window, 0, MAX_WINDOW, f"[0, {MAX_WINDOW}]")
 
 
 def vote_args(min_support, max_conflicts):
     """-> (min_support, max_conflicts): integers in 0 .. 65 535 each (ValueError otherwise)"""
-    s, c = _integer("min_support", min_support), _integer("max_conflicts", max_conflicts)
+    s, c = A.integer("min_support", min_support), A.integer("max_conflicts", max_conflicts)
     if not (0 <= s <= MAX_VIEWS and 0 <= c <= MAX_VIEWS):
         raise ValueError(f"min_support and max_conflicts must lie in [0, {MAX_VIEWS}], got {min_support!r}, {max_conflicts!r}")
     return s, c
@@ -102,10 +97,7 @@ def planes_arg(planes, views, rows, cols, device=None):
     if len(planes) != views:
         raise ValueError(f"{views} views need {views} planes, got {len(planes)}")
     for p in planes:
-        if not (isinstance(p, torch.Tensor) and p.is_cuda and p.dtype == torch.float32 and tuple(p.shape) == (rows, cols) and p.is_contiguous()):
-            raise ValueError(f"planes: contiguous CUDA float32 tensors [{rows}, {cols}]")
-        if device is not None and p.device.index != device:
-            raise ValueError(f"planes must live on device {device}")
+        A.cuda_tensor("planes", p, torch.float32, (rows, cols), f"planes: contiguous CUDA float32 tensors [{rows}, {cols}]", device)
     return planes
 
 
@@ -135,19 +127,12 @@ class Plan:
 
 class ConsistencyFilter(_lib.CtxHandle):
     """Consistency filter for up to max_points records and max_views views per plan, on the context's stream."""
-    _destroy = "rgbid_consist_destroy"
+    _destroy, _signatures, _timing, _stages = "rgbid_consist_destroy", SIGNATURES, "rgbid_consist_timing", STAGES
 
     def __init__(self, ctx, max_points, max_views):
         super().__init__(ctx)
         self.max_points, self.max_views = int(max_points), int(max_views)
-        L = self.L
-        L.rgbid_consist_create.argtypes = [C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_int]
-        L.rgbid_consist_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                         C.c_void_p, C.c_void_p, C.c_void_p]
-        L.rgbid_consist_counts.argtypes = [C.c_void_p, C.c_void_p]
-        L.rgbid_consist_emit.argtypes = [C.c_void_p, C.c_void_p, C.c_ulonglong]
-        L.rgbid_consist_timing.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        self._created(L.rgbid_consist_create(C.byref(self._h), ctx._h, C.c_ulonglong(self.max_points), self.max_views))
+        self._created(self.L.rgbid_consist_create(C.byref(self._h), ctx._h, C.c_ulonglong(self.max_points), self.max_views))
 
     def plan(self, points, offsets, planes, R, t, K, rows, cols, tol_rel=0.02, tol_abs=0.0, window=1, min_support=0, max_conflicts=0,
              z_min=0.05, z_max=20.0):
@@ -171,7 +156,7 @@ class ConsistencyFilter(_lib.CtxHandle):
         views = (View * V)(*[View(Pose((C.c_double * 9)(*R[v].reshape(9)), (C.c_double * 3)(*t[v])), planes[v].data_ptr()) for v in range(V)])
         stats = np.zeros(4, np.uint64); kept = C.c_ulonglong()
         self.ctx.wait_torch_stream()
-        check(self.L.rgbid_consist_plan(self._h, C.c_void_p(points.data_ptr() if n else 0), C.c_ulonglong(n), V, views,
+        check(self.L.rgbid_consist_plan(self._h, self.ptr(points), C.c_ulonglong(n), V, views,
                                         off.ctypes.data_as(C.c_void_p) if off is not None else None, k, rows, cols, C.byref(prm),
                                         stats.ctypes.data_as(C.c_void_p), C.byref(kept)))
         return Plan(kept.value, n, V, stats)
@@ -180,18 +165,12 @@ class ConsistencyFilter(_lib.CtxHandle):
         """write support | conflicts << 16 of the last plan's records, in input order, into `out` (CUDA int32 / uint32 tensor [>= n]).
         Asynchronous on the context's stream."""
         assert out.is_cuda and out.element_size() == 4 and not out.is_floating_point() and out.is_contiguous() and out.dim() == 1
-        check(self.L.rgbid_consist_counts(self._h, C.c_void_p(out.data_ptr() if out.numel() else 0)))
+        check(self.L.rgbid_consist_counts(self._h, self.ptr(out)))
 
     def emit(self, out):
         """write the kept records of the last plan into `out` (CUDA uint8 tensor [>= kept, 32]).  Asynchronous on the context's stream."""
         records_out(out)
-        check(self.L.rgbid_consist_emit(self._h, C.c_void_p(out.data_ptr() if out.numel() else 0), C.c_ulonglong(out.shape[0])))
-
-    def timing(self, enable=True):
-        """record HIP events around the stages of the following plans / emits; -> the device ms of the last ones {stage: ms}"""
-        ms = (C.c_float * 3)()
-        check(self.L.rgbid_consist_timing(self._h, int(enable), ms))
-        return dict(zip(STAGES, ms[:]))
+        check(self.L.rgbid_consist_emit(self._h, self.ptr(out), C.c_ulonglong(out.shape[0])))
 
     def filter(self, points, offsets, planes, R, t, K, rows, cols, tol_rel=0.02, tol_abs=0.0, window=1, min_support=0, max_conflicts=0,
                z_min=0.05, z_max=20.0, return_counts=False, return_offsets=False, return_plan=False):
@@ -203,9 +182,8 @@ class ConsistencyFilter(_lib.CtxHandle):
         if return_offsets and offsets is None:
             raise ValueError("return_offsets needs offsets")
         p = self.plan(points, offsets, planes, R, t, K, rows, cols, tol_rel, tol_abs, window, min_support, max_conflicts, z_min, z_max)
-        dev = f"cuda:{self.ctx.device}"
-        out = torch.empty((p.kept, 32), dtype=torch.uint8, device=dev)
-        cnt = torch.empty((p.n,), dtype=torch.int32, device=dev) if return_counts or return_offsets else None
+        out = torch.empty((p.kept, 32), dtype=torch.uint8, device=self._dev)
+        cnt = torch.empty((p.n,), dtype=torch.int32, device=self._dev) if return_counts or return_offsets else None
         self.ctx.wait_torch_stream()   # the outputs are torch's allocations
         if cnt is not None:
             self.counts(cnt)

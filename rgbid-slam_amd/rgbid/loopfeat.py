@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import check
+from ._lib import check, ci, f32, f64, vp
 
 KP_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("response", "<f4"), ("direction", "<i4"), ("desc", "u1", (32,)), ("X", "<f8", (3,)),
                      ("cov", "<f8", (6,))])
@@ -27,10 +27,24 @@ assert MATCH_DTYPE.itemsize == 16
 
 CELL, CELL_MAX, BORDER, DIRECTIONS, TESTS = 32, 64, 16, 32, 256
 MAX_KEYPOINTS, MAX_ITERS, MAX_LEVELS = 1536, 4096, 8
-EXPORTS = ["rgbid_loopfeat_create", "rgbid_loopfeat_destroy", "rgbid_loopfeat_tables", "rgbid_loopfeat_layout", "rgbid_loopfeat_extract",
-           "rgbid_loopfeat_match", "rgbid_loopfeat_ransac", "rgbid_loopfeat_timing", "rgbid_loopfeat_create_levels",
-           "rgbid_loopfeat_plan_levels", "rgbid_loopfeat_resize_table", "rgbid_loopfeat_level_layout", "rgbid_loopfeat_extract_levels",
-           "rgbid_loopfeat_pyramid", "rgbid_loopfeat_timing_pyramid"]
+SIGNATURES = {
+    "rgbid_loopfeat_create": (vp, vp, ci, ci, ci),
+    "rgbid_loopfeat_create_levels": (vp, vp, ci, ci, ci, ci, f32),
+    "rgbid_loopfeat_destroy": (vp,),
+    "rgbid_loopfeat_plan_levels": (ci, ci, ci, ci, f32, vp, vp, vp),
+    "rgbid_loopfeat_resize_table": (ci, ci, vp, vp),
+    "rgbid_loopfeat_tables": (vp, vp, vp),
+    "rgbid_loopfeat_layout": (vp, vp, vp, vp),
+    "rgbid_loopfeat_level_layout": (vp, ci, vp, vp, vp, vp, vp, vp),
+    "rgbid_loopfeat_extract": (vp, vp, vp, ci, vp, vp, vp),
+    "rgbid_loopfeat_extract_levels": (vp, vp, vp, ci, vp, vp, vp, vp),
+    "rgbid_loopfeat_pyramid": (vp, vp, ci, ci, vp),
+    "rgbid_loopfeat_match": (vp, vp, vp, ci, vp, ci, f32, vp, vp),
+    "rgbid_loopfeat_ransac": (vp, vp, ci, vp, ci, vp, vp, vp, ci, f64, vp, vp, vp),
+    "rgbid_loopfeat_timing": (vp, ci, vp),
+    "rgbid_loopfeat_timing_pyramid": (vp, vp),
+}
+EXPORTS = list(SIGNATURES)
 STAGES = ("response", "select", "describe", "match", "ransac")
 LEVELS, SCALE = 8, 1.2         # the reference's FEATURE_EXTRACTOR LEVELS and SCALE; the default here is one level
 
@@ -67,10 +81,9 @@ def mt19937_words(rs, n):
 
 def tables():
     """the library's host tables -> (pattern int8 [256, 4], rotated int8 [32, 256, 4], bounds float64 [16, 2])"""
-    L = _lib.lib()
+    L = _lib.bind(SIGNATURES)
     pat = np.zeros((TESTS, 4), np.int8); rot = np.zeros((DIRECTIONS, TESTS, 4), np.int8); bnd = np.zeros((16, 2), np.float64)
     p = lambda a: a.ctypes.data_as(C.c_void_p)
-    L.rgbid_loopfeat_tables.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     check(L.rgbid_loopfeat_tables(p(pat), p(rot), p(bnd)))
     return pat, rot, bnd
 
@@ -123,8 +136,7 @@ def layout_levels(rows, cols, max_keypoints, levels=1, scale=SCALE):
 
 def plan_levels(rows, cols, max_keypoints, levels=1, scale=SCALE):
     """rgbid_loopfeat_plan_levels: the library's own answer to layout_levels, the same tuples; RgbidError for its refusals.  Needs no device."""
-    L = _lib.lib()
-    L.rgbid_loopfeat_plan_levels.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+    L = _lib.bind(SIGNATURES)
     n = C.c_int32(0)
     geo = np.zeros((MAX_LEVELS, 5), np.int32); s = np.zeros(MAX_LEVELS, np.float32)
     check(L.rgbid_loopfeat_plan_levels(int(rows), int(cols), int(max_keypoints), int(levels), C.c_float(float(scale)), C.byref(n),
@@ -134,8 +146,7 @@ def plan_levels(rows, cols, max_keypoints, levels=1, scale=SCALE):
 
 def resize_table(src, dst):
     """rgbid_loopfeat_resize_table -> (x0 int32 [dst], w1 int32 [dst]) of one axis.  Needs no device."""
-    L = _lib.lib()
-    L.rgbid_loopfeat_resize_table.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L = _lib.bind(SIGNATURES)
     x0 = np.zeros(max(int(dst), 0), np.int32); w1 = np.zeros(max(int(dst), 0), np.int32)
     check(L.rgbid_loopfeat_resize_table(int(src), int(dst), x0.ctypes.data_as(C.c_void_p), w1.ctypes.data_as(C.c_void_p)))
     return x0, w1
@@ -166,7 +177,7 @@ class LoopFeat(_lib.CtxHandle):
     """Feature extractor, matcher and RANSAC for keyframes of rows x cols pixels, on the context's stream.  levels > 1: features over a
     pyramid of that many images at `scale` between neighbours (self.levels lists those that exist), so that a revisit at another distance
     still matches; levels = 1 is the single-level extractor."""
-    _destroy = "rgbid_loopfeat_destroy"
+    _destroy, _signatures, _timing, _stages = "rgbid_loopfeat_destroy", SIGNATURES, "rgbid_loopfeat_timing", STAGES
 
     def __init__(self, ctx, rows, cols, max_keypoints=1000, levels=1, scale=SCALE):
         super().__init__(ctx)
@@ -176,36 +187,17 @@ class LoopFeat(_lib.CtxHandle):
         self.levels = layout_levels(rows, cols, max_keypoints, levels, scale)
         _, _, self.cells_x, self.cells_y, self.per_cell, _ = self.levels[0]
         self.scale = float(np.float32(scale))
-        L = self.L
-        vp, ci = C.c_void_p, C.c_int
-        L.rgbid_loopfeat_create_levels.argtypes = [vp, vp, ci, ci, ci, ci, C.c_float]
-        L.rgbid_loopfeat_destroy.argtypes = [vp]
-        L.rgbid_loopfeat_extract_levels.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp]
-        L.rgbid_loopfeat_pyramid.argtypes = [vp, vp, ci, ci, vp]
-        L.rgbid_loopfeat_level_layout.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp]
-        L.rgbid_loopfeat_timing_pyramid.argtypes = [vp, vp]
-        L.rgbid_loopfeat_match.argtypes = [vp, vp, vp, ci, vp, ci, C.c_float, vp, vp]
-        L.rgbid_loopfeat_ransac.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, ci, C.c_double, vp, vp, vp]
-        L.rgbid_loopfeat_timing.argtypes = [vp, ci, vp]
-        self._created(L.rgbid_loopfeat_create_levels(C.byref(self._h), ctx._h, self.rows, self.cols, self.max_keypoints, int(levels),
-                                                     C.c_float(self.scale)))
-        self.dev = f"cuda:{ctx.device}"
+        self._created(self.L.rgbid_loopfeat_create_levels(C.byref(self._h), ctx._h, self.rows, self.cols, self.max_keypoints, int(levels),
+                                                          C.c_float(self.scale)))
+        self.dev = self._dev
 
-    def _dev(self, a, dtype):
+    def _on_device(self, a, dtype):
         t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
         return t.to(device=self.dev, dtype=dtype).contiguous()
 
-    def timing(self, enable=True):
-        """record HIP events around the stages of the following calls; -> the device ms of the last ones {stage: ms}"""
-        ms = (C.c_float * 5)()
-        check(self.L.rgbid_loopfeat_timing(self._h, int(enable), ms))
-        return dict(zip(STAGES, ms[:]))
-
     def timing_pyramid(self):
         """the device ms the last timed extract spent on its pyramid (0.0 with one level)"""
-        ms = C.c_float(0.0)
-        check(self.L.rgbid_loopfeat_timing_pyramid(self._h, C.byref(ms)))
-        return float(ms.value)
+        return self._stage_ms("rgbid_loopfeat_timing_pyramid", ("pyramid",))["pyramid"]
 
     def level_layout(self, level):
         """rgbid_loopfeat_level_layout -> (rows_l, cols_l, cells_x, cells_y, per_cell, s_l) as the library holds it"""
@@ -216,7 +208,7 @@ class LoopFeat(_lib.CtxHandle):
 
     def pyramid(self, grey, level):
         """level `level` of the pyramid of grey [n, rows, cols] uint8 -> [n, rows_l, cols_l] uint8 on the device.  Synchronises."""
-        g = self._dev(grey, torch.uint8)
+        g = self._on_device(grey, torch.uint8)
         assert g.dim() == 3 and tuple(g.shape[1:]) == (self.rows, self.cols), g.shape
         if not 0 <= int(level) < len(self.levels):
             raise ValueError(f"level {level} does not exist (levels 0 .. {len(self.levels) - 1})")
@@ -230,7 +222,7 @@ class LoopFeat(_lib.CtxHandle):
     def extract(self, grey, invdepth, K, aux=False):
         """grey [n, rows, cols] uint8 and invdepth [n, rows, cols] float32 (numpy or tensors), K = (fx, fy, cx, cy) -> Features (with the
         16-byte aux records when aux is set).  Synchronises."""
-        g, w = self._dev(grey, torch.uint8), self._dev(invdepth, torch.float32)
+        g, w = self._on_device(grey, torch.uint8), self._on_device(invdepth, torch.float32)
         assert g.dim() == 3 and tuple(g.shape[1:]) == (self.rows, self.cols) and g.shape == w.shape, (g.shape, w.shape)
         n = int(g.shape[0])
         kps = torch.empty((n, self.max_keypoints, 120), dtype=torch.uint8, device=self.dev)
@@ -246,7 +238,7 @@ class LoopFeat(_lib.CtxHandle):
 
     def _pairs(self, pairs):
         p = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
-        return p, self._dev(p, torch.int32)
+        return p, self._on_device(p, torch.int32)
 
     def match(self, feats, pairs, ratio=MATCH_RATIO, lists=True):
         """pairs [(query, candidate)] keyframe indices -> (matches [P, max_keypoints, 16] uint8 on the device (None without lists), counts [P]
@@ -272,7 +264,7 @@ class LoopFeat(_lib.CtxHandle):
             u = uniform_draws(iters, seed)
         u = np.ascontiguousarray(u, np.float64)
         iters = len(u) // 3
-        ud = self._dev(u, torch.float64)
+        ud = self._on_device(u, torch.float64)
         pose = torch.zeros((P, 12), dtype=torch.float64, device=self.dev)
         res = torch.zeros((P, 2), dtype=torch.int32, device=self.dev)
         mask = torch.zeros((P, self.max_keypoints), dtype=torch.uint8, device=self.dev)

@@ -10,49 +10,38 @@ import ctypes as C
 import numpy as np
 import torch
 
+from . import _args as A
 from . import _lib
-from ._lib import check
+from ._lib import check, ci, cu, u64, vp
 
 MAX_VERTICES = 1 << 31
 MAX_TRIANGLES = 1 << 31
-EXPORTS = ["rgbid_mesh_create", "rgbid_mesh_destroy", "rgbid_mesh_label", "rgbid_mesh_components", "rgbid_mesh_select", "rgbid_mesh_emit",
-           "rgbid_mesh_timing"]
+SIGNATURES = {
+    "rgbid_mesh_create": (vp, vp, u64, u64),
+    "rgbid_mesh_destroy": (vp,),
+    "rgbid_mesh_label": (vp, u64, u64, vp, vp),
+    "rgbid_mesh_components": (vp, vp, vp),
+    "rgbid_mesh_select": (vp, cu, vp, vp, vp, vp),
+    "rgbid_mesh_emit": (vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, u64),
+    "rgbid_mesh_timing": (vp, ci, vp),
+}
+EXPORTS = list(SIGNATURES)
 STAGES = ("label", "select", "emit")
-
-
-def _integer(name, v):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-        raise ValueError(f"{name}: an integer, got {v!r}")
-    return int(v)
 
 
 def capacity_arg(max_vertices, max_triangles):
     """-> (max_vertices, max_triangles) of a handle: each 1 .. 2^31 (ValueError otherwise)"""
-    v, t = _integer("max_vertices", max_vertices), _integer("max_triangles", max_triangles)
-    if not 1 <= v <= MAX_VERTICES:
-        raise ValueError(f"max_vertices must lie in [1, 2^31], got {max_vertices!r}")
-    if not 1 <= t <= MAX_TRIANGLES:
-        raise ValueError(f"max_triangles must lie in [1, 2^31], got {max_triangles!r}")
-    return v, t
-
-
-def _rows3(name, x, dtype_ok, what, rows=None, device=None):
-    if not (isinstance(x, torch.Tensor) and x.is_cuda and dtype_ok(x) and x.dim() == 2 and x.shape[1] == 3 and x.is_contiguous()):
-        raise ValueError(f"{name}: a contiguous CUDA {what} tensor [n, 3]")
-    if rows is not None and x.shape[0] != rows:
-        raise ValueError(f"{name}: {rows} rows, one per vertex, got {x.shape[0]}")
-    if device is not None and x.device.index != device:
-        raise ValueError(f"{name} must live on device {device}")
-    return x
+    v, t = A.integer("max_vertices", max_vertices), A.integer("max_triangles", max_triangles)
+    A.in_range("max_vertices", v, 1, MAX_VERTICES, "[1, 2^31]", max_vertices)
+    return v, A.in_range("max_triangles", t, 1, MAX_TRIANGLES, "[1, 2^31]", max_triangles)
 
 
 def mesh_arg(triangles, n_vertices, max_vertices=MAX_VERTICES, max_triangles=MAX_TRIANGLES, device=None):
     """-> (triangles, n_vertices): a contiguous CUDA tensor [n_t, 3] of 4-byte integers (int32 holding the uint32 indices, as Volume.extract
     returns them) with n_t <= max_triangles, and 0 <= n_vertices <= max_vertices, not 0 when there are triangles (ValueError otherwise)"""
-    n_v = _integer("n_vertices", n_vertices)
-    _rows3("triangles", triangles, lambda x: x.element_size() == 4 and not x.is_floating_point(), "int32", device=device)
-    if not 0 <= n_v <= max_vertices:
-        raise ValueError(f"n_vertices must lie in [0, {max_vertices}], got {n_vertices!r}")
+    n_v = A.integer("n_vertices", n_vertices)
+    A.rows3("triangles", triangles, A.int4, device=device)
+    A.in_range("n_vertices", n_v, 0, max_vertices, f"[0, {max_vertices}]", n_vertices)
     if triangles.shape[0] > max_triangles:
         raise ValueError(f"{triangles.shape[0]} triangles are more than {max_triangles}")
     if triangles.shape[0] and n_v == 0:
@@ -62,17 +51,14 @@ def mesh_arg(triangles, n_vertices, max_vertices=MAX_VERTICES, max_triangles=MAX
 
 def min_triangles_arg(min_triangles):
     """-> min_triangles: an integer in 0 .. 2^32 - 1 (ValueError otherwise)"""
-    n = _integer("min_triangles", min_triangles)
-    if not 0 <= n < 1 << 32:
-        raise ValueError(f"min_triangles must lie in [0, 2^32 - 1], got {min_triangles!r}")
-    return n
+    return A.integer_in("min_triangles", min_triangles, 0, (1 << 32) - 1, "[0, 2^32 - 1]")
 
 
 def largest_arg(largest):
     """-> largest: None or an integer >= 1, the number of components to keep (ValueError otherwise)"""
     if largest is None:
         return None
-    k = _integer("largest", largest)
+    k = A.integer("largest", largest)
     if k < 1:
         raise ValueError(f"largest must be at least 1, got {largest!r}")
     return k
@@ -82,12 +68,7 @@ def keep_arg(keep, components, device=None):
     """-> keep: None or a contiguous CUDA uint8 tensor [components] (ValueError otherwise)"""
     if keep is None:
         return None
-    if not (isinstance(keep, torch.Tensor) and keep.is_cuda and keep.dtype == torch.uint8 and keep.dim() == 1 and keep.is_contiguous()
-            and keep.shape[0] == components):
-        raise ValueError(f"keep: a contiguous CUDA uint8 tensor [{components}], one byte per component")
-    if device is not None and keep.device.index != device:
-        raise ValueError(f"keep must live on device {device}")
-    return keep
+    return A.cuda_tensor("keep", keep, torch.uint8, (components,), f"keep: a contiguous CUDA uint8 tensor [{components}], one byte per component", device)
 
 
 def largest_mask(table, k):
@@ -106,7 +87,7 @@ def largest_mask(table, k):
 
 class Components(_lib.CtxHandle):
     """The components of meshes of up to max_vertices vertices and max_triangles triangles, on the context's stream."""
-    _destroy = "rgbid_mesh_destroy"
+    _destroy, _signatures, _timing, _stages = "rgbid_mesh_destroy", SIGNATURES, "rgbid_mesh_timing", STAGES
 
     def __init__(self, ctx, max_vertices, max_triangles):
         self.max_vertices, self.max_triangles = capacity_arg(max_vertices, max_triangles)
@@ -114,18 +95,7 @@ class Components(_lib.CtxHandle):
         self._triangles = None                 # the labelled mesh: emit reads it again
         self.n_vertices = self.components = 0
         self.kept = None
-        L = self.L
-        L.rgbid_mesh_create.argtypes = [C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_ulonglong]
-        L.rgbid_mesh_label.argtypes = [C.c_void_p, C.c_ulonglong, C.c_ulonglong, C.c_void_p, C.c_void_p]
-        L.rgbid_mesh_components.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.rgbid_mesh_select.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.rgbid_mesh_emit.argtypes = [C.c_void_p] + [C.c_void_p] * 8 + [C.c_ulonglong, C.c_ulonglong]
-        L.rgbid_mesh_timing.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        self._created(L.rgbid_mesh_create(C.byref(self._h), ctx._h, C.c_ulonglong(self.max_vertices), C.c_ulonglong(self.max_triangles)))
-
-    @property
-    def _dev(self):
-        return f"cuda:{self.ctx.device}"
+        self._created(self.L.rgbid_mesh_create(C.byref(self._h), ctx._h, C.c_ulonglong(self.max_vertices), C.c_ulonglong(self.max_triangles)))
 
     def label(self, triangles, n_vertices, tables=True):
         """the components of the mesh `triangles` (CUDA [n_t, 3], 4-byte integers) over n_vertices vertices -> dict(components, table int32
@@ -135,16 +105,14 @@ class Components(_lib.CtxHandle):
         self._triangles, self.kept = None, None
         n_c = C.c_ulonglong()
         self.ctx.wait_torch_stream()
-        check(self.L.rgbid_mesh_label(self._h, C.c_ulonglong(n_v), C.c_ulonglong(triangles.shape[0]),
-                                      C.c_void_p(triangles.data_ptr() if triangles.numel() else 0), C.byref(n_c)))
+        check(self.L.rgbid_mesh_label(self._h, C.c_ulonglong(n_v), C.c_ulonglong(triangles.shape[0]), self.ptr(triangles), C.byref(n_c)))
         self._triangles, self.n_vertices, self.components = triangles, n_v, int(n_c.value)
         out = dict(components=self.components)
         if tables:
             table = torch.empty((self.components, 3), dtype=torch.int32, device=self._dev)
             labels = torch.empty((n_v,), dtype=torch.int32, device=self._dev)
             self.ctx.wait_torch_stream()   # the outputs are torch's allocations
-            check(self.L.rgbid_mesh_components(self._h, C.c_void_p(table.data_ptr() if table.numel() else 0),
-                                               C.c_void_p(labels.data_ptr() if labels.numel() else 0)))
+            check(self.L.rgbid_mesh_components(self._h, self.ptr(table), self.ptr(labels)))
             self.ctx.sync()
             out.update(table=table, labels=labels)
         return out
@@ -159,14 +127,13 @@ class Components(_lib.CtxHandle):
         kc, kv, kt = C.c_ulonglong(), C.c_ulonglong(), C.c_ulonglong()
         self.kept = None
         self.ctx.wait_torch_stream()
-        check(self.L.rgbid_mesh_select(self._h, n, C.c_void_p(keep.data_ptr() if keep is not None and keep.numel() else 0), C.byref(kc), C.byref(kv),
-                                       C.byref(kt)))
+        check(self.L.rgbid_mesh_select(self._h, n, self.opt_ptr(keep), C.byref(kc), C.byref(kv), C.byref(kt)))
         self.kept = dict(components=int(kc.value), vertices=int(kv.value), triangles=int(kt.value))
         return dict(self.kept)
 
     def emit_into(self, vertices, colours, normals, vertices_out, colours_out, normals_out, old_index_out, triangles_out):
         """the raw call: the last selection written asynchronously on the context's stream into the given CUDA tensors (or None)"""
-        ptr = lambda x: C.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
+        ptr = self.opt_ptr
         check(self.L.rgbid_mesh_emit(self._h, ptr(vertices), ptr(colours), ptr(normals), ptr(vertices_out), ptr(colours_out), ptr(normals_out),
                                      ptr(old_index_out), ptr(triangles_out), C.c_ulonglong(vertices_out.shape[0]), C.c_ulonglong(triangles_out.shape[0])))
 
@@ -178,11 +145,11 @@ class Components(_lib.CtxHandle):
         if self._triangles is None or self.kept is None:
             raise ValueError("emit: nothing is selected")
         dev, n = self.ctx.device, self.n_vertices
-        _rows3("vertices", vertices, lambda x: x.dtype == torch.float32, "float32", n, dev)
+        A.rows3("vertices", vertices, torch.float32, n, dev)
         if colours is not None:
-            _rows3("colours", colours, lambda x: x.dtype == torch.uint8, "uint8", n, dev)
+            A.rows3("colours", colours, torch.uint8, n, dev)
         if normals is not None:
-            _rows3("normals", normals, lambda x: x.dtype == torch.float32, "float32", n, dev)
+            A.rows3("normals", normals, torch.float32, n, dev)
         kv, kt = self.kept["vertices"], self.kept["triangles"]
         new = lambda like, rows: None if like is None else torch.empty((rows, 3), dtype=like.dtype, device=self._dev)
         out = dict(vertices=new(vertices, kv), colours=new(colours, kv), normals=new(normals, kv),
@@ -193,12 +160,6 @@ class Components(_lib.CtxHandle):
         self.ctx.sync()
         return out
 
-    def timing(self, enable=True):
-        """record HIP events around the stages of the following calls; -> the device ms of the last ones {stage: ms}"""
-        ms = (C.c_float * 3)()
-        check(self.L.rgbid_mesh_timing(self._h, int(enable), ms))
-        return dict(zip(STAGES, ms[:]))
-
 
 def filter_components(ctx, vertices, colours, triangles, normals=None, min_triangles=1, largest=None):
     """one-shot: the mesh (vertices float32 [n, 3], colours uint8 [n, 3] or None, triangles [n_t, 3], normals float32 [n, 3] or None, CUDA
@@ -207,7 +168,7 @@ def filter_components(ctx, vertices, colours, triangles, normals=None, min_trian
     dict(components, vertices, triangles, kept_components, kept_vertices, kept_triangles)."""
     n = min_triangles_arg(min_triangles)
     k = largest_arg(largest)
-    _rows3("vertices", vertices, lambda x: x.dtype == torch.float32, "float32")
+    A.rows3("vertices", vertices, torch.float32)
     triangles, n_v = mesh_arg(triangles, vertices.shape[0])
     cc = Components(ctx, max(n_v, 1), max(triangles.shape[0], 1))
     try:

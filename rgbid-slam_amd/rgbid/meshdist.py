@@ -5,14 +5,14 @@
 to a brute force over all triangles.  `summary` turns the distances into the figures a surface evaluation reports,
 `mesh_deviation` measures two meshes against each other and `cloud_deviation` a keyframe cloud against a mesh."""
 import ctypes as C
-import math
 
 import numpy as np
 import torch
 
+from . import _args as A
 from . import _lib
 from . import mesh as MS
-from ._lib import check
+from ._lib import check, ci, f32, u64, vp
 
 MAX_VERTICES = 1 << 31
 MAX_TRIANGLES = 1 << 31
@@ -23,8 +23,16 @@ NO_REGION = 255                          # RGBID_MESHDIST_NO_REGION
 MAX_CELL = 1 << 18                       # RGBID_MESHDIST_MAX_CELL
 CELL_FACTOR = np.float32(1.0625)         # RGBID_MESHDIST_CELL_FACTOR: smallest cell size / d_max
 MIN_DISTANCE, MAX_DISTANCE = 2.0 ** -60, 2.0 ** 60
-MESHDIST_EXPORTS = ["rgbid_meshdist_create", "rgbid_meshdist_destroy", "rgbid_meshdist_plan", "rgbid_meshdist_query",
-                    "rgbid_meshdist_query_records", "rgbid_meshdist_set_query_sort", "rgbid_meshdist_timing"]
+SIGNATURES = {
+    "rgbid_meshdist_create": (vp, vp, u64, u64, u64, u64),
+    "rgbid_meshdist_destroy": (vp,),
+    "rgbid_meshdist_plan": (vp, u64, vp, u64, vp, f32, f32, vp, vp),
+    "rgbid_meshdist_query": (vp, u64, vp, vp, vp, vp, vp, vp),
+    "rgbid_meshdist_query_records": (vp, u64, vp, vp, vp, vp, vp, vp),
+    "rgbid_meshdist_set_query_sort": (vp, ci),
+    "rgbid_meshdist_timing": (vp, ci, vp),
+}
+MESHDIST_EXPORTS = EXPORTS = list(SIGNATURES)
 STAGES = ("box", "pairs", "sort", "cells", "query")
 STATS = ("participating", "pairs", "cells", "longest_run")
 OUTPUTS = ("triangle", "distance", "closest", "region", "candidates")
@@ -34,28 +42,14 @@ REGIONS = ("A", "B", "C", "AB", "AC", "BC", "face")
 def capacity_arg(max_vertices, max_triangles, max_pairs, max_queries):
     """-> the four capacities of a handle: each an integer in 1 .. 2^31 (ValueError otherwise)"""
     v, t = MS.capacity_arg(max_vertices, max_triangles)
-    p, q = MS._integer("max_pairs", max_pairs), MS._integer("max_queries", max_queries)
-    if not 1 <= p <= MAX_PAIRS:
-        raise ValueError(f"max_pairs must lie in [1, 2^31], got {max_pairs!r}")
-    if not 1 <= q <= MAX_QUERIES:
-        raise ValueError(f"max_queries must lie in [1, 2^31], got {max_queries!r}")
-    return v, t, p, q
+    p, q = A.integer("max_pairs", max_pairs), A.integer("max_queries", max_queries)
+    return v, t, A.in_range("max_pairs", p, 1, MAX_PAIRS, "[1, 2^31]", max_pairs), A.in_range("max_queries", q, 1, MAX_QUERIES, "[1, 2^31]", max_queries)
 
 
 def distance_arg(d_max):
     """-> d_max as the float32 value the library receives: finite, > 0 and in [2^-60, 2^60] (ValueError otherwise)"""
-    try:
-        if isinstance(d_max, (bool, str, bytes)):
-            raise TypeError
-        with np.errstate(over="ignore"):
-            d = float(np.float32(d_max))
-    except (TypeError, ValueError, OverflowError):
-        raise ValueError(f"d_max: a number of metres, got {d_max!r}") from None
-    if not (math.isfinite(d) and d > 0):
-        raise ValueError(f"d_max must be finite and > 0, got {d_max!r}")
-    if not MIN_DISTANCE <= d <= MAX_DISTANCE:
-        raise ValueError(f"d_max must lie in [2^-60, 2^60], got {d_max!r}")
-    return d
+    d = A.positive32("d_max", d_max, f"d_max: a number of metres, got {d_max!r}", (bool, str, bytes))
+    return A.in_range("d_max", d, MIN_DISTANCE, MAX_DISTANCE, "[2^-60, 2^60]", d_max)
 
 
 def cell_arg(cell, d_max):
@@ -64,15 +58,7 @@ def cell_arg(cell, d_max):
     least = float(np.float32(distance_arg(d_max)) * CELL_FACTOR)
     if cell is None:
         return least
-    try:
-        if isinstance(cell, (bool, str, bytes)):
-            raise TypeError
-        with np.errstate(over="ignore"):
-            c = float(np.float32(cell))
-    except (TypeError, ValueError, OverflowError):
-        raise ValueError(f"cell: a number of metres, got {cell!r}") from None
-    if not (math.isfinite(c) and c > 0):
-        raise ValueError(f"cell must be finite and > 0, got {cell!r}")
+    c = A.positive32("cell", cell, f"cell: a number of metres, got {cell!r}", (bool, str, bytes))
     if c < least:
         raise ValueError(f"cell must be at least 1.0625 d_max = {least!r}, got {cell!r}")
     if c > MAX_DISTANCE * float(CELL_FACTOR):
@@ -83,14 +69,14 @@ def cell_arg(cell, d_max):
 def mesh_arg(vertices, triangles, max_vertices=MAX_VERTICES, max_triangles=MAX_TRIANGLES, device=None):
     """-> (vertices, triangles): contiguous CUDA tensors float32 [n_v, 3] and 4-byte integers [n_t, 3] within the capacities, no triangles
     without vertices (ValueError otherwise)"""
-    MS._rows3("vertices", vertices, lambda x: x.dtype == torch.float32, "float32", device=device)
+    A.rows3("vertices", vertices, torch.float32, device=device)
     triangles, _ = MS.mesh_arg(triangles, vertices.shape[0], max_vertices, max_triangles, device)
     return vertices, triangles
 
 
 def points_arg(points, max_queries=MAX_QUERIES, device=None):
     """-> points: a contiguous CUDA float32 tensor [n, 3] of at most max_queries rows (ValueError otherwise)"""
-    MS._rows3("points", points, lambda x: x.dtype == torch.float32, "float32", device=device)
+    A.rows3("points", points, torch.float32, device=device)
     if points.shape[0] > max_queries:
         raise ValueError(f"{points.shape[0]} points are more than {max_queries}")
     return points
@@ -98,11 +84,7 @@ def points_arg(points, max_queries=MAX_QUERIES, device=None):
 
 def records_arg(records, max_queries=MAX_QUERIES, device=None):
     """-> records: a contiguous CUDA uint8 tensor [n, 32] of rgbid_cloud_point records, at most max_queries rows (ValueError otherwise)"""
-    if not (isinstance(records, torch.Tensor) and records.is_cuda and records.dtype == torch.uint8 and records.dim() == 2
-            and records.shape[1] == 32 and records.is_contiguous()):
-        raise ValueError("records: a contiguous CUDA uint8 tensor [n, 32] of rgbid_cloud_point records")
-    if device is not None and records.device.index != device:
-        raise ValueError(f"records must live on device {device}")
+    A.cuda_tensor("records", records, torch.uint8, (None, 32), "records: a contiguous CUDA uint8 tensor [n, 32] of rgbid_cloud_point records", device)
     if records.shape[0] > max_queries:
         raise ValueError(f"{records.shape[0]} records are more than {max_queries}")
     return records
@@ -125,26 +107,15 @@ def outputs_arg(outputs):
 class Distance(_lib.CtxHandle):
     """The truncated nearest-triangle search over meshes of up to max_vertices vertices and max_triangles triangles whose grid holds up to
     max_pairs (cell, triangle) pairs, for up to max_queries points per call, on the context's stream."""
-    _destroy = "rgbid_meshdist_destroy"
+    _destroy, _signatures, _timing, _stages = "rgbid_meshdist_destroy", SIGNATURES, "rgbid_meshdist_timing", STAGES
 
     def __init__(self, ctx, max_vertices, max_triangles, max_pairs, max_queries):
         self.max_vertices, self.max_triangles, self.max_pairs, self.max_queries = capacity_arg(max_vertices, max_triangles, max_pairs, max_queries)
         super().__init__(ctx)
         self.planned = None                    # the last plan's figures
         self.needed_pairs = None               # what the last plan said it needs, also when it was refused
-        L = self.L
-        L.rgbid_meshdist_create.argtypes = [C.c_void_p, C.c_void_p] + [C.c_ulonglong] * 4
-        L.rgbid_meshdist_plan.argtypes = [C.c_void_p, C.c_ulonglong, C.c_void_p, C.c_ulonglong, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
-        L.rgbid_meshdist_query.argtypes = [C.c_void_p, C.c_ulonglong] + [C.c_void_p] * 6
-        L.rgbid_meshdist_query_records.argtypes = [C.c_void_p, C.c_ulonglong] + [C.c_void_p] * 6
-        L.rgbid_meshdist_set_query_sort.argtypes = [C.c_void_p, C.c_int]
-        L.rgbid_meshdist_timing.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        self._created(L.rgbid_meshdist_create(C.byref(self._h), ctx._h, *(C.c_ulonglong(x) for x in (self.max_vertices, self.max_triangles,
-                                                                                                       self.max_pairs, self.max_queries))))
-
-    @property
-    def _dev(self):
-        return f"cuda:{self.ctx.device}"
+        self._created(self.L.rgbid_meshdist_create(C.byref(self._h), ctx._h, *(C.c_ulonglong(x) for x in (self.max_vertices, self.max_triangles,
+                                                                                                            self.max_pairs, self.max_queries))))
 
     def sort_queries(self, enable=True):
         """walk the queries of the following calls in the order of their cells (the default) or in input order; the outputs are the same"""
@@ -160,10 +131,9 @@ class Distance(_lib.CtxHandle):
         vertices, triangles = mesh_arg(vertices, triangles, self.max_vertices, self.max_triangles, self.ctx.device)
         self.planned, self.needed_pairs = None, None
         grid, stats = (C.c_longlong * 6)(), (C.c_ulonglong * 4)()
-        ptr = lambda x: C.c_void_p(x.data_ptr() if x.numel() else 0)
         self.ctx.wait_torch_stream()
-        err = self.L.rgbid_meshdist_plan(self._h, C.c_ulonglong(vertices.shape[0]), ptr(vertices), C.c_ulonglong(triangles.shape[0]), ptr(triangles),
-                                         C.c_float(d), C.c_float(0.0 if cell is None else c), grid, stats)
+        err = self.L.rgbid_meshdist_plan(self._h, C.c_ulonglong(vertices.shape[0]), self.ptr(vertices), C.c_ulonglong(triangles.shape[0]),
+                                         self.ptr(triangles), C.c_float(d), C.c_float(0.0 if cell is None else c), grid, stats)
         self.needed_pairs = int(stats[1])
         if err and self.needed_pairs > self.max_pairs:
             raise _lib.RgbidError(f"the mesh needs {self.needed_pairs} (cell, triangle) pairs, the handle holds {self.max_pairs}")
@@ -174,7 +144,7 @@ class Distance(_lib.CtxHandle):
     def query_into(self, points, triangle=None, distance=None, closest=None, region=None, candidates=None, records=False):
         """the raw call: the queries (float32 [n, 3], or with `records` uint8 [n, 32]) against the last plan, written asynchronously on
         the context's stream into the given CUDA tensors (or None)"""
-        ptr = lambda x: C.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
+        ptr = self.opt_ptr
         f = self.L.rgbid_meshdist_query_records if records else self.L.rgbid_meshdist_query
         check(f(self._h, C.c_ulonglong(points.shape[0]), ptr(points), ptr(triangle), ptr(distance), ptr(closest), ptr(region), ptr(candidates)))
 
@@ -201,12 +171,6 @@ class Distance(_lib.CtxHandle):
     def query_records(self, records, outputs=("triangle", "distance")):
         """the same for the positions of rgbid_cloud_point records (CUDA uint8 [n, 32])"""
         return self._query(records_arg(records, self.max_queries, self.ctx.device), outputs, True)
-
-    def timing(self, enable=True):
-        """record HIP events around the stages of the following calls; -> the device ms of the last ones {stage: ms}"""
-        ms = (C.c_float * 5)()
-        check(self.L.rgbid_meshdist_timing(self._h, int(enable), ms))
-        return dict(zip(STAGES, ms[:]))
 
 
 def summary(distance):

@@ -6,53 +6,43 @@ returns the kept records unchanged, in input order, bitwise reproducible (DESIGN
 `rgbid.cloud.write_ply` take them as they take the unfiltered cloud.
 """
 import ctypes as C
-import math
 
 import numpy as np
 import torch
 
+from . import _args as A
 from . import _lib
-from ._lib import check
+from ._lib import check, ci, cu, f32, u64, vp
 from .cloud import records, records_out
 
 MAX_POINTS = 1 << 31
 MAX_CELL = 1 << 18                      # RGBID_OUTLIER_MAX_CELL: the largest |floor(p * inv)| the plan accepts
 CELL_FACTOR = np.float32(1.0625)        # RGBID_OUTLIER_CELL_FACTOR: cell size / radius
 MIN_RADIUS, MAX_RADIUS = 2.0 ** -60, 2.0 ** 60
-EXPORTS = ["rgbid_outlier_create", "rgbid_outlier_destroy", "rgbid_outlier_plan", "rgbid_outlier_counts", "rgbid_outlier_emit",
-           "rgbid_outlier_timing"]
+SIGNATURES = {
+    "rgbid_outlier_create": (vp, vp, u64),
+    "rgbid_outlier_destroy": (vp,),
+    "rgbid_outlier_plan": (vp, vp, u64, f32, cu, cu, vp, vp),
+    "rgbid_outlier_counts": (vp, vp),
+    "rgbid_outlier_emit": (vp, vp, u64),
+    "rgbid_outlier_timing": (vp, ci, vp),
+}
+EXPORTS = list(SIGNATURES)
 STAGES = ("box", "sort", "cells", "count", "emit")
 
 
 def radius32(radius):
     """-> the radius as the float32 value the library receives: finite, > 0 and in [2^-60, 2^60] (ValueError otherwise)"""
-    try:
-        r = float(np.float32(radius))
-    except (TypeError, ValueError, OverflowError):
-        raise ValueError(f"radius: a number, got {radius!r}")
-    if not (math.isfinite(r) and r > 0):
-        raise ValueError(f"radius must be finite and > 0, got {radius!r}")
-    if not MIN_RADIUS <= r <= MAX_RADIUS:
-        raise ValueError(f"radius must lie in [2^-60, 2^60], got {radius!r}")
-    return r
+    r = A.positive32("radius", radius, f"radius: a number, got {radius!r}", over="warn")
+    return A.in_range("radius", r, MIN_RADIUS, MAX_RADIUS, "[2^-60, 2^60]", radius)
 
 
 def neighbour_args(min_neighbours, cap=None):
     """-> (min_neighbours, cap) as the library takes them: 0 <= min_neighbours <= cap, 1 <= cap < 2^32; the default cap is
     max(min_neighbours, 1) (ValueError otherwise)"""
-    if isinstance(min_neighbours, bool) or not isinstance(min_neighbours, (int, np.integer)):
-        raise ValueError(f"min_neighbours: an integer, got {min_neighbours!r}")
-    m = int(min_neighbours)
-    if cap is None:
-        cap = max(m, 1)
-    if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)):
-        raise ValueError(f"cap: an integer, got {cap!r}")
-    c = int(cap)
-    if not 1 <= c < 1 << 32:
-        raise ValueError(f"cap must lie in [1, 2^32), got {cap!r}")
-    if not 0 <= m <= c:
-        raise ValueError(f"min_neighbours must lie in [0, cap = {c}], got {min_neighbours!r}")
-    return m, c
+    m = A.integer("min_neighbours", min_neighbours)
+    c = A.integer_in("cap", max(m, 1) if cap is None else cap, 1, (1 << 32) - 1, "[1, 2^32)")
+    return A.in_range("min_neighbours", m, 0, c, f"[0, cap = {c}]", min_neighbours), c
 
 
 def cell_size(radius):
@@ -73,16 +63,11 @@ class Plan:
 
 class RadiusFilter(_lib.CtxHandle):
     """Radius outlier filter for up to max_points input records per plan, on the context's stream."""
-    _destroy = "rgbid_outlier_destroy"
+    _destroy, _signatures, _timing, _stages = "rgbid_outlier_destroy", SIGNATURES, "rgbid_outlier_timing", STAGES
 
     def __init__(self, ctx, max_points):
         super().__init__(ctx)
         self.max_points = int(max_points)
-        self.L.rgbid_outlier_create.argtypes = [C.c_void_p, C.c_void_p, C.c_ulonglong]
-        self.L.rgbid_outlier_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_float, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p]
-        self.L.rgbid_outlier_counts.argtypes = [C.c_void_p, C.c_void_p]
-        self.L.rgbid_outlier_emit.argtypes = [C.c_void_p, C.c_void_p, C.c_ulonglong]
-        self.L.rgbid_outlier_timing.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         self._created(self.L.rgbid_outlier_create(C.byref(self._h), ctx._h, C.c_ulonglong(self.max_points)))
 
     def plan(self, points, radius, min_neighbours, cap=None):
@@ -93,35 +78,28 @@ class RadiusFilter(_lib.CtxHandle):
         m, c = neighbour_args(min_neighbours, cap)
         stats = np.zeros(3, np.uint64); kept = C.c_ulonglong()
         self.ctx.wait_torch_stream()
-        check(self.L.rgbid_outlier_plan(self._h, C.c_void_p(points.data_ptr() if points.numel() else 0), C.c_ulonglong(points.shape[0]),
-                                        C.c_float(r), C.c_uint(c), C.c_uint(m), stats.ctypes.data_as(C.c_void_p), C.byref(kept)))
+        check(self.L.rgbid_outlier_plan(self._h, self.ptr(points), C.c_ulonglong(points.shape[0]), C.c_float(r), C.c_uint(c), C.c_uint(m),
+                                        stats.ctypes.data_as(C.c_void_p), C.byref(kept)))
         return Plan(kept.value, points.shape[0], stats)
 
     def counts(self, out):
         """write the clamped neighbour counts of the last plan, in input order, into `out` (CUDA int32 / uint32 tensor [>= n]).
         Asynchronous on the context's stream."""
         assert out.is_cuda and out.element_size() == 4 and not out.is_floating_point() and out.is_contiguous() and out.dim() == 1
-        check(self.L.rgbid_outlier_counts(self._h, C.c_void_p(out.data_ptr() if out.numel() else 0)))
+        check(self.L.rgbid_outlier_counts(self._h, self.ptr(out)))
 
     def emit(self, out):
         """write the kept records of the last plan into `out` (CUDA uint8 tensor [>= kept, 32]).  Asynchronous on the context's stream."""
         records_out(out)
-        check(self.L.rgbid_outlier_emit(self._h, C.c_void_p(out.data_ptr() if out.numel() else 0), C.c_ulonglong(out.shape[0])))
-
-    def timing(self, enable=True):
-        """record HIP events around the stages of the following plans / emits; -> the device ms of the last ones {stage: ms}"""
-        ms = (C.c_float * 5)()
-        check(self.L.rgbid_outlier_timing(self._h, int(enable), ms))
-        return dict(zip(STAGES, ms[:]))
+        check(self.L.rgbid_outlier_emit(self._h, self.ptr(out), C.c_ulonglong(out.shape[0])))
 
     def filter(self, points, radius, min_neighbours, cap=None, return_counts=False, return_plan=False):
         """-> CUDA uint8 [kept, 32]: the records of at least min_neighbours neighbours within radius, unchanged, in input order; with
         return_counts also the int32 [M] counts (clamped at cap, as non-negative values below 2^31 or their two's complement above);
         with return_plan also the Plan.  `points` must stay unchanged until this returns (it synchronises)."""
         p = self.plan(points, radius, min_neighbours, cap)
-        dev = f"cuda:{self.ctx.device}"
-        out = torch.empty((p.kept, 32), dtype=torch.uint8, device=dev)
-        cnt = torch.empty((p.n,), dtype=torch.int32, device=dev) if return_counts else None
+        out = torch.empty((p.kept, 32), dtype=torch.uint8, device=self._dev)
+        cnt = torch.empty((p.n,), dtype=torch.int32, device=self._dev) if return_counts else None
         self.ctx.wait_torch_stream()   # the outputs are torch's allocations
         if cnt is not None:
             self.counts(cnt)

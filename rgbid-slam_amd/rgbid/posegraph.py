@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import check
+from ._lib import check, ci, vp
 
 SEQ_ODO, SEQ_KF, LC_KF = 0, 1, 2
 OK, NOT_PD = 0, 1
@@ -22,8 +22,17 @@ EDGE_DTYPE = np.dtype([("from", "<i4"), ("to", "<i4"), ("type", "<i4"), ("reserv
 assert EDGE_DTYPE.itemsize == 400
 GRAPH_DTYPE = np.dtype([("v0", "<i4"), ("n_vertices", "<i4"), ("e0", "<i4"), ("n_edges", "<i4")])
 
-EXPORTS = ["rgbid_pg_create", "rgbid_pg_destroy", "rgbid_pg_optimise", "rgbid_pg_set_timing", "rgbid_pg_last_times", "rgbid_pg_last_work",
-           "rgbid_pg_set_limits", "rgbid_pg_envelope"]
+SIGNATURES = {
+    "rgbid_pg_create": (vp, vp),
+    "rgbid_pg_destroy": (vp,),
+    "rgbid_pg_optimise": (vp, ci, vp, vp, vp, ci, vp, vp, vp),
+    "rgbid_pg_set_limits": (vp, ci, ci),
+    "rgbid_pg_envelope": (ci, ci, vp, ci, ci, vp, vp, vp),
+    "rgbid_pg_set_timing": (vp, ci),
+    "rgbid_pg_last_times": (vp, vp, vp),
+    "rgbid_pg_last_work": (vp, vp, vp, vp),
+}
+EXPORTS = list(SIGNATURES)
 
 
 def edges(rows):
@@ -82,7 +91,7 @@ def choose_mode(graphs):
 class PoseGraph(_lib.CtxHandle):
     """Device pose-graph solver on a context's device and stream."""
 
-    _destroy = "rgbid_pg_destroy"
+    _destroy, _signatures = "rgbid_pg_destroy", SIGNATURES
 
     def __init__(self, ctx):
         super().__init__(ctx)
@@ -140,7 +149,7 @@ class PoseGraph(_lib.CtxHandle):
 def envelope(n_vertices, edges, stage):
     """Host only: the separators of a stage (0 / 1: multilevel level 2 / level 1, 2: single level) of one graph and the block envelope of its
     reduced system -> (sep_vertex [ns], first [ns]): first[i] is the first block column of block row i."""
-    L = _lib.lib()
+    L = _lib.bind(SIGNATURES)
     E = np.ascontiguousarray(edges, EDGE_DTYPE)
     n = C.c_int()
     sv = np.zeros(max(int(n_vertices), 1), np.int32)

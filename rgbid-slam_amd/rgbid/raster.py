@@ -10,10 +10,11 @@ import ctypes as C
 import numpy as np
 import torch
 
+from . import _args as A
 from . import _lib
 from . import mesh as MS
 from . import render as RD
-from ._lib import check
+from ._lib import check, ci, f32, u64, vp
 from .render import Pose, depth_range, intrinsics, outputs_arg, poses, rank_value
 
 MAX_TRIANGLES = (1 << 31) - 1
@@ -27,7 +28,14 @@ TILE = 8
 TIMED_CHUNKS = 8
 EMPTY = 0xFFFFFFFF
 NAN_BITS = 0x7FFFFFFF
-EXPORTS = ["rgbid_raster_create", "rgbid_raster_destroy", "rgbid_raster_views", "rgbid_raster_counts", "rgbid_raster_timing"]
+SIGNATURES = {
+    "rgbid_raster_create": (vp, vp, u64, u64, u64),
+    "rgbid_raster_destroy": (vp,),
+    "rgbid_raster_views": (vp, vp, u64, vp, u64, vp, vp, ci, vp, vp, ci, ci, f32, f32, vp, vp, vp, vp),
+    "rgbid_raster_counts": (vp, ci, vp),
+    "rgbid_raster_timing": (vp, ci, vp),
+}
+EXPORTS = list(SIGNATURES)
 STAGES = ("project", "setup", "large", "resolve")
 COUNTS = ("gated", "degenerate", "empty_box", "drawn", "fragments", "pixels")
 PLANES = RD.PLANES
@@ -35,14 +43,10 @@ PLANES = RD.PLANES
 
 def capacity_arg(max_vertices, max_triangles, max_pixels):
     """-> the capacities of a handle: 1 .. 2^31 vertices, 1 .. 2^31 - 1 triangles, at least one pixel (ValueError otherwise)"""
-    v, t, p = MS._integer("max_vertices", max_vertices), MS._integer("max_triangles", max_triangles), MS._integer("max_pixels", max_pixels)
-    if not 1 <= v <= MAX_VERTICES:
-        raise ValueError(f"max_vertices must lie in [1, 2^31], got {max_vertices!r}")
-    if not 1 <= t <= MAX_TRIANGLES:
-        raise ValueError(f"max_triangles must lie in [1, 2^31 - 1], got {max_triangles!r}")
-    if not 1 <= p <= 1 << 38:
-        raise ValueError(f"max_pixels must lie in [1, 2^38], got {max_pixels!r}")
-    return v, t, p
+    v, t, p = A.integer("max_vertices", max_vertices), A.integer("max_triangles", max_triangles), A.integer("max_pixels", max_pixels)
+    A.in_range("max_vertices", v, 1, MAX_VERTICES, "[1, 2^31]", max_vertices)
+    A.in_range("max_triangles", t, 1, MAX_TRIANGLES, "[1, 2^31 - 1]", max_triangles)
+    return v, t, A.in_range("max_pixels", p, 1, 1 << 38, "[1, 2^38]", max_pixels)
 
 
 def image_size(rows, cols, views=1, max_pixels=None):
@@ -59,24 +63,14 @@ def image_size(rows, cols, views=1, max_pixels=None):
 def mesh_arg(vertices, triangles, colours=None, normals=None, max_vertices=MAX_VERTICES, max_triangles=MAX_TRIANGLES, device=None):
     """-> (vertices, triangles, colours, normals): contiguous CUDA tensors float32 [n_v, 3], 4-byte integers [n_t, 3], uint8 [n_v, 3] or
     None, float32 [n_v, 3] or None, within the capacities (ValueError otherwise)"""
-    MS._rows3("vertices", vertices, lambda x: x.dtype == torch.float32, "float32", device=device)
+    A.rows3("vertices", vertices, torch.float32, device=device)
     n_v = vertices.shape[0]
     MS.mesh_arg(triangles, n_v, max_vertices, max_triangles, device)
     if colours is not None:
-        MS._rows3("colours", colours, lambda x: x.dtype == torch.uint8, "uint8", n_v, device)
+        A.rows3("colours", colours, torch.uint8, n_v, device)
     if normals is not None:
-        MS._rows3("normals", normals, lambda x: x.dtype == torch.float32, "float32", n_v, device)
+        A.rows3("normals", normals, torch.float32, n_v, device)
     return vertices, triangles, colours, normals
-
-
-def _plane(name, x, shape, dtype, device):
-    if x is None:
-        return None
-    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == dtype and tuple(x.shape) == shape and x.is_contiguous()):
-        raise ValueError(f"{name}: a contiguous CUDA {dtype} tensor {list(shape)}")
-    if device is not None and x.device.index != device:
-        raise ValueError(f"{name} must live on device {device}")
-    return x
 
 
 def plane_shapes(V, rows, cols):
@@ -86,21 +80,16 @@ def plane_shapes(V, rows, cols):
 
 class Rasteriser(_lib.CtxHandle):
     """Rasteriser for meshes of up to max_vertices vertices and max_triangles triangles and rows * cols * views <= max_pixels per call, on
-    the context's stream."""
-    _destroy = "rgbid_raster_destroy"
+    the context's stream.  timing() gives the last call's stages summed over its chunks of views (zeros for a call of more than
+    TIMED_CHUNKS chunks)."""
+    _destroy, _signatures, _timing, _stages = "rgbid_raster_destroy", SIGNATURES, "rgbid_raster_timing", STAGES
 
     def __init__(self, ctx, max_vertices, max_triangles, max_pixels):
         self.max_vertices, self.max_triangles, self.max_pixels = capacity_arg(max_vertices, max_triangles, max_pixels)
         super().__init__(ctx)
         self._views = 0
-        L = self.L
-        L.rgbid_raster_create.argtypes = [C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong]
-        L.rgbid_raster_views.argtypes = [C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_void_p, C.c_ulonglong, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                         C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.rgbid_raster_counts.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        L.rgbid_raster_timing.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        self._created(L.rgbid_raster_create(C.byref(self._h), ctx._h, C.c_ulonglong(self.max_vertices), C.c_ulonglong(self.max_triangles),
-                                            C.c_ulonglong(self.max_pixels)))
+        self._created(self.L.rgbid_raster_create(C.byref(self._h), ctx._h, C.c_ulonglong(self.max_vertices), C.c_ulonglong(self.max_triangles),
+                                                 C.c_ulonglong(self.max_pixels)))
 
     def render_into(self, vertices, triangles, R, t, K, rows, cols, colours=None, normals=None, z_min=0.05, z_max=20.0, index=None, depth=None,
                     colour=None, normal=None):
@@ -116,13 +105,14 @@ class Rasteriser(_lib.CtxHandle):
         shapes = plane_shapes(V, rows, cols)
         given = dict(index=index, depth=depth, colour=colour, normal=normal)
         for name, x in given.items():
-            _plane(name, x, shapes[name][0], shapes[name][1], dev)
+            if x is not None:
+                A.cuda_tensor(name, x, shapes[name][1], shapes[name][0], f"{name}: a contiguous CUDA {shapes[name][1]} tensor {list(shapes[name][0])}", dev)
         if colour is not None and colours is None:
             raise ValueError("the colour plane needs the vertices' colours")
         if normal is not None and normals is None:
             raise ValueError("the normal plane needs the vertices' normals")
         arr = (Pose * V)(*[Pose((C.c_double * 9)(*R[v].reshape(9)), (C.c_double * 3)(*t[v])) for v in range(V)])
-        ptr = lambda a: C.c_void_p(a.data_ptr() if a is not None and a.numel() else 0)
+        ptr = self.opt_ptr
         self._views = 0
         check(self.L.rgbid_raster_views(self._h, ptr(vertices), C.c_ulonglong(vertices.shape[0]), ptr(triangles), C.c_ulonglong(triangles.shape[0]),
                                         ptr(colours), ptr(normals), V, arr, k, rows, cols, C.c_float(lo), C.c_float(hi), ptr(index), ptr(depth),
@@ -142,9 +132,8 @@ class Rasteriser(_lib.CtxHandle):
             raise ValueError("the normal plane needs the vertices' normals")
         V = len(poses(R, t)[0])
         rows, cols = image_size(rows, cols, V, self.max_pixels)
-        dev = f"cuda:{self.ctx.device}"
         shapes = plane_shapes(V, rows, cols)
-        planes = {o: torch.empty(shapes[o][0], dtype=shapes[o][1], device=dev) for o in outs}
+        planes = {o: torch.empty(shapes[o][0], dtype=shapes[o][1], device=self._dev) for o in outs}
         self.ctx.wait_torch_stream()   # the mesh was written, and the planes allocated, on torch's stream
         self.render_into(vertices, triangles, R, t, K, rows, cols, colours, normals, z_min, z_max, **planes)
         self.ctx.sync()
@@ -157,13 +146,6 @@ class Rasteriser(_lib.CtxHandle):
         out = (C.c_ulonglong * (6 * self._views))()
         check(self.L.rgbid_raster_counts(self._h, self._views, out))
         return [dict(zip(COUNTS, (int(x) for x in out[6 * v:6 * v + 6]))) for v in range(self._views)]
-
-    def timing(self, enable=True):
-        """record HIP events around the stages of the following calls; -> the device ms of the last one {stage: ms}, summed over its
-        chunks of views (zeros for a call of more than TIMED_CHUNKS chunks)"""
-        ms = (C.c_float * 4)()
-        check(self.L.rgbid_raster_timing(self._h, int(enable), ms))
-        return dict(zip(STAGES, ms[:]))
 
 
 def render_mesh(ctx, vertices, triangles, R, t, K, rows, cols, colours=None, normals=None, z_min=0.05, z_max=20.0, outputs=("depth", "colour")):

@@ -11,8 +11,9 @@ import math
 import numpy as np
 import torch
 
+from . import _args as A
 from . import _lib
-from ._lib import check
+from ._lib import check, ci, f32, u64, vp
 from .cloud import records
 
 MAX_SPLAT = 4
@@ -22,8 +23,15 @@ VIEW_CHUNK = 16
 EMPTY = 0xFFFFFFFF
 NAN_BITS = 0x7FFFFFFF
 DEPTH_PNG_SCALE = 5000.0                # a TUM depth file holds metres * 5000 (millimetres * 5); 0 = no measurement
-EXPORTS = ["rgbid_render_create", "rgbid_render_destroy", "rgbid_render_pose_cw", "rgbid_render_views", "rgbid_render_timing",
-           "rgbid_render_stats"]
+SIGNATURES = {
+    "rgbid_render_create": (vp, vp, u64, u64),
+    "rgbid_render_destroy": (vp,),
+    "rgbid_render_pose_cw": (vp, vp),
+    "rgbid_render_views": (vp, vp, u64, ci, vp, vp, ci, ci, ci, f32, f32, vp, vp, vp, vp),
+    "rgbid_render_timing": (vp, ci, vp),
+    "rgbid_render_stats": (vp, ci, vp),
+}
+EXPORTS = list(SIGNATURES)
 STAGES = ("clear", "splat", "resolve")
 PLANES = ("index", "depth", "colour", "normal")
 
@@ -33,15 +41,9 @@ class Pose(C.Structure):
     _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3)]
 
 
-def _integer(name, v):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-        raise ValueError(f"{name}: an integer, got {v!r}")
-    return int(v)
-
-
 def image_size(rows, cols, views=1, max_pixels=None):
     """-> (rows, cols) as the library takes them: 1 .. 2^20 each, and rows * cols * views <= max_pixels when given (ValueError otherwise)"""
-    r, c, v = _integer("rows", rows), _integer("cols", cols), _integer("views", views)
+    r, c, v = A.integer("rows", rows), A.integer("cols", cols), A.integer("views", views)
     if not (1 <= r <= MAX_DIM and 1 <= c <= MAX_DIM):
         raise ValueError(f"rows and cols must lie in [1, 2^20], got {rows!r} x {cols!r}")
     if v < 1:
@@ -53,18 +55,12 @@ def image_size(rows, cols, views=1, max_pixels=None):
 
 def splat_arg(splat):
     """-> the splat half-width: an integer in 0 .. 4 (ValueError otherwise)"""
-    s = _integer("splat", splat)
-    if not 0 <= s <= MAX_SPLAT:
-        raise ValueError(f"splat must lie in [0, {MAX_SPLAT}], got {splat!r}")
-    return s
+    return A.integer_in("splat", splat, 0, MAX_SPLAT, f"[0, {MAX_SPLAT}]")
 
 
 def depth_range(z_min, z_max):
     """-> (z_min, z_max) as the float32 values the library receives: finite, 0 < z_min <= z_max (ValueError otherwise)"""
-    try:
-        lo, hi = float(np.float32(z_min)), float(np.float32(z_max))
-    except (TypeError, ValueError, OverflowError):
-        raise ValueError(f"z_min, z_max: numbers, got {z_min!r}, {z_max!r}")
+    lo, hi = (A.float32(z, f"z_min, z_max: numbers, got {z_min!r}, {z_max!r}", over="warn") for z in (z_min, z_max))
     if not (math.isfinite(lo) and math.isfinite(hi) and 0 < lo <= hi):
         raise ValueError(f"z_min, z_max must be finite with 0 < z_min <= z_max, got {z_min!r}, {z_max!r}")
     return lo, hi
@@ -113,24 +109,18 @@ def pose_cw(R, t):
     """the twelve float32 values r00 .. r22, tx, ty, tz of R_CW | t_CW as the library forms them from one world pose"""
     p = Pose((C.c_double * 9)(*np.asarray(R, np.float64).reshape(9)), (C.c_double * 3)(*np.asarray(t, np.float64).reshape(3)))
     out = (C.c_float * 12)()
-    check(_lib.lib().rgbid_render_pose_cw(C.byref(p), out))
+    check(_lib.bind(SIGNATURES).rgbid_render_pose_cw(C.byref(p), out))
     return np.array(out[:], np.float32)
 
 
 class Renderer(_lib.CtxHandle):
     """Renderer for up to max_points records and rows * cols * views <= max_pixels per call, on the context's stream."""
-    _destroy = "rgbid_render_destroy"
+    _destroy, _signatures, _timing, _stages = "rgbid_render_destroy", SIGNATURES, "rgbid_render_timing", STAGES
 
     def __init__(self, ctx, max_points, max_pixels):
         super().__init__(ctx)
         self.max_points, self.max_pixels = int(max_points), int(max_pixels)
-        L = self.L
-        L.rgbid_render_create.argtypes = [C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_ulonglong]
-        L.rgbid_render_views.argtypes = [C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                         C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.rgbid_render_timing.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        L.rgbid_render_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        self._created(L.rgbid_render_create(C.byref(self._h), ctx._h, C.c_ulonglong(self.max_points), C.c_ulonglong(self.max_pixels)))
+        self._created(self.L.rgbid_render_create(C.byref(self._h), ctx._h, C.c_ulonglong(self.max_points), C.c_ulonglong(self.max_pixels)))
 
     def render_into(self, points, R, t, K, rows, cols, splat, z_min, z_max, index=None, depth=None, colour=None, normal=None):
         """the raw call: checked arguments, the given CUDA planes (or None) filled asynchronously on the context's stream"""
@@ -144,8 +134,8 @@ class Renderer(_lib.CtxHandle):
         if points.shape[0] > self.max_points:
             raise ValueError(f"{points.shape[0]} records are more than the renderer's {self.max_points}")
         arr = (Pose * V)(*[Pose((C.c_double * 9)(*R[v].reshape(9)), (C.c_double * 3)(*t[v])) for v in range(V)])
-        ptr = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None
-        check(self.L.rgbid_render_views(self._h, C.c_void_p(points.data_ptr() if points.numel() else 0), C.c_ulonglong(points.shape[0]), V, arr, k,
+        ptr = self.opt_ptr
+        check(self.L.rgbid_render_views(self._h, ptr(points), C.c_ulonglong(points.shape[0]), V, arr, k,
                                         rows, cols, s, C.c_float(lo), C.c_float(hi), ptr(index), ptr(depth), ptr(colour), ptr(normal)))
 
     def render(self, points, R, t, K, rows, cols, splat=1, z_min=0.05, z_max=20.0, outputs=("depth", "colour")):
@@ -156,20 +146,13 @@ class Renderer(_lib.CtxHandle):
         outs = outputs_arg(outputs)
         V = len(poses(R, t)[0])
         rows, cols = image_size(rows, cols, V, self.max_pixels)
-        dev = f"cuda:{self.ctx.device}"
         shape = {"index": ((V, rows, cols), torch.int32), "depth": ((V, rows, cols), torch.float32),
                  "colour": ((V, rows, cols, 3), torch.uint8), "normal": ((V, 3, rows, cols), torch.float32)}
-        planes = {o: torch.empty(shape[o][0], dtype=shape[o][1], device=dev) for o in outs}
+        planes = {o: torch.empty(shape[o][0], dtype=shape[o][1], device=self._dev) for o in outs}
         self.ctx.wait_torch_stream()   # the records were written, and the planes allocated, on torch's stream
         self.render_into(points, R, t, K, rows, cols, splat, z_min, z_max, **planes)
         self.ctx.sync()
         return planes
-
-    def timing(self, enable=True):
-        """record HIP events around the stages of the following calls; -> the device ms of the last one {stage: ms}"""
-        ms = (C.c_float * 3)()
-        check(self.L.rgbid_render_timing(self._h, int(enable), ms))
-        return dict(zip(STAGES, ms[:]))
 
     def stats(self, enable=True):
         """count in the following calls; -> the last one's {pairs, writes, atomics}: visible (record, view) pairs, the pixel writes they

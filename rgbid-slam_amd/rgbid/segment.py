@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import check
+from ._lib import check, ci, f32, vp
 from .cloud import Source, source
 
 MAX_BINS, DEFAULT_BINS = 128, 80
@@ -20,22 +20,33 @@ MAX_LEVELS, DEFAULT_LEVELS = 8, 4
 MAX_WINDOW = 256
 DEFAULT_K, DEFAULT_MIN_SIZE = 0.6, 300
 THRESHOLDS = np.array([0.0, 0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7, 0.8, 0.9], np.float32)
-EXPORTS = ["rgbid_segment_create", "rgbid_segment_destroy", "rgbid_segment_workspace_bytes", "rgbid_segment_device_bytes", "rgbid_segment_bins", "rgbid_segment_set_window",
-           "rgbid_segment_run", "rgbid_segment_mask_keypoints", "rgbid_segment_last_rounds", "rgbid_segment_timing"]
+SIGNATURES = {
+    "rgbid_segment_create": (vp, vp, ci, ci, ci, ci),
+    "rgbid_segment_destroy": (vp,),
+    "rgbid_segment_workspace_bytes": (ci, ci, ci, ci, vp),
+    "rgbid_segment_device_bytes": (vp, vp),
+    "rgbid_segment_bins": (ci, vp),
+    "rgbid_segment_set_window": (vp, ci),
+    "rgbid_segment_run": (vp, ci, vp, vp, f32, ci, ci, ci, vp, vp, vp, vp, vp, vp),
+    "rgbid_segment_mask_keypoints": (vp, vp, vp, ci, ci, vp, vp, ci, vp),
+    "rgbid_segment_last_rounds": (vp, vp),
+    "rgbid_segment_timing": (vp, ci, vp),
+}
+EXPORTS = list(SIGNATURES)
 STAGES = ("edges", "sort", "pass1", "pass2", "labels", "histogram")
 
 
 def bins(nbins=DEFAULT_BINS):
     """the bin centres of the histogram of normals, float32 [nbins, 3] (needs no device)"""
     out = np.zeros((int(nbins), 3), np.float32)
-    check(_lib.lib().rgbid_segment_bins(int(nbins), out.ctypes.data_as(C.c_void_p)))
+    check(_lib.bind(SIGNATURES).rgbid_segment_bins(int(nbins), out.ctypes.data_as(C.c_void_p)))
     return out
 
 
 def workspace_bytes(rows, cols, max_keyframes, max_segments):
     """device bytes a Segmenter of these arguments allocates (needs no device)"""
     b = C.c_ulonglong()
-    check(_lib.lib().rgbid_segment_workspace_bytes(int(rows), int(cols), int(max_keyframes), int(max_segments), C.byref(b)))
+    check(_lib.bind(SIGNATURES).rgbid_segment_workspace_bytes(int(rows), int(cols), int(max_keyframes), int(max_segments), C.byref(b)))
     return b.value
 
 
@@ -62,7 +73,7 @@ def blocks_of(blocks):
 class Segmenter(_lib.CtxHandle):
     """Segmenter for keyframes of rows x cols pixels, up to max_keyframes per call, with tables for max_segments segments per keyframe
     (default: min(rows cols, 4096)), on the context's stream."""
-    _destroy = "rgbid_segment_destroy"
+    _destroy, _signatures, _timing, _stages = "rgbid_segment_destroy", SIGNATURES, "rgbid_segment_timing", STAGES
 
     def __init__(self, ctx, rows, cols, max_keyframes, max_segments=None, k=DEFAULT_K, min_size=DEFAULT_MIN_SIZE, nbins=DEFAULT_BINS,
                  levels=DEFAULT_LEVELS):
@@ -70,13 +81,7 @@ class Segmenter(_lib.CtxHandle):
         self.rows, self.cols, self.max_keyframes = int(rows), int(cols), int(max_keyframes)
         self.max_segments = int(max_segments) if max_segments is not None else min(self.rows * self.cols, 4096)
         self.k, self.min_size, self.nbins, self.levels = float(k), int(min_size), int(nbins), int(levels)
-        L = self.L
-        L.rgbid_segment_run.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6
-        L.rgbid_segment_mask_keypoints.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        L.rgbid_segment_set_window.argtypes = [C.c_void_p, C.c_int]
-        L.rgbid_segment_last_rounds.argtypes = [C.c_void_p, C.c_void_p]
-        L.rgbid_segment_timing.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        self._created(L.rgbid_segment_create(C.byref(self._h), ctx._h, self.rows, self.cols, self.max_keyframes, self.max_segments))
+        self._created(self.L.rgbid_segment_create(C.byref(self._h), ctx._h, self.rows, self.cols, self.max_keyframes, self.max_segments))
 
     def set_window(self, window):
         """test hook: the window of the union-find rounds (1 .. 256); no window changes a result"""
@@ -92,7 +97,7 @@ class Segmenter(_lib.CtxHandle):
         min_size = self.min_size if min_size is None else int(min_size)
         nbins = self.nbins if nbins is None else int(nbins)
         levels = self.levels if levels is None else int(levels)
-        dev = f"cuda:{self.ctx.device}"
+        dev = self._dev
         i32 = dict(dtype=torch.int32, device=dev)
         labels = torch.empty((n, self.rows, self.cols), **i32)
         counts = torch.empty((n,), **i32)
@@ -136,13 +141,6 @@ class Segmenter(_lib.CtxHandle):
         r = (C.c_ulonglong * 2)()
         check(self.L.rgbid_segment_last_rounds(self._h, r))
         return int(r[0]), int(r[1])
-
-    def timing(self, enable=True):
-        """record HIP events around the stages of the following calls; -> the device ms of the last one {stage: ms}"""
-        ms = (C.c_float * 6)()
-        check(self.L.rgbid_segment_timing(self._h, int(enable), ms))
-        return dict(zip(STAGES, ms[:]))
-
 
 DEFAULT_MAX_SEGMENTS = 4096
 

@@ -9,15 +9,23 @@ import ctypes as C
 import numpy as np
 import torch
 
+from . import _args as A
 from . import _lib
 from . import mesh as MS
-from ._lib import check
+from ._lib import check, ci, cu, u64, vp
 
 MAX_VERTICES = 1 << 31
 MAX_TRIANGLES = 1 << 31
 NO_CLUSTER = 0xFFFFFFFF
 KEEP_DUPLICATES = 1
-EXPORTS = ["rgbid_simplify_create", "rgbid_simplify_destroy", "rgbid_simplify_plan", "rgbid_simplify_emit", "rgbid_simplify_timing"]
+SIGNATURES = {
+    "rgbid_simplify_create": (vp, vp, u64, u64),
+    "rgbid_simplify_destroy": (vp,),
+    "rgbid_simplify_plan": (vp, u64, vp, u64, vp, vp, cu, vp, vp),
+    "rgbid_simplify_emit": (vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, u64),
+    "rgbid_simplify_timing": (vp, ci, vp),
+}
+EXPORTS = list(SIGNATURES)
 STAGES = ("vertices", "triangles", "emit")
 COUNTS = ("participating", "clusters", "lost", "collapsed", "duplicate", "kept")
 
@@ -46,30 +54,21 @@ def cell_arg(cell):
 def mesh_arg(vertices, triangles, max_vertices=MAX_VERTICES, max_triangles=MAX_TRIANGLES, device=None):
     """-> (vertices, triangles): contiguous CUDA tensors float32 [n_v, 3] and 4-byte integers [n_t, 3] within the capacities, no triangles
     without vertices (ValueError otherwise)"""
-    MS._rows3("vertices", vertices, lambda x: x.dtype == torch.float32, "float32", device=device)
+    A.rows3("vertices", vertices, torch.float32, device=device)
     triangles, _ = MS.mesh_arg(triangles, vertices.shape[0], max_vertices, max_triangles, device)
     return vertices, triangles
 
 
 class Simplifier(_lib.CtxHandle):
     """Vertex clustering of meshes of up to max_vertices vertices and max_triangles triangles, on the context's stream."""
-    _destroy = "rgbid_simplify_destroy"
+    _destroy, _signatures, _timing, _stages = "rgbid_simplify_destroy", SIGNATURES, "rgbid_simplify_timing", STAGES
 
     def __init__(self, ctx, max_vertices, max_triangles):
         self.max_vertices, self.max_triangles = capacity_arg(max_vertices, max_triangles)
         super().__init__(ctx)
         self._mesh = None                      # the planned mesh: emit reads it again
         self.counts = None
-        L = self.L
-        L.rgbid_simplify_create.argtypes = [C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_ulonglong]
-        L.rgbid_simplify_plan.argtypes = [C.c_void_p, C.c_ulonglong, C.c_void_p, C.c_ulonglong, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
-        L.rgbid_simplify_emit.argtypes = [C.c_void_p] + [C.c_void_p] * 8 + [C.c_ulonglong, C.c_ulonglong]
-        L.rgbid_simplify_timing.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        self._created(L.rgbid_simplify_create(C.byref(self._h), ctx._h, C.c_ulonglong(self.max_vertices), C.c_ulonglong(self.max_triangles)))
-
-    @property
-    def _dev(self):
-        return f"cuda:{self.ctx.device}"
+        self._created(self.L.rgbid_simplify_create(C.byref(self._h), ctx._h, C.c_ulonglong(self.max_vertices), C.c_ulonglong(self.max_triangles)))
 
     def plan(self, vertices, triangles, cell, keep_duplicates=False):
         """cluster the mesh (CUDA float32 [n_v, 3], 4-byte integers [n_t, 3]) with cells of `cell` metres (a scalar or three values)
@@ -79,17 +78,16 @@ class Simplifier(_lib.CtxHandle):
         vertices, triangles = mesh_arg(vertices, triangles, self.max_vertices, self.max_triangles, self.ctx.device)
         self._mesh, self.counts = None, None
         grid, counts = (C.c_longlong * 6)(), (C.c_ulonglong * 6)()
-        ptr = lambda x: C.c_void_p(x.data_ptr() if x.numel() else 0)
         self.ctx.wait_torch_stream()
-        check(self.L.rgbid_simplify_plan(self._h, C.c_ulonglong(vertices.shape[0]), ptr(vertices), C.c_ulonglong(triangles.shape[0]), ptr(triangles),
-                                         (C.c_float * 3)(*cell), KEEP_DUPLICATES if keep_duplicates else 0, grid, counts))
+        check(self.L.rgbid_simplify_plan(self._h, C.c_ulonglong(vertices.shape[0]), self.ptr(vertices), C.c_ulonglong(triangles.shape[0]),
+                                         self.ptr(triangles), (C.c_float * 3)(*cell), KEEP_DUPLICATES if keep_duplicates else 0, grid, counts))
         self._mesh = (vertices, triangles)
         self.counts = dict(zip(COUNTS, (int(x) for x in counts)))
         return dict(grid=[int(x) for x in grid], **self.counts)
 
     def emit_into(self, colours, normals, vertices_out, colours_out, normals_out, members_out, cluster_of_out, triangles_out):
         """the raw call: the last plan written asynchronously on the context's stream into the given CUDA tensors (or None)"""
-        ptr = lambda x: C.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
+        ptr = self.opt_ptr
         rows = lambda x: C.c_ulonglong(x.shape[0] if x is not None else 0)
         check(self.L.rgbid_simplify_emit(self._h, ptr(colours), ptr(normals), ptr(vertices_out), ptr(colours_out), ptr(normals_out), ptr(members_out),
                                          ptr(cluster_of_out), ptr(triangles_out), rows(vertices_out), rows(triangles_out)))
@@ -102,9 +100,9 @@ class Simplifier(_lib.CtxHandle):
             raise ValueError("emit: nothing is planned")
         dev, n = self.ctx.device, self._mesh[0].shape[0]
         if colours is not None:
-            MS._rows3("colours", colours, lambda x: x.dtype == torch.uint8, "uint8", n, dev)
+            A.rows3("colours", colours, torch.uint8, n, dev)
         if normals is not None:
-            MS._rows3("normals", normals, lambda x: x.dtype == torch.float32, "float32", n, dev)
+            A.rows3("normals", normals, torch.float32, n, dev)
         nc, kt = self.counts["clusters"], self.counts["kept"]
         new = lambda like, rows: None if like is None else torch.empty((rows, 3), dtype=like.dtype, device=self._dev)
         out = dict(vertices=new(self._mesh[0], nc), colours=new(colours, nc), normals=new(normals, nc),
@@ -115,12 +113,6 @@ class Simplifier(_lib.CtxHandle):
         self.emit_into(colours, normals, out["vertices"], out["colours"], out["normals"], out["members"], out["cluster_of"], out["triangles"])
         self.ctx.sync()
         return out
-
-    def timing(self, enable=True):
-        """record HIP events around the stages of the following calls; -> the device ms of the last ones {stage: ms}"""
-        ms = (C.c_float * 3)()
-        check(self.L.rgbid_simplify_timing(self._h, int(enable), ms))
-        return dict(zip(STAGES, ms[:]))
 
 
 def simplify_mesh(ctx, vertices, colours, triangles, normals=None, cell=0.05, keep_duplicates=False, drop_unreferenced=True):

@@ -12,29 +12,35 @@ import math
 import numpy as np
 import torch
 
+from . import _args as A
 from . import _lib
 from . import mesh as MS
-from ._lib import check
+from ._lib import check, ci, cu, f64, u64, vp
 
 MAX_VERTICES = 1 << 31
 MAX_TRIANGLES = 1 << 29
 MAX_ITERATIONS = 4096
 PLAN_NORMALS = 1
 PIN_BOUNDARY = 1
-EXPORTS = ["rgbid_smooth_create", "rgbid_smooth_destroy", "rgbid_smooth_plan", "rgbid_smooth_adjacency", "rgbid_smooth_run", "rgbid_smooth_normals",
-           "rgbid_smooth_timing"]
+SIGNATURES = {
+    "rgbid_smooth_create": (vp, vp, u64, u64),
+    "rgbid_smooth_destroy": (vp,),
+    "rgbid_smooth_plan": (vp, u64, u64, vp, cu, vp),
+    "rgbid_smooth_adjacency": (vp, vp, vp, vp, vp, u64),
+    "rgbid_smooth_run": (vp, vp, vp, cu, f64, f64, cu),
+    "rgbid_smooth_normals": (vp, vp, vp),
+    "rgbid_smooth_timing": (vp, ci, vp),
+}
+EXPORTS = list(SIGNATURES)
 STAGES = ("plan", "run", "normals")
 COUNTS = ("pairs", "edges", "boundary_pairs", "boundary_vertices", "isolated", "max_degree", "dropped", "non_manifold")
 
 
 def capacity_arg(max_vertices, max_triangles):
     """-> (max_vertices, max_triangles) of a handle: 1 .. 2^31 and 1 .. 2^29 (ValueError otherwise)"""
-    v, t = MS._integer("max_vertices", max_vertices), MS._integer("max_triangles", max_triangles)
-    if not 1 <= v <= MAX_VERTICES:
-        raise ValueError(f"max_vertices must lie in [1, 2^31], got {max_vertices!r}")
-    if not 1 <= t <= MAX_TRIANGLES:
-        raise ValueError(f"max_triangles must lie in [1, 2^29], got {max_triangles!r}")
-    return v, t
+    v, t = A.integer("max_vertices", max_vertices), A.integer("max_triangles", max_triangles)
+    A.in_range("max_vertices", v, 1, MAX_VERTICES, "[1, 2^31]", max_vertices)
+    return v, A.in_range("max_triangles", t, 1, MAX_TRIANGLES, "[1, 2^29]", max_triangles)
 
 
 def mesh_arg(triangles, n_vertices, max_vertices=MAX_VERTICES, max_triangles=MAX_TRIANGLES, device=None):
@@ -45,10 +51,7 @@ def mesh_arg(triangles, n_vertices, max_vertices=MAX_VERTICES, max_triangles=MAX
 
 def iterations_arg(iterations):
     """-> iterations: an integer in 0 .. 4096 (ValueError otherwise)"""
-    n = MS._integer("iterations", iterations)
-    if not 0 <= n <= MAX_ITERATIONS:
-        raise ValueError(f"iterations must lie in [0, {MAX_ITERATIONS}], got {iterations!r}")
-    return n
+    return A.integer_in("iterations", iterations, 0, MAX_ITERATIONS, f"[0, {MAX_ITERATIONS}]")
 
 
 def factors_arg(lam, mu):
@@ -66,25 +69,14 @@ def factors_arg(lam, mu):
 
 class Smoother(_lib.CtxHandle):
     """Taubin smoothing and vertex normals of meshes of up to max_vertices vertices and max_triangles triangles, on the context's stream."""
-    _destroy = "rgbid_smooth_destroy"
+    _destroy, _signatures, _timing, _stages = "rgbid_smooth_destroy", SIGNATURES, "rgbid_smooth_timing", STAGES
 
     def __init__(self, ctx, max_vertices, max_triangles):
         self.max_vertices, self.max_triangles = capacity_arg(max_vertices, max_triangles)
         super().__init__(ctx)
         self._triangles = None                 # the planned triangles: normals reads them again
         self.n_vertices, self.counts, self.has_normals = 0, None, False
-        L = self.L
-        L.rgbid_smooth_create.argtypes = [C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_ulonglong]
-        L.rgbid_smooth_plan.argtypes = [C.c_void_p, C.c_ulonglong, C.c_ulonglong, C.c_void_p, C.c_uint32, C.c_void_p]
-        L.rgbid_smooth_adjacency.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_ulonglong]
-        L.rgbid_smooth_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_double, C.c_double, C.c_uint32]
-        L.rgbid_smooth_normals.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.rgbid_smooth_timing.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        self._created(L.rgbid_smooth_create(C.byref(self._h), ctx._h, C.c_ulonglong(self.max_vertices), C.c_ulonglong(self.max_triangles)))
-
-    @property
-    def _dev(self):
-        return f"cuda:{self.ctx.device}"
+        self._created(self.L.rgbid_smooth_create(C.byref(self._h), ctx._h, C.c_ulonglong(self.max_vertices), C.c_ulonglong(self.max_triangles)))
 
     def plan(self, triangles, n_vertices, normals=False):
         """the neighbourhoods of the mesh `triangles` (CUDA [n_t, 3], 4-byte integers) over n_vertices vertices, with `normals` also the
@@ -94,8 +86,8 @@ class Smoother(_lib.CtxHandle):
         self._triangles, self.counts = None, None
         counts = (C.c_ulonglong * 8)()
         self.ctx.wait_torch_stream()
-        check(self.L.rgbid_smooth_plan(self._h, C.c_ulonglong(n_v), C.c_ulonglong(triangles.shape[0]),
-                                       C.c_void_p(triangles.data_ptr() if triangles.numel() else 0), PLAN_NORMALS if normals else 0, counts))
+        check(self.L.rgbid_smooth_plan(self._h, C.c_ulonglong(n_v), C.c_ulonglong(triangles.shape[0]), self.ptr(triangles), PLAN_NORMALS if normals else 0,
+                                       counts))
         self._triangles, self.n_vertices, self.has_normals = triangles, n_v, bool(normals)
         self.counts = dict(zip(COUNTS, (int(x) for x in counts)))
         return dict(self.counts)
@@ -106,7 +98,7 @@ class Smoother(_lib.CtxHandle):
 
     def adjacency_into(self, offsets, neighbours, incidences, boundary, pair_capacity):
         """the raw call: the last plan's CSR copied asynchronously on the context's stream into the given CUDA tensors (or None)"""
-        ptr = lambda x: C.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
+        ptr = self.opt_ptr
         check(self.L.rgbid_smooth_adjacency(self._h, ptr(offsets), ptr(neighbours), ptr(incidences), ptr(boundary), C.c_ulonglong(pair_capacity)))
 
     def adjacency(self):
@@ -128,16 +120,15 @@ class Smoother(_lib.CtxHandle):
         lam, mu = factors_arg(lam, mu)
         self._planned("run")
         for name, x in (("vertices", vertices), ("vertices_out", vertices_out)):
-            MS._rows3(name, x, lambda y: y.dtype == torch.float32, "float32", self.n_vertices, self.ctx.device)
-        ptr = lambda x: C.c_void_p(x.data_ptr() if x.numel() else 0)
-        check(self.L.rgbid_smooth_run(self._h, ptr(vertices), ptr(vertices_out), n, lam, mu, PIN_BOUNDARY if pin_boundary else 0))
+            A.rows3(name, x, torch.float32, self.n_vertices, self.ctx.device)
+        check(self.L.rgbid_smooth_run(self._h, self.ptr(vertices), self.ptr(vertices_out), n, lam, mu, PIN_BOUNDARY if pin_boundary else 0))
 
     def run(self, vertices, iterations, lam=0.5, mu=-0.53, pin_boundary=False):
         """the positions after `iterations` iterations over the last plan -> a new CUDA tensor float32 [n_v, 3].  Synchronises."""
         n = iterations_arg(iterations)
         lam, mu = factors_arg(lam, mu)
         self._planned("run")
-        MS._rows3("vertices", vertices, lambda y: y.dtype == torch.float32, "float32", self.n_vertices, self.ctx.device)
+        A.rows3("vertices", vertices, torch.float32, self.n_vertices, self.ctx.device)
         out = torch.empty_like(vertices)
         self.ctx.wait_torch_stream()   # the output is torch's allocation
         self.run_into(vertices, out, n, lam, mu, pin_boundary)
@@ -146,8 +137,7 @@ class Smoother(_lib.CtxHandle):
 
     def normals_into(self, vertices, normals_out):
         """the raw call: the area-weighted normals of `vertices` over the last plan into normals_out, asynchronously"""
-        ptr = lambda x: C.c_void_p(x.data_ptr() if x.numel() else 0)
-        check(self.L.rgbid_smooth_normals(self._h, ptr(vertices), ptr(normals_out)))
+        check(self.L.rgbid_smooth_normals(self._h, self.ptr(vertices), self.ptr(normals_out)))
 
     def normals(self, vertices):
         """the area-weighted unit normals of the positions `vertices` (CUDA float32 [n_v, 3]) over the last plan, which must have been made
@@ -155,18 +145,12 @@ class Smoother(_lib.CtxHandle):
         self._planned("normals")
         if not self.has_normals:
             raise ValueError("normals: the plan was made without normals=True")
-        MS._rows3("vertices", vertices, lambda y: y.dtype == torch.float32, "float32", self.n_vertices, self.ctx.device)
+        A.rows3("vertices", vertices, torch.float32, self.n_vertices, self.ctx.device)
         out = torch.empty_like(vertices)
         self.ctx.wait_torch_stream()   # the output is torch's allocation
         self.normals_into(vertices, out)
         self.ctx.sync()
         return out
-
-    def timing(self, enable=True):
-        """record HIP events around the stages of the following calls; -> the device ms of the last ones {stage: ms}"""
-        ms = (C.c_float * 3)()
-        check(self.L.rgbid_smooth_timing(self._h, int(enable), ms))
-        return dict(zip(STAGES, ms[:]))
 
 
 def smooth_mesh(ctx, vertices, triangles, iterations, lam=0.5, mu=-0.53, pin_boundary=False, normals=False):
@@ -176,7 +160,7 @@ def smooth_mesh(ctx, vertices, triangles, iterations, lam=0.5, mu=-0.53, pin_bou
     dropped, non_manifold)."""
     n = iterations_arg(iterations)
     lam, mu = factors_arg(lam, mu)
-    MS._rows3("vertices", vertices, lambda y: y.dtype == torch.float32, "float32")
+    A.rows3("vertices", vertices, torch.float32)
     triangles, n_v = mesh_arg(triangles, vertices.shape[0])
     sm = Smoother(ctx, max(n_v, 1), max(triangles.shape[0], 1))
     try:

@@ -13,8 +13,9 @@ import math
 import numpy as np
 import torch
 
+from . import _args as A
 from . import _lib
-from ._lib import check
+from ._lib import check, ci, cu, f32, f64, u64, vp
 from .consist import planes_arg
 from .render import Pose, agreement_summary, depth_range, image_size, intrinsics, poses, rank_value  # noqa: F401 (agreement_summary: for callers)
 
@@ -22,13 +23,33 @@ MAX_VOXELS = 1 << 29
 MAX_VIEWS = 65535
 MAX_WEIGHT = 65535
 VIEW_CHUNK = 16                         # RGBID_TSDF_VIEW_CHUNK: views one launch walks; more go in further launches, in order
-EXPORTS = ["rgbid_tsdf_create", "rgbid_tsdf_destroy", "rgbid_tsdf_configure", "rgbid_tsdf_reset", "rgbid_tsdf_integrate", "rgbid_tsdf_get_state",
-           "rgbid_tsdf_set_state", "rgbid_tsdf_extract_plan", "rgbid_tsdf_extract_emit", "rgbid_tsdf_timing"]
+VOLUME_SIGNATURES = {                   # rgbid_tsdf.h
+    "rgbid_tsdf_create": (vp, vp, u64, ci, ci),
+    "rgbid_tsdf_destroy": (vp,),
+    "rgbid_tsdf_configure": (vp, ci, ci, ci, vp, f32, f32),
+    "rgbid_tsdf_reset": (vp,),
+    "rgbid_tsdf_integrate": (vp, ci, vp, vp, ci, ci, f32, f32),
+    "rgbid_tsdf_get_state": (vp, vp, vp, vp),
+    "rgbid_tsdf_set_state": (vp, vp, vp, vp),
+    "rgbid_tsdf_extract_plan": (vp, cu, vp, vp),
+    "rgbid_tsdf_extract_emit": (vp, vp, vp, vp, u64, u64),
+    "rgbid_tsdf_timing": (vp, ci, vp),
+}
+RAYCAST_SIGNATURES = {                  # rgbid_tsdf_raycast.h
+    "rgbid_tsdf_pose_wc": (vp, vp),
+    "rgbid_tsdf_raycast": (vp, ci, vp, vp, ci, ci, f32, f32, f32, cu, vp, vp, vp),
+    "rgbid_tsdf_raycast_timing": (vp, ci, vp),
+    "rgbid_tsdf_extract_normals": (vp, vp, u64),
+}
+ALIGN_SIGNATURES = {                    # rgbid_tsdf_align.h
+    "rgbid_tsdf_align": (vp, ci, vp, vp, ci, ci, f32, f32, cu, f32, f64, f64, cu, ci, vp, vp),
+    "rgbid_tsdf_align_timing": (vp, ci, vp),
+}
+SIGNATURES = {**VOLUME_SIGNATURES, **RAYCAST_SIGNATURES, **ALIGN_SIGNATURES}
+EXPORTS, RAYCAST_EXPORTS, ALIGN_EXPORTS = list(VOLUME_SIGNATURES), list(RAYCAST_SIGNATURES), list(ALIGN_SIGNATURES)
 STAGES = ("integrate", "scan", "emit")
 MAX_STEPS = 65536                       # RGBID_TSDF_MAX_STEPS: (z_max - z_min) / step at most
-RAYCAST_EXPORTS = ["rgbid_tsdf_pose_wc", "rgbid_tsdf_raycast", "rgbid_tsdf_raycast_timing", "rgbid_tsdf_extract_normals"]   # rgbid_tsdf_raycast.h
 RAYCAST_PLANES = ("depth", "normal", "colour")
-ALIGN_EXPORTS = ["rgbid_tsdf_align", "rgbid_tsdf_align_timing"]                                                                          # rgbid_tsdf_align.h
 ALIGN_STAGES = ("system", "solve")
 ALIGN_STATUS = ("running", "converged", "few", "singular")                                                                              # RGBID_TSDF_ALIGN_*
 ALIGN_STRIDES = (1, 2, 4, 8)
@@ -43,37 +64,16 @@ class View(C.Structure):
     _fields_ = [("pose", Pose), ("depthinv_dev", C.c_void_p), ("colour_dev", C.c_void_p)]
 
 
-def _integer(name, v):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-        raise ValueError(f"{name}: an integer, got {v!r}")
-    return int(v)
-
-
-def _float32(name, v):
-    try:
-        with np.errstate(over="ignore"):
-            f = float(np.float32(v))
-    except (TypeError, ValueError, OverflowError):
-        raise ValueError(f"{name}: a number, got {v!r}")
-    if not math.isfinite(f):
-        raise ValueError(f"{name} must be finite, got {v!r}")
-    return f
-
-
 def capacity_arg(max_voxels, max_views):
     """-> (max_voxels, max_views) of a handle: 8 .. 2^29 voxels and 1 .. 65 535 views per call (ValueError otherwise)"""
-    n, v = _integer("max_voxels", max_voxels), _integer("max_views", max_views)
-    if not 8 <= n <= MAX_VOXELS:
-        raise ValueError(f"max_voxels must lie in [8, 2^29], got {max_voxels!r}")
-    if not 1 <= v <= MAX_VIEWS:
-        raise ValueError(f"max_views must lie in [1, {MAX_VIEWS}], got {max_views!r}")
-    return n, v
+    n, v = A.integer("max_voxels", max_voxels), A.integer("max_views", max_views)
+    return A.in_range("max_voxels", n, 8, MAX_VOXELS, "[8, 2^29]", max_voxels), A.in_range("max_views", v, 1, MAX_VIEWS, f"[1, {MAX_VIEWS}]", max_views)
 
 
 def grid_arg(nx, ny, nz, origin, voxel, trunc, max_voxels=MAX_VOXELS):
     """-> (nx, ny, nz, origin, voxel, trunc) as the library takes them: dimensions >= 2 with nx ny nz <= max_voxels, origin three finite
     float32 values, voxel and trunc finite float32 values > 0 (ValueError otherwise)"""
-    dims = tuple(_integer(n, v) for n, v in zip(("nx", "ny", "nz"), (nx, ny, nz)))
+    dims = tuple(A.integer(n, v) for n, v in zip(("nx", "ny", "nz"), (nx, ny, nz)))
     if min(dims) < 2:
         raise ValueError(f"every dimension must be at least 2, got {dims}")
     if dims[0] * dims[1] * dims[2] > max_voxels:
@@ -84,8 +84,8 @@ def grid_arg(nx, ny, nz, origin, voxel, trunc, max_voxels=MAX_VOXELS):
         raise ValueError(f"origin: three numbers, got {origin!r}")
     if len(o) != 3:
         raise ValueError(f"origin: three numbers, got {origin!r}")
-    o = [_float32("origin", v) for v in o]
-    h, tr = _float32("voxel", voxel), _float32("trunc", trunc)
+    o = [A.finite32("origin", v) for v in o]
+    h, tr = A.finite32("voxel", voxel), A.finite32("trunc", trunc)
     if not (h > 0 and tr > 0):
         raise ValueError(f"voxel and trunc must be > 0, got {voxel!r}, {trunc!r}")
     return dims + (o, h, tr)
@@ -93,10 +93,7 @@ def grid_arg(nx, ny, nz, origin, voxel, trunc, max_voxels=MAX_VOXELS):
 
 def weight_arg(min_weight):
     """-> min_weight: an integer in 1 .. 65 535 (ValueError otherwise)"""
-    w = _integer("min_weight", min_weight)
-    if not 1 <= w <= MAX_WEIGHT:
-        raise ValueError(f"min_weight must lie in [1, {MAX_WEIGHT}], got {min_weight!r}")
-    return w
+    return A.integer_in("min_weight", min_weight, 1, MAX_WEIGHT, f"[1, {MAX_WEIGHT}]")
 
 
 def component_filter_arg(min_component, largest_components):
@@ -139,7 +136,7 @@ def step_arg(step, z_min, z_max):
     """-> the ray cast's sample spacing as the float32 value the library receives: finite, > 0 and with (z_max - z_min) / step <= 65 536
     for the gate's float32 values (ValueError otherwise)"""
     lo, hi = depth_range(z_min, z_max)
-    s = _float32("step", step)
+    s = A.finite32("step", step)
     if not s > 0:
         raise ValueError(f"step must be > 0, got {step!r}")
     if (hi - lo) / s > MAX_STEPS:
@@ -155,16 +152,6 @@ def raycast_outputs_arg(outputs):
     return outs
 
 
-def _float64(name, v):
-    try:
-        f = float(v)
-    except (TypeError, ValueError, OverflowError):
-        raise ValueError(f"{name}: a number, got {v!r}")
-    if isinstance(v, (bool, str)) or not math.isfinite(f):
-        raise ValueError(f"{name} must be a finite number, got {v!r}")
-    return f
-
-
 def align_levels_arg(levels):
     """-> the levels as a tuple of (stride, iterations): 1 .. 4 pairs, stride out of 1, 2, 4, 8, iterations >= 1 and at most 256 in all
     (ValueError otherwise)"""
@@ -174,7 +161,7 @@ def align_levels_arg(levels):
         raise ValueError(f"levels: pairs (stride, iterations), got {levels!r}")
     if not 1 <= len(lv) <= ALIGN_MAX_LEVELS or any(len(l) != 2 for l in lv):
         raise ValueError(f"levels: 1 .. {ALIGN_MAX_LEVELS} pairs (stride, iterations), got {levels!r}")
-    lv = tuple((_integer("stride", s), _integer("iterations", n)) for s, n in lv)
+    lv = tuple((A.integer("stride", s), A.integer("iterations", n)) for s, n in lv)
     if any(s not in ALIGN_STRIDES for s, _ in lv):
         raise ValueError(f"a stride must be one of {ALIGN_STRIDES}, got {levels!r}")
     if any(n < 1 for _, n in lv) or sum(n for _, n in lv) > ALIGN_MAX_ITERATIONS:
@@ -185,7 +172,7 @@ def align_levels_arg(levels):
 def align_params_arg(huber, damping, eps, min_pixels):
     """-> (huber, damping, eps, min_pixels) as the library takes them: huber a finite float32 > 0, damping finite and >= 0, eps finite and
     > 0, min_pixels an integer in 6 .. 2^32 - 1 (ValueError otherwise)"""
-    h, d, e, n = _float32("huber", huber), _float64("damping", damping), _float64("eps", eps), _integer("min_pixels", min_pixels)
+    h, d, e, n = A.finite32("huber", huber), A.finite64("damping", damping), A.finite64("eps", eps), A.integer("min_pixels", min_pixels)
     if not h > 0:
         raise ValueError(f"huber must be > 0, got {huber!r}")
     if not d >= 0:
@@ -215,7 +202,7 @@ def pose_wc(R, t):
     """the twelve float32 values R00 .. R22, tx, ty, tz of R_WC | t_WC as the library forms them from one world pose"""
     p = Pose((C.c_double * 9)(*np.asarray(R, np.float64).reshape(9)), (C.c_double * 3)(*np.asarray(t, np.float64).reshape(3)))
     out = (C.c_float * 12)()
-    check(_lib.lib().rgbid_tsdf_pose_wc(C.byref(p), out))
+    check(_lib.bind(SIGNATURES).rgbid_tsdf_pose_wc(C.byref(p), out))
     return np.array(out[:], np.float32)
 
 
@@ -242,12 +229,8 @@ def colours_arg(colours, views, rows, cols, device=None):
     if len(colours) != views:
         raise ValueError(f"{views} views need {views} colour planes, got {len(colours)}")
     for c in colours:
-        if c is None:
-            continue
-        if not (isinstance(c, torch.Tensor) and c.is_cuda and c.dtype == torch.uint8 and tuple(c.shape) == (rows, cols, 3) and c.is_contiguous()):
-            raise ValueError(f"colours: contiguous CUDA uint8 tensors [{rows}, {cols}, 3] or None")
-        if device is not None and c.device.index != device:
-            raise ValueError(f"colours must live on device {device}")
+        if c is not None:
+            A.cuda_tensor("colours", c, torch.uint8, (rows, cols, 3), f"colours: contiguous CUDA uint8 tensors [{rows}, {cols}, 3] or None", device)
     return colours
 
 
@@ -259,7 +242,7 @@ def bounds_grid(bounds, voxel, max_voxels=MAX_VOXELS):
         b = np.asarray(bounds, np.float64).reshape(-1)
     except (TypeError, ValueError):
         raise ValueError(f"bounds: x0 y0 z0 x1 y1 z1, got {bounds!r}")
-    h = _float32("voxel", voxel)
+    h = A.finite32("voxel", voxel)
     if b.shape != (6,) or not np.isfinite(b).all() or (b[3:] < b[:3]).any():
         raise ValueError(f"bounds: six finite numbers x0 y0 z0 x1 y1 z1 with x0 <= x1, y0 <= y1, z0 <= z1, got {bounds!r}")
     if not h > 0:
@@ -277,7 +260,7 @@ def bounds_grid(bounds, voxel, max_voxels=MAX_VOXELS):
 
 class Volume(_lib.CtxHandle):
     """A TSDF volume of up to max_voxels voxels that takes up to max_views views per integrate call, on the context's stream."""
-    _destroy = "rgbid_tsdf_destroy"
+    _destroy, _signatures, _timing, _stages = "rgbid_tsdf_destroy", SIGNATURES, "rgbid_tsdf_timing", STAGES
 
     def __init__(self, ctx, max_voxels, max_views, colour=True):
         self.max_voxels, self.max_views = capacity_arg(max_voxels, max_views)
@@ -285,32 +268,18 @@ class Volume(_lib.CtxHandle):
         self.colour = bool(colour)
         self.nx = self.ny = self.nz = 2
         self.origin, self.voxel, self.trunc = [0.0, 0.0, 0.0], 1.0, 1.0   # a new handle's shape (rgbid_tsdf_create)
-        L = self.L
-        L.rgbid_tsdf_create.argtypes = [C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_int, C.c_int]
-        L.rgbid_tsdf_configure.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_float]
-        L.rgbid_tsdf_reset.argtypes = [C.c_void_p]
-        L.rgbid_tsdf_integrate.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float]
-        L.rgbid_tsdf_get_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.rgbid_tsdf_set_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.rgbid_tsdf_extract_plan.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p]
-        L.rgbid_tsdf_extract_emit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_ulonglong]
-        L.rgbid_tsdf_timing.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        L.rgbid_tsdf_raycast.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_uint,
-                                         C.c_void_p, C.c_void_p, C.c_void_p]
-        L.rgbid_tsdf_raycast_timing.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        L.rgbid_tsdf_extract_normals.argtypes = [C.c_void_p, C.c_void_p, C.c_ulonglong]
-        L.rgbid_tsdf_align.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint, C.c_float,
-                                       C.c_double, C.c_double, C.c_uint, C.c_int, C.c_void_p, C.c_void_p]
-        L.rgbid_tsdf_align_timing.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        self._created(L.rgbid_tsdf_create(C.byref(self._h), ctx._h, C.c_ulonglong(self.max_voxels), self.max_views, int(self.colour)))
+        self._created(self.L.rgbid_tsdf_create(C.byref(self._h), ctx._h, C.c_ulonglong(self.max_voxels), self.max_views, int(self.colour)))
 
     @property
     def shape(self):
         return (self.nz, self.ny, self.nx)
 
-    @property
-    def _dev(self):
-        return f"cuda:{self.ctx.device}"
+    def _own_tensor(self, x, dtype, shape, what):
+        """-> x: a contiguous CUDA tensor of `dtype` and `shape` on the volume's device (ValueError(what, and the device) otherwise)"""
+        what += f" on device {self.ctx.device}"
+        if A.cuda_tensor(None, x, dtype, shape, what).device.index != self.ctx.device:
+            raise ValueError(what)
+        return x
 
     def configure(self, nx, ny, nz, origin, voxel, trunc):
         """the volume's shape (nx ny nz voxels of `voxel` metres, the centre of voxel (0, 0, 0) at `origin`, truncation `trunc` metres),
@@ -353,17 +322,12 @@ class Volume(_lib.CtxHandle):
 
     def set_state(self, D, counts, rgb_sum=None):
         """replace the state by CUDA tensors of state()'s shapes (counts and rgb_sum int32 or uint32 bits; None: zeros).  Synchronises."""
-        def plane(name, x, dtype_ok, shape):
-            if x is None:
-                return None
-            if not (isinstance(x, torch.Tensor) and x.is_cuda and dtype_ok(x) and tuple(x.shape) == shape and x.is_contiguous()
-                    and x.device.index == self.ctx.device):
-                raise ValueError(f"{name}: a contiguous CUDA tensor {list(shape)} of 4-byte elements on device {self.ctx.device}")
-            return x.data_ptr()
-        is_int = lambda x: x.element_size() == 4 and not x.is_floating_point()
-        d = plane("D", D, lambda x: x.dtype == torch.float32, self.shape)
-        c = plane("counts", counts, is_int, self.shape)
-        s = plane("rgb_sum", rgb_sum, is_int, (3,) + self.shape)
+        def plane(name, x, dtype, shape):
+            if x is not None:
+                return self._own_tensor(x, dtype, shape, f"{name}: a contiguous CUDA tensor {list(shape)} of 4-byte elements").data_ptr()
+        d = plane("D", D, torch.float32, self.shape)
+        c = plane("counts", counts, A.int4, self.shape)
+        s = plane("rgb_sum", rgb_sum, A.int4, (3,) + self.shape)
         if s is not None and not self.colour:
             raise ValueError("rgb_sum: the volume holds no colour")
         self.ctx.wait_torch_stream()
@@ -412,7 +376,7 @@ class Volume(_lib.CtxHandle):
     def emit_normals(self, normals):
         """write the last plan's vertex normals into a CUDA tensor [>= nv, 3] float32.  Asynchronous."""
         assert normals.is_cuda and normals.dtype == torch.float32 and normals.is_contiguous() and normals.dim() == 2 and normals.shape[1] == 3
-        check(self.L.rgbid_tsdf_extract_normals(self._h, C.c_void_p(normals.data_ptr() if normals.numel() else 0), C.c_ulonglong(normals.shape[0])))
+        check(self.L.rgbid_tsdf_extract_normals(self._h, self.ptr(normals), C.c_ulonglong(normals.shape[0])))
 
     def _raycast_args(self, R, t, K, rows, cols, step, min_weight, z_min, z_max):
         """the ray cast's arguments as the library takes them (ValueError for what it would refuse)"""
@@ -431,11 +395,10 @@ class Volume(_lib.CtxHandle):
         k = (C.c_float * 4)(*k)
         shapes = dict(depth=((V, rows, cols), torch.float32), normal=((V, 3, rows, cols), torch.float32), colour=((V, rows, cols, 3), torch.uint8))
         for name, x in (("depth", depth), ("normal", normal), ("colour", colour)):
-            if x is not None and not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == shapes[name][1] and tuple(x.shape) == shapes[name][0]
-                                      and x.is_contiguous() and x.device.index == self.ctx.device):
-                raise ValueError(f"{name}: a contiguous CUDA {shapes[name][1]} tensor {list(shapes[name][0])} on device {self.ctx.device}")
+            if x is not None:
+                self._own_tensor(x, shapes[name][1], shapes[name][0], f"{name}: a contiguous CUDA {shapes[name][1]} tensor {list(shapes[name][0])}")
         arr = (Pose * V)(*[Pose((C.c_double * 9)(*R[v].reshape(9)), (C.c_double * 3)(*t[v])) for v in range(V)])
-        ptr = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None
+        ptr = self.opt_ptr
         check(self.L.rgbid_tsdf_raycast(self._h, V, arr, k, rows, cols, C.c_float(lo), C.c_float(hi), C.c_float(s), w, ptr(depth), ptr(normal),
                                         ptr(colour)))
 
@@ -457,9 +420,7 @@ class Volume(_lib.CtxHandle):
 
     def raycast_timing(self, enable=True):
         """record HIP events around the following ray casts (the switch is `timing`'s); -> the device ms of the last one"""
-        ms = (C.c_float * 1)()
-        check(self.L.rgbid_tsdf_raycast_timing(self._h, int(enable), ms))
-        return float(ms[0])
+        return self._stage_ms("rgbid_tsdf_raycast_timing", ("raycast",), int(enable))["raycast"]
 
     def _align_args(self, R, t, K, rows, cols, levels, huber, damping, eps, min_pixels, min_weight, z_min, z_max):
         """the alignment's arguments as the library takes them (ValueError for what it would refuse)"""
@@ -507,9 +468,7 @@ class Volume(_lib.CtxHandle):
     def align_timing(self, enable=True):
         """record HIP events around every launch of the following alignments (the switch is `timing`'s); -> the device ms of the last
         call, summed over its launches {stage: ms}"""
-        ms = (C.c_float * 2)()
-        check(self.L.rgbid_tsdf_align_timing(self._h, int(enable), ms))
-        return dict(zip(ALIGN_STAGES, ms[:]))
+        return self._stage_ms("rgbid_tsdf_align_timing", ALIGN_STAGES, int(enable))
 
     def emit(self, vertices, colours, triangles):
         """write the last plan's mesh into CUDA tensors [>= nv, 3] float32, [>= nv, 3] uint8 or None, [>= nt, 3] int32.  Asynchronous."""
@@ -517,16 +476,9 @@ class Volume(_lib.CtxHandle):
         assert triangles.is_cuda and triangles.element_size() == 4 and triangles.is_contiguous() and triangles.dim() == 2 and triangles.shape[1] == 3
         if colours is not None:
             assert colours.is_cuda and colours.dtype == torch.uint8 and colours.is_contiguous() and tuple(colours.shape) == tuple(vertices.shape)
-        ptr = lambda x: C.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
+        ptr = self.opt_ptr
         check(self.L.rgbid_tsdf_extract_emit(self._h, ptr(vertices), ptr(colours), ptr(triangles), C.c_ulonglong(vertices.shape[0]),
                                              C.c_ulonglong(triangles.shape[0])))
-
-    def timing(self, enable=True):
-        """record HIP events around the stages of the following calls; -> the device ms of the last ones {stage: ms}"""
-        ms = (C.c_float * 3)()
-        check(self.L.rgbid_tsdf_timing(self._h, int(enable), ms))
-        return dict(zip(STAGES, ms[:]))
-
 
 def cloud_bounds(points, pad=0.0):
     """the bounding box x0 y0 z0 x1 y1 z1 of the finite records of a cloud (CUDA uint8 [M, 32]), padded by `pad` metres; None without one"""
@@ -558,7 +510,7 @@ def fuse(ctx, keyframes, K, rows, cols, bounds=None, voxel=0.02, trunc=None, min
     if not keyframes:
         raise ValueError("no keyframes to fuse")
     if bounds is None:
-        bounds = cloud_bounds(points, _float32("trunc", trunc)) if points is not None else None
+        bounds = cloud_bounds(points, A.finite32("trunc", trunc)) if points is not None else None
         if bounds is None:
             raise ValueError("bounds: needed without a cloud of finite points")
     nx, ny, nz, origin = bounds_grid(bounds, voxel, max_voxels)

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import check
+from ._lib import check, ci, cu, u64, vp
 from .cloud import records, records_out
 
 # rgbid_voxel_point: centroid, mean normal, member count, mean colour, flags (bit 0: some member is novel)
@@ -21,7 +21,14 @@ VOXEL_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"),
 assert VOXEL_DTYPE.itemsize == 32
 
 MAX_POINTS = 1 << 31
-EXPORTS = ["rgbid_voxel_create", "rgbid_voxel_destroy", "rgbid_voxel_plan", "rgbid_voxel_emit", "rgbid_voxel_timing"]
+SIGNATURES = {
+    "rgbid_voxel_create": (vp, vp, u64),
+    "rgbid_voxel_destroy": (vp,),
+    "rgbid_voxel_plan": (vp, vp, u64, vp, cu, vp, vp, vp),
+    "rgbid_voxel_emit": (vp, vp, u64),
+    "rgbid_voxel_timing": (vp, ci, vp),
+}
+EXPORTS = list(SIGNATURES)
 STAGES = ("box", "keys", "sort", "runs", "emit")
 
 
@@ -58,15 +65,11 @@ class Plan:
 
 class VoxelGrid(_lib.CtxHandle):
     """Voxel-grid filter for up to max_points input records per plan, on the context's stream."""
-    _destroy = "rgbid_voxel_destroy"
+    _destroy, _signatures, _timing, _stages = "rgbid_voxel_destroy", SIGNATURES, "rgbid_voxel_timing", STAGES
 
     def __init__(self, ctx, max_points):
         super().__init__(ctx)
         self.max_points = int(max_points)
-        self.L.rgbid_voxel_create.argtypes = [C.c_void_p, C.c_void_p, C.c_ulonglong]
-        self.L.rgbid_voxel_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]
-        self.L.rgbid_voxel_emit.argtypes = [C.c_void_p, C.c_void_p, C.c_ulonglong]
-        self.L.rgbid_voxel_timing.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         self._created(self.L.rgbid_voxel_create(C.byref(self._h), ctx._h, C.c_ulonglong(self.max_points)))
 
     def plan(self, points, leaf=0.01, min_points=0):
@@ -76,26 +79,20 @@ class VoxelGrid(_lib.CtxHandle):
         lf = (C.c_float * 3)(*leaf3(leaf))
         grid = np.zeros(6, np.int64); stats = np.zeros(3, np.uint64); nv = C.c_ulonglong()
         self.ctx.wait_torch_stream()
-        check(self.L.rgbid_voxel_plan(self._h, C.c_void_p(points.data_ptr() if points.numel() else 0), C.c_ulonglong(points.shape[0]), lf,
+        check(self.L.rgbid_voxel_plan(self._h, self.ptr(points), C.c_ulonglong(points.shape[0]), lf,
                                       C.c_uint(int(min_points)), grid.ctypes.data_as(C.c_void_p), stats.ctypes.data_as(C.c_void_p), C.byref(nv)))
         return Plan(nv.value, grid, stats)
 
     def emit(self, out):
         """write the voxels of the last plan into `out` (CUDA uint8 tensor [>= V, 32]).  Asynchronous on the context's stream."""
         records_out(out)
-        check(self.L.rgbid_voxel_emit(self._h, C.c_void_p(out.data_ptr() if out.numel() else 0), C.c_ulonglong(out.shape[0])))
-
-    def timing(self, enable=True):
-        """record HIP events around the stages of the following plans / emits; -> the device ms of the last ones {stage: ms}"""
-        ms = (C.c_float * 5)()
-        check(self.L.rgbid_voxel_timing(self._h, int(enable), ms))
-        return dict(zip(STAGES, ms[:]))
+        check(self.L.rgbid_voxel_emit(self._h, self.ptr(out), C.c_ulonglong(out.shape[0])))
 
     def build(self, points, leaf=0.01, min_points=0, return_plan=False):
         """-> CUDA uint8 [V, 32] of rgbid_voxel_point records (as_numpy gives the structured view); with return_plan, (voxels, Plan).
         `points` must stay unchanged until this returns (it synchronises)."""
         p = self.plan(points, leaf, min_points)
-        out = torch.empty((p.voxels, 32), dtype=torch.uint8, device=f"cuda:{self.ctx.device}")
+        out = torch.empty((p.voxels, 32), dtype=torch.uint8, device=self._dev)
         self.ctx.wait_torch_stream()   # the output is torch's allocation
         self.emit(out)
         self.ctx.sync()

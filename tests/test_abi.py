@@ -15,6 +15,112 @@ def _declared(header):
     return sorted(set(re.findall(r"\b(rgbid_[a-z0-9_]+)\s*\(", txt)))
 
 
+C_INTEGERS = {"int": (4, True), "int32_t": (4, True), "unsigned": (4, False), "unsigned int": (4, False), "uint32_t": (4, False),
+              "long long": (8, True), "int64_t": (8, True), "unsigned long long": (8, False), "uint64_t": (8, False), "size_t": (8, False)}
+
+
+def _prototypes(header):
+    """the `int rgbid_...(...);` prototypes of a C99 header -> {name: [class of each parameter]}: "pointer" (a pointer or an array),
+    ("integer", bytes, signed), "float", "double", "struct" (a typedef'd struct by value); a parameter of none of these is an error"""
+    txt = open(os.path.join(ROOT, "include", header)).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    txt = re.sub(r"^[ \t]*#.*$", "", txt, flags=re.M)
+    structs = set(re.findall(r"\}\s*(rgbid_\w+)\s*;", txt)) | set(re.findall(r"typedef\s+struct\s+\w+\s+(rgbid_\w+)\s*;", txt))
+    out = {}
+    for name, params in re.findall(r"\bint\s+(rgbid_\w+)\s*\(([^)]*)\)\s*;", txt):
+        classes = []
+        for p in [q.strip() for q in params.split(",")]:
+            if p == "void" and "," not in params:
+                continue
+            if "*" in p or "[" in p:
+                classes.append("pointer")
+                continue
+            kind = " ".join(w for w in p.split()[:-1] if w != "const")      # the last word is the parameter's name
+            if kind in C_INTEGERS:
+                classes.append(("integer",) + C_INTEGERS[kind])
+            elif kind in ("float", "double"):
+                classes.append(kind)
+            elif kind in structs or re.fullmatch(r"rgbid_\w+", kind):
+                classes.append("struct")
+            else:
+                raise AssertionError(f"{header}: {name}: cannot classify the parameter {p!r}")
+        out[name] = classes
+    return out
+
+
+def _ctype_class(t):
+    """the same classes for a ctypes type of a signature table"""
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, (ctypes._Pointer, ctypes.Array)):
+        return "pointer"
+    if issubclass(t, ctypes.Structure):
+        return "struct"
+    if t is ctypes.c_float or t is ctypes.c_double:
+        return "float" if t is ctypes.c_float else "double"
+    code = getattr(t, "_type_", None)
+    if isinstance(code, str) and code in "bhilqBHILQ":
+        return ("integer", ctypes.sizeof(t), code.islower())
+    raise AssertionError(f"cannot classify the ctypes type {t!r}")
+
+
+def _signature_mismatches(tables):
+    """every (function, parameter index, header's class, table's class) at which {function: tuple of ctypes} departs from the headers"""
+    declared = {}
+    for path in sorted(os.listdir(os.path.join(ROOT, "include"))):
+        if re.fullmatch(r"rgbid_\w+\.h", path):
+            declared.update(_prototypes(path))
+    bad = []
+    for name, types in tables.items():
+        if name not in declared:
+            bad.append((name, None, "no prototype", None))
+            continue
+        have = [_ctype_class(t) for t in types]
+        if len(have) != len(declared[name]):
+            bad.append((name, None, len(declared[name]), len(have)))
+        bad += [(name, i, want, got) for i, (want, got) in enumerate(zip(declared[name], have)) if want != got]
+    return bad
+
+
+def _handle_modules():
+    """the modules of the package that subclass CtxHandle, by name"""
+    import importlib
+    pkg = os.path.join(ROOT, "rgbid-slam_amd", "rgbid")
+    names = sorted(f[:-3] for f in os.listdir(pkg) if f.endswith(".py") and re.search(r"^class\s+\w+\(_lib\.CtxHandle\)", open(os.path.join(pkg, f)).read(), re.M))
+    return {n: importlib.import_module("rgbid." + n) for n in names}
+
+
+# the modules on the per-frame path or over other libraries: they keep their own bindings (they hold no signature table)
+OWN_BINDINGS = ["batched.py", "device.py", "dist.py", "engine.py", "host.py", "kfalign.py", "sequence.py"]
+
+
+def test_signature_tables_match_the_headers():
+    """every binding's table of C functions (SIGNATURES: name -> tuple of ctypes) has, for each function, as many parameters as the
+    prototype in include/rgbid_*.h and the prototype's class of each: a pointer, an integer of that width and signedness, float, double, a
+    struct by value.  A c_uint where the header says unsigned long long loads, passes every other CPU test and hands a kernel a wrong
+    count; here it fails.  EXPORTS is the table's names."""
+    mods = _handle_modules()
+    assert len(mods) >= 17, sorted(mods)
+    tables, without = {}, []
+    for name, mod in mods.items():
+        if not hasattr(mod, "SIGNATURES"):
+            without.append(name + ".py")
+            continue
+        exports = [n for k, v in vars(mod).items() if k.endswith("EXPORTS") for n in v]      # tsdf lists one per header
+        assert set(exports) == set(mod.SIGNATURES) and set(mod.EXPORTS) <= set(mod.SIGNATURES), name
+        assert all(isinstance(t, tuple) for t in mod.SIGNATURES.values()), name
+        tables.update(mod.SIGNATURES)
+    assert without == ["engine.py", "kfalign.py"] and set(without) <= set(OWN_BINDINGS), without
+    assert len(tables) >= 115, len(tables)
+    bad = _signature_mismatches(tables)
+    assert not bad, bad
+    # the guard bites: a 64-bit count declared as 32 bits, a dropped parameter and an unknown function are each reported
+    wrong = dict(tables)
+    wrong["rgbid_meshdist_create"] = tables["rgbid_meshdist_create"][:2] + (ctypes.c_uint,) + tables["rgbid_meshdist_create"][3:]
+    wrong["rgbid_mesh_timing"] = tables["rgbid_mesh_timing"][:-1]
+    wrong["rgbid_mesh_nothing"] = ()
+    assert set(_signature_mismatches(wrong)) == {("rgbid_meshdist_create", 2, ("integer", 8, False), ("integer", 4, False)), ("rgbid_mesh_timing", None, 3, 2),
+                                                 ("rgbid_mesh_nothing", None, "no prototype", None)}
+
+
 def test_library_exports_every_declared_symbol():
     _lib.build()
     L = ctypes.CDLL(_lib.LIB_PATH)
@@ -123,3 +229,19 @@ def test_handles_share_one_host_plumbing():
     pkg = os.path.join(ROOT, "rgbid-slam_amd", "rgbid")
     dels = sorted(f for f in os.listdir(pkg) if f.endswith(".py") and re.search(r"def\s+__del__", open(os.path.join(pkg, f)).read()))
     assert dels == ["_lib.py", "device.py", "host.py"], dels
+    # the Python side of a binding comes from rgbid/_args.py (checks) and rgbid/_lib.py (signature tables, handle helpers) alone
+    src = {f: open(os.path.join(pkg, f)).read() for f in sorted(os.listdir(pkg)) if f.endswith(".py")}
+    integer_tests = [f for f, text in src.items() if re.search(r"isinstance\(\w+, bool\) or not isinstance\(\w+, \(int, np\.integer\)\)", text)]
+    assert integer_tests == ["_args.py"], integer_tests
+    binders = [f for f, text in src.items() if re.search(r"\.argtypes\s*=", text)]
+    assert set(binders) <= {"_lib.py"} | set(OWN_BINDINGS) and "_lib.py" in binders, binders
+    features = {f[:-3] for f in src if not f.startswith("_") and f not in OWN_BINDINGS}      # those keep their private helpers to themselves and to tum.py
+    aliases = {f: dict(re.findall(r"^\s*from \. import (\w+) as (\w+)$", text, re.M)) for f, text in src.items()}
+    reach = []
+    for f, text in src.items():
+        names = {alias: mod for mod, alias in aliases[f].items() if mod in features}
+        names.update({m: m for m in re.findall(r"^\s*from \. import (\w+)$", text, re.M) if m in features})
+        reach += [(f, m.group(0)) for m in re.finditer(r"\b(\w+)\._[a-z]\w*", text) if names.get(m.group(1), f[:-3]) != f[:-3]]
+        reach += [(f, m.group(0)) for m in re.finditer(r"^\s*from \.(\w+) import (.*)$", text, re.M)
+                  if m.group(1) in features and re.search(r"(^|,\s*)_[a-z]", m.group(2))]
+    assert not reach, reach
