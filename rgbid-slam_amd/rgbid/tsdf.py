@@ -492,7 +492,7 @@ def cloud_bounds(points, pad=0.0):
 
 def fuse(ctx, keyframes, K, rows, cols, bounds=None, voxel=0.02, trunc=None, min_weight=1, z_min=0.05, z_max=20.0, max_voxels=1 << 27,
          points=None, return_volume=False, normals=False, keep_volume=False, min_component=None, largest_components=None, simplify=None,
-         smooth=None):
+         smooth=None, recolour=None, recolour_tolerance=None, recolour_measured=None):
     """one-shot over the keyframes of a run (ChunkCloud.keyframes with `depthinv` and, for a coloured mesh, `colour`): a volume over
     `bounds` = x0 y0 z0 x1 y1 z1 (None: the box of the cloud `points`, padded by trunc) with voxels of `voxel` metres, every keyframe
     integrated in order with its world pose, the surface extracted -> (vertices, colours, triangles) as CUDA tensors, with normals
@@ -501,8 +501,23 @@ def fuse(ctx, keyframes, K, rows, cols, bounds=None, voxel=0.02, trunc=None, min
     largest_components are Volume.extract's: with one of them the mesh loses its small connected components and the volume's figures
     gain `filter`, the components, vertices and triangles before and after.  simplify is Volume.extract's too: the mesh is decimated by
     vertex clustering with that cell and the volume's figures gain `simplify`.  smooth is Volume.extract's as well: the vertices are moved
-    by Taubin's filter last, the normals are those of the smoothed surface and the volume's figures gain `smooth`."""
+    by Taubin's filter last, the normals are those of the smoothed surface and the volume's figures gain `smooth`.  recolour = "mean" or
+    "best" replaces the colours of the mesh that is returned, after every other option, by what the keyframes show at full resolution
+    (rgbid.recolour.recolour_mesh, DESIGN.md section 27: every keyframe needs its `colour`): a keyframe colours a vertex where the mesh's
+    own depth at its pose agrees with the vertex's within recolour_tolerance metres (None: 2 voxel) and, with recolour_measured, where
+    its own `depthinv` agrees within that many metres; the mesh's normals weight the keyframes when it has them; a vertex no keyframe
+    sees keeps its colour; the volume's figures gain `recolour`: the vertices, those a keyframe coloured, the (vertex, keyframe) pairs
+    per class.  None leaves every byte as it is."""
     trunc = 4.0 * voxel if trunc is None else trunc
+    if recolour is not None:
+        from . import recolour as RC     # recolour imports raster, which needs nothing of this module
+        RC.mode_arg(recolour)
+        RC.keyframes_arg(keyframes, recolour_measured is not None)
+        recolour_tolerance = RC.tolerance_arg("recolour_tolerance", 2.0 * voxel if recolour_tolerance is None else recolour_tolerance)
+        if recolour_measured is not None:
+            RC.tolerance_arg("recolour_measured", recolour_measured)
+    elif recolour_tolerance is not None or recolour_measured is not None:
+        raise ValueError("recolour_tolerance and recolour_measured need recolour")
     w = weight_arg(min_weight)
     component_filter_arg(min_component, largest_components)
     simplify_arg(simplify)
@@ -527,6 +542,12 @@ def fuse(ctx, keyframes, K, rows, cols, bounds=None, voxel=0.02, trunc=None, min
         filtered = min_component is not None or largest_components is not None
         mesh = vol.extract(w, colours=True, normals=normals, min_component=min_component, largest_components=largest_components, simplify=simplify,
                            smooth=smooth)
+        if recolour is not None:
+            nrm = mesh[3] if normals else None
+            new_colours, used, pairs = RC.recolour_mesh(ctx, mesh[0], mesh[2], keyframes, K, rows, cols, nrm, mesh[1], recolour, recolour_tolerance,
+                                                        recolour_measured, z_min=z_min, z_max=z_max)
+            mesh = (mesh[0], new_colours) + tuple(mesh[2:])
+            recoloured = dict(mode=recolour, vertices=int(used.shape[0]), coloured=int((used != 0).sum().item()), **RC.counts_total(pairs))
         if return_volume:
             _, counts, _ = vol.state()
             mesh += (dict(nx=nx, ny=ny, nz=nz, origin=origin, voxels=nx * ny * nz, touched=int(((counts & 0xFFFF) != 0).sum().item())),)
@@ -536,6 +557,8 @@ def fuse(ctx, keyframes, K, rows, cols, bounds=None, voxel=0.02, trunc=None, min
                 mesh[-1]["simplify"] = vol.last_simplify
             if smooth is not None:
                 mesh[-1]["smooth"] = vol.last_smooth
+            if recolour is not None:
+                mesh[-1]["recolour"] = recoloured
         if keep_volume:
             mesh += (vol,)
             vol = None

@@ -132,6 +132,14 @@ def main():
                          "world frame) and the other way round")
     ap.add_argument("--mesh-reference-distance", type=float, default=None, metavar="D",
                     help="with --mesh-reference: the truncation distance in metres (default: the volume's truncation distance)")
+    ap.add_argument("--mesh-recolour", choices=("mean", "best"), default=None,
+                    help="with --mesh: recolour the vertices of the mesh that is written, after all clean-up options, from the keyframes that see "
+                         "them, sampled at full resolution (DESIGN.md section 27): the weighted mean of those keyframes, or the one that faces "
+                         "the vertex most")
+    ap.add_argument("--mesh-recolour-tolerance", type=float, default=None, metavar="M",
+                    help="with --mesh-recolour: metres between a vertex and the mesh's own depth in a keyframe for the keyframe to see it (default 2 H)")
+    ap.add_argument("--mesh-recolour-measured", type=float, default=None, metavar="M",
+                    help="with --mesh-recolour: also ask that the keyframe's own depth lies within M metres of the vertex")
     ap.add_argument("--mesh-align-check", action="store_true",
                     help="with --mesh: fuse the even-numbered keyframes, align the odd-numbered ones to that model (DESIGN.md section 21) and print "
                          "the corrections the alignment proposes; nothing is applied")
@@ -201,6 +209,10 @@ def main():
         ap.error("--mesh-render-step needs --mesh-render or --mesh-render-check")
     if not args.mesh and (args.mesh_raster or args.mesh_raster_check):
         ap.error("--mesh-raster / --mesh-raster-check need --mesh")
+    if not args.mesh and args.mesh_recolour is not None:
+        ap.error("--mesh-recolour needs --mesh")
+    if args.mesh_recolour is None and (args.mesh_recolour_tolerance is not None or args.mesh_recolour_measured is not None):
+        ap.error("--mesh-recolour-tolerance / --mesh-recolour-measured need --mesh-recolour")
     if not args.mesh and (args.mesh_align_check or args.mesh_align_iterations is not None):
         ap.error("--mesh-align-check / --mesh-align-iterations need --mesh")
     if args.mesh_align_iterations is not None and not args.mesh_align_check:
@@ -244,6 +256,13 @@ def main():
                 mesh_filter["smooth"] = TS.smooth_arg(dict(iterations=args.mesh_smooth, lam=0.5 if args.mesh_smooth_lambda is None else args.mesh_smooth_lambda,
                                                            mu=-0.53 if args.mesh_smooth_mu is None else args.mesh_smooth_mu,
                                                            pin_boundary=args.mesh_smooth_pin_boundary))
+            if args.mesh_recolour is not None:
+                from rgbid import recolour as RC
+                mesh_filter["recolour"] = args.mesh_recolour
+                if args.mesh_recolour_tolerance is not None:
+                    mesh_filter["recolour_tolerance"] = RC.tolerance_arg("--mesh-recolour-tolerance", args.mesh_recolour_tolerance)
+                if args.mesh_recolour_measured is not None:
+                    mesh_filter["recolour_measured"] = RC.tolerance_arg("--mesh-recolour-measured", args.mesh_recolour_measured)
             reference = None
             if args.mesh_deviation is not None or args.mesh_reference:
                 from rgbid import meshdist as MD
@@ -427,6 +446,10 @@ def main():
         if smo:
             print(f"rank {rank}: mesh smooth: {smo['iterations']} iterations of lambda {smo['lam']:g}, mu {smo['mu']:g}, {smo['edges']} edges, "
                   f"{smo['boundary_vertices']} boundary vertices, {'pinned' if smo['pin_boundary'] else 'not pinned'}")
+        rec = vol.get("recolour")
+        if rec:
+            print(f"rank {rank}: mesh recolour ({rec['mode']}): {rec['coloured']} of {rec['vertices']} vertices coloured from {len(pc.keyframes)} keyframes; pairs: "
+                  + ", ".join(f"{rec[k]} {k}" for k in ("gated", "outside", "hidden", "unmeasured", "averted", "taken")))
         if args.mesh_deviation is not None or args.mesh_reference:
             dev = lambda x: torch.from_numpy(np.ascontiguousarray(x.view(np.int32) if x.dtype == np.uint32 else x)).to(verts.device)
             try:
