@@ -169,9 +169,57 @@ def optimise(P, E, multilevel=True, iters=(10, 5, 10)):
     return P
 
 
+def stages(P, E):
+    """(stage id of rgbid_pg_envelope, active edges, fixed flags) of multilevel level 2, multilevel level 1 and the single level"""
+    fixed = fixed_vertices(len(P), E)
+    E2, E1 = E[E["type"] != SEQ_ODO], E[E["type"] == SEQ_ODO]
+    f1 = fixed.copy()
+    for ed in E2:
+        f1[int(ed["from"])] = f1[int(ed["to"])] = True
+    return [(0, E2, fixed), (1, E1, f1), (2, E, fixed)]
+
+
+def hessian(P, E, fixed):
+    """H over the free active vertices (gauss_newton's assembly) -> (H, free vertices)"""
+    nv = len(P)
+    act = np.zeros(nv, bool)
+    for ed in E:
+        act[int(ed["from"])] = act[int(ed["to"])] = True
+    free = [v for v in range(nv) if act[v] and not fixed[v]]
+    idx = {v: k for k, v in enumerate(free)}
+    H = np.zeros((6 * len(free), 6 * len(free)))
+    for ed in E:
+        _, Om, Ji, Jj = _terms(P, ed)
+        blocks = [(idx.get(int(ed["from"])), Ji), (idx.get(int(ed["to"])), Jj)]
+        for a, Ja in blocks:
+            for c, Jc in blocks:
+                if a is not None and c is not None:
+                    H[6 * a:6 * a + 6, 6 * c:6 * c + 6] += Ja.T @ Om @ Jc
+    return H, free
+
+
+def pose_err(a, b):
+    """max translation difference (m) and max rotation angle (rad) between two pose sets [V, 12]"""
+    dt = np.abs(a[:, 9:] - b[:, 9:]).max()
+    ang = 0.0
+    for x, y in zip(a, b):   # |deltaR(Ra^T Rb)| / 2 = sin(angle): exact at small angles, where arccos of the trace is not
+        ang = max(ang, float(np.linalg.norm(deltaR(x[:9].reshape(3, 3).T @ y[:9].reshape(3, 3)))) / 2)
+    return dt, ang
+
+
 # ---- synthetic graphs ----
 def rand_rot(r, scale):
     return exp(np.concatenate([np.zeros(3), r.normal(0, scale, 3)]))[0]
+
+
+def comb(ns):
+    """vertex 0 (fixed) and separators 2, 4, .., 2 ns, each tied to vertex 0 and to the separator before it"""
+    from rgbid import posegraph as PG
+    n = 2 * ns + 2
+    rr = np.random.default_rng(ns)
+    rows = [(0, k, SEQ_KF, rand_rot(rr, 0.01), rr.normal(0, 0.01, 3), np.eye(6) * 1e-4) for k in range(2, 2 * ns + 1, 2)]
+    rows += [(k - 2, k, SEQ_KF, rand_rot(rr, 0.01), rr.normal(0, 0.01, 3), np.eye(6) * 1e-4) for k in range(4, 2 * ns + 1, 2)]
+    return np.tile(np.concatenate([np.eye(3).reshape(9), np.zeros(3)]), (n, 1)), PG.edges(rows)
 
 
 def make_graph(r, T, K=6, L=2, lost=(), drift=0.01, noise=1e-3, loops_to_start=False):

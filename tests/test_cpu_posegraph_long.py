@@ -11,6 +11,7 @@ import pytest
 from rgbid import _lib
 from rgbid import posegraph as PG
 from tests import pg_mirror as M
+from tests.pg_mirror import hessian as _mirror_H, stages as _stages
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -33,35 +34,6 @@ def test_library_exports_set_limits():
     L = ctypes.CDLL(_lib.LIB_PATH)
     assert hasattr(L, "rgbid_pg_set_limits") and hasattr(L, "rgbid_pg_envelope")
     assert PG.MAX_SEPARATORS == 256 and hasattr(PG.PoseGraph, "set_limits")
-
-
-def _mirror_H(P, E, fixed):
-    """the mirror's H over the free active vertices (gauss_newton's assembly) -> (H, free vertices)"""
-    nv = len(P)
-    act = np.zeros(nv, bool)
-    for ed in E:
-        act[int(ed["from"])] = act[int(ed["to"])] = True
-    free = [v for v in range(nv) if act[v] and not fixed[v]]
-    idx = {v: k for k, v in enumerate(free)}
-    H = np.zeros((6 * len(free), 6 * len(free)))
-    for ed in E:
-        _, Om, Ji, Jj = M._terms(P, ed)
-        blocks = [(idx.get(int(ed["from"])), Ji), (idx.get(int(ed["to"])), Jj)]
-        for a, Ja in blocks:
-            for c, Jc in blocks:
-                if a is not None and c is not None:
-                    H[6 * a:6 * a + 6, 6 * c:6 * c + 6] += Ja.T @ Om @ Jc
-    return H, free
-
-
-def _stages(P, E):
-    """(stage id, active edges, fixed flags) of the three stages"""
-    fixed = M.fixed_vertices(len(P), E)
-    E2, E1 = E[E["type"] != PG.SEQ_ODO], E[E["type"] == PG.SEQ_ODO]
-    f1 = fixed.copy()
-    for ed in E2:
-        f1[int(ed["from"])] = f1[int(ed["to"])] = True
-    return [(0, E2, fixed), (1, E1, f1), (2, E, fixed)]
 
 
 @pytest.mark.parametrize("seed", [0, 1, 2, 3])

@@ -5,17 +5,9 @@ import pytest
 from rgbid import posegraph as PG
 from rgbid._lib import RgbidError
 from tests import pg_mirror as M
+from tests.pg_mirror import comb as _comb, pose_err as _pose_err
 
 pytestmark = pytest.mark.gpu
-
-
-def _pose_err(a, b):
-    """max translation difference (m) and max rotation angle (rad) between two pose sets [V, 12]"""
-    dt = np.abs(a[:, 9:] - b[:, 9:]).max()
-    ang = 0.0
-    for x, y in zip(a, b):   # |deltaR(Ra^T Rb)| / 2 = sin(angle): exact at small angles, where arccos of the trace is not
-        ang = max(ang, float(np.linalg.norm(M.deltaR(x[:9].reshape(3, 3).T @ y[:9].reshape(3, 3)))) / 2)
-    return dt, ang
 
 
 def _batch(seed, n):
@@ -136,12 +128,7 @@ def test_refusals_and_numerical_failure(ctx):
                 pg.optimise([(P, bad)], multilevel=ml)
         # exactly RGBID_PG_MAX_SEPARATORS separators are solved (the reduced right-hand side fills its LDS vector), one more is refused
         for ns, ok in ((PG.MAX_SEPARATORS, True), (PG.MAX_SEPARATORS + 1, False)):
-            n = 2 * ns + 2                      # vertex 0 (fixed) and separators 2, 4, .., 2 ns
-            rr = np.random.default_rng(ns)
-            rows = [(0, k, PG.SEQ_KF, M.rand_rot(rr, 0.01), rr.normal(0, 0.01, 3), np.eye(6) * 1e-4) for k in range(2, 2 * ns + 1, 2)]
-            rows += [(k - 2, k, PG.SEQ_KF, M.rand_rot(rr, 0.01), rr.normal(0, 0.01, 3), np.eye(6) * 1e-4) for k in range(4, 2 * ns + 1, 2)]
-            many = PG.edges(rows)
-            Pm = np.tile(np.concatenate([np.eye(3).reshape(9), np.zeros(3)]), (n, 1))
+            Pm, many = _comb(ns)                # vertex 0 (fixed) and separators 2, 4, .., 2 ns
             if ok:
                 out, status, _ = pg.optimise([(Pm, many)], multilevel=True, iters=(2, 0, 0))
                 ref = M.optimise(Pm, many, multilevel=True, iters=(2, 0, 0))

@@ -6,19 +6,11 @@ import pytest
 from rgbid import posegraph as PG
 from rgbid._lib import RgbidError
 from tests import pg_mirror as M
+from tests.pg_mirror import comb as _comb, pose_err as _pose_err
 
 pytestmark = pytest.mark.gpu
 
 E_INVALID = -1
-
-
-def _pose_err(a, b):
-    """max translation difference (m) and max rotation angle (rad) between two pose sets [V, 12]"""
-    dt = np.abs(a[:, 9:] - b[:, 9:]).max()
-    ang = 0.0
-    for x, y in zip(a, b):   # |deltaR(Ra^T Rb)| / 2 = sin(angle): exact at small angles, where arccos of the trace is not
-        ang = max(ang, float(np.linalg.norm(M.deltaR(x[:9].reshape(3, 3).T @ y[:9].reshape(3, 3)))) / 2)
-    return dt, ang
 
 
 def _batch(seed, n):
@@ -29,15 +21,6 @@ def _batch(seed, n):
         lost = tuple(int(x) for x in r.integers(1, T, size=int(r.integers(0, 3))))
         graphs.append(M.make_graph(r, T, K=int(r.integers(2, 12)), L=int(r.integers(0, 4)), lost=lost, drift=0.005, noise=1e-4)[:2])
     return graphs
-
-
-def _comb(ns):
-    """vertex 0 (fixed) and separators 2, 4, .., 2 ns, each tied to vertex 0 and to the separator before it"""
-    n = 2 * ns + 2
-    rr = np.random.default_rng(ns)
-    rows = [(0, k, PG.SEQ_KF, M.rand_rot(rr, 0.01), rr.normal(0, 0.01, 3), np.eye(6) * 1e-4) for k in range(2, 2 * ns + 1, 2)]
-    rows += [(k - 2, k, PG.SEQ_KF, M.rand_rot(rr, 0.01), rr.normal(0, 0.01, 3), np.eye(6) * 1e-4) for k in range(4, 2 * ns + 1, 2)]
-    return np.tile(np.concatenate([np.eye(3).reshape(9), np.zeros(3)]), (n, 1)), PG.edges(rows)
 
 
 def _separators(P, E, stage):
