@@ -25,7 +25,8 @@
  *              the host, 0 when n_w is 0 or N (DBoW2's IDF in Q16.16; the only floating-point step).  Nodes that are no leaves carry 0.
  *  transform   every descriptor descends from the root to a word by the nearest child.  A keyframe's vector lists its distinct words in
  *              ascending order; with c_w descriptors in word w, a_w = c_w * W_w and A = sum a_w (uint64), the entry's value is
- *              v_w = (uint32) ((a_w << 30) / A); entries of value 0 stay.  A = 0 gives an empty vector.
+ *              v_w = (uint32) ((a_w << 30) / A); entries of value 0 stay.  A = 0 gives an empty vector.  c_w <= RGBID_LOOPFEAT_MAX_KEYPOINTS
+ *              = 1 536 and W_w <= RGBID_BOW_MAX_WEIGHT give a_w < 2^31, so a_w << 30 stays inside 64 bits.
  *  score       S(q, c) = sum over the common words of min(v_q, v_c) in uint64: DBoW2's L1 score 1 - 0.5 sum |v - w| of L1-normalised
  *              vectors, scaled by 2^30.
  *  shortlist   for query q the candidates c <= q - min_separation with S(q, c) > 0, the T largest by (S descending, c descending).
@@ -46,6 +47,9 @@ extern "C" {
 #define RGBID_BOW_MAX_LEAVES (1 << 20)
 #define RGBID_BOW_MAX_ITERS 64
 #define RGBID_BOW_MAX_SHORTLIST 64        /* a wave keeps its best candidates one per lane */
+/* the largest weight: a batch holds at most 65 535 keyframes, so W_w <= floor(log(65535 / 1) * 65536 + 0.5) = 726 816 (N = 65 535, n_w = 1).
+ * 1 536 * 726 816 = 1 116 389 376 < 2^31 is what the transform's a_w << 30 rests on; rgbid_bow_import refuses anything larger. */
+#define RGBID_BOW_MAX_WEIGHT 726816
 
 /* one entry of a keyframe's vector, 8 bytes */
 typedef struct rgbid_bow_entry {
@@ -62,19 +66,22 @@ int rgbid_bow_destroy(rgbid_bow* v);
 /* most nodes a tree of (k, depth) can have: sum of k^l, l = 0 .. depth; RGBID_E_INVALID outside the limits.  Needs no device. */
 int rgbid_bow_max_nodes(int k, int depth, int32_t* nodes);
 /* train on the descriptors of n_kf keyframes kps_dev [n_kf][max_keypoints], counts_dev [n_kf] (1 <= max_keypoints <=
- * RGBID_LOOPFEAT_MAX_KEYPOINTS, 1 <= iters <= RGBID_BOW_MAX_ITERS), then set the weights from the same keyframes.  Scratch is allocated for
- * the batch on first use and grown on demand; the final step (the weights) waits for the stream. */
+ * RGBID_LOOPFEAT_MAX_KEYPOINTS, 1 <= iters <= RGBID_BOW_MAX_ITERS), then set the weights from the same keyframes.  Here and wherever a call
+ * takes counts_dev, a count below 0 reads as 0 and one above max_keypoints as max_keypoints.  Scratch is allocated for the batch on first use
+ * and grown on demand; the final step (the weights) waits for the stream. */
 int rgbid_bow_train(rgbid_bow* v, const rgbid_loopfeat_kp* kps_dev, const int32_t* counts_dev, int n_kf, int max_keypoints, int iters);
-/* recompute the weights from another set of keyframes (N = n_kf; n_kf = 0 zeroes them).  Waits for the stream. */
+/* recompute the weights from another set of keyframes (N = n_kf; n_kf = 0 zeroes them; counts_dev clamped to 0 .. max_keypoints as in
+ * rgbid_bow_train).  Waits for the stream. */
 int rgbid_bow_set_weights(rgbid_bow* v, const rgbid_loopfeat_kp* kps_dev, const int32_t* counts_dev, int n_kf, int max_keypoints);
 /* the tree to host buffers (each optional): *nodes; centroids [nodes][32]; children [nodes][2] = first child, number of children (0, 0 for a
  * leaf); weights [nodes].  Waits for the stream.  Call it once for *nodes, then with buffers of that size. */
 int rgbid_bow_export(rgbid_bow* v, int32_t* nodes, uint8_t* centroids, int32_t* children, uint32_t* weights);
-/* the reverse: a tree in the numbering above that fits this handle's k and depth; anything else is RGBID_E_INVALID and leaves the
- * vocabulary as it was. */
+/* the reverse: a tree in the numbering above that fits this handle's k and depth, with no weight above RGBID_BOW_MAX_WEIGHT; anything else
+ * is RGBID_E_INVALID and leaves the vocabulary as it was. */
 int rgbid_bow_import(rgbid_bow* v, int32_t nodes, const uint8_t* centroids, const int32_t* children, const uint32_t* weights);
 /* vectors of n_kf keyframes: bow_dev [n_kf][max_keypoints] entries (unused ones zeroed), bow_counts_dev [n_kf]; words_dev [n_kf][max_keypoints]
- * (optional) receives the word of every descriptor, -1 in unused slots.  Asynchronous. */
+ * (optional) receives the word of every descriptor, -1 in unused slots; counts_dev clamped to 0 .. max_keypoints as in rgbid_bow_train.
+ * Asynchronous. */
 int rgbid_bow_transform(rgbid_bow* v, const rgbid_loopfeat_kp* kps_dev, const int32_t* counts_dev, int n_kf, int max_keypoints,
                         int32_t* words_dev, rgbid_bow_entry* bow_dev, int32_t* bow_counts_dev);
 /* scores_dev [n_pairs] = S(q, c) of pairs_dev [n_pairs][2]; a pair naming a keyframe outside 0 .. n_kf - 1 scores 0.  Asynchronous. */

@@ -43,6 +43,7 @@ constexpr int VCHUNK = 64;                // descriptors a vote block walks
 constexpr int SORTN = 2048;               // >= RGBID_LOOPFEAT_MAX_KEYPOINTS, a power of two
 constexpr int NO_CHILD = 0xFF;
 static_assert(SORTN >= RGBID_LOOPFEAT_MAX_KEYPOINTS, "a keyframe's words are sorted in LDS");
+static_assert((u64)RGBID_LOOPFEAT_MAX_KEYPOINTS * RGBID_BOW_MAX_WEIGHT < (1ull << 31), "a_w = c_w * W_w < 2^31: a_w << 30 stays inside 64 bits");
 
 // what the training kernels share: the tree, the per-node, per-slot and per-row state
 struct BowTrain {
@@ -658,6 +659,9 @@ int rgbid_bow_import(rgbid_bow* v, int32_t nodes, const uint8_t* centroids, cons
     next += cnt;
   }
   if (next != nodes) return RGBID_E_INVALID;
+  // the transform's a_w = c_w * W_w stays below 2^31 (and a_w << 30 inside 64 bits) only for weights training can produce
+  for (int i = 0; i < nodes; ++i)
+    if (weights[i] > RGBID_BOW_MAX_WEIGHT) return RGBID_E_INVALID;
   (void)hipSetDevice(v->ctx->device);
   RGBID_HIP(hipStreamSynchronize(v->ctx->stream));
   RGBID_HIP(hipMemcpy(v->cent, centroids, 32 * (size_t)nodes, hipMemcpyHostToDevice));

@@ -18,6 +18,7 @@ from ._lib import check, ci, vp
 ENTRY_DTYPE = np.dtype([("word", "<u4"), ("value", "<u4")])
 assert ENTRY_DTYPE.itemsize == 8
 MAX_K, MAX_DEPTH, MAX_LEAVES, MAX_ITERS, MAX_SHORTLIST = 16, 6, 1 << 20, 64, 64
+MAX_WEIGHT = 726816            # RGBID_BOW_MAX_WEIGHT: the largest weight training can produce; import_ refuses a larger one
 ONE = 1 << 30                  # what the values of a vector sum to (at most)
 SIGNATURES = {
     "rgbid_bow_create": (vp, vp, ci, ci),
@@ -98,7 +99,8 @@ class Vocabulary(_lib.CtxHandle):
         return dict(k=self.k, depth=self.depth, centroids=cen, children=ch, weights=w)
 
     def import_(self, centroids, children, weights):
-        """the reverse of export; RgbidError for a tree that is not numbered as include/rgbid_bow.h says or does not fit k and depth"""
+        """the reverse of export; RgbidError for a tree that is not numbered as include/rgbid_bow.h says, does not fit k and depth or holds a
+        weight above MAX_WEIGHT"""
         cen = np.ascontiguousarray(centroids, np.uint8).reshape(-1, 32)
         ch = np.ascontiguousarray(children, np.int32).reshape(-1, 2)
         w = np.ascontiguousarray(weights, np.uint32).reshape(-1)

@@ -10,38 +10,10 @@ from rgbid import _lib
 from rgbid import bow as BW
 from rgbid import loopfeat as LF
 from tests import bow_mirror as M
+from tests.bow_cases import chunks, clustered, feats_of, uniform
 
 pytestmark = pytest.mark.gpu
 MAXKP = 1000
-
-
-def feats_of(per_kf, max_kp=MAXKP, seed=1):
-    """descriptor arrays [c_i, 32] per keyframe -> loopfeat.Features; the unused slots hold random descriptors that nothing may read"""
-    r = np.random.default_rng(seed)
-    n = len(per_kf)
-    kp = np.zeros((n, max_kp), LF.KP_DTYPE)
-    kp["desc"] = r.integers(0, 256, (n, max_kp, 32), dtype=np.uint8)
-    counts = np.zeros(n, np.int32)
-    for i, d in enumerate(per_kf):
-        kp["desc"][i, :len(d)] = d
-        counts[i] = len(d)
-    raw = np.ascontiguousarray(kp).view(np.uint8).reshape(n, max_kp, 120)
-    return LF.Features(torch.from_numpy(raw).cuda(), torch.from_numpy(counts).cuda())
-
-
-def chunks(desc, size=MAXKP):
-    return [desc[s:s + size] for s in range(0, len(desc), size)]
-
-
-def uniform(r, n):
-    return r.integers(0, 256, (n, 32), dtype=np.uint8)
-
-
-def clustered(r, n, prototypes=50, flip=0.1):
-    """n descriptors around `prototypes` random ones, each bit flipped with probability `flip`"""
-    proto = np.unpackbits(uniform(r, prototypes), axis=1, bitorder="little")
-    b = proto[r.integers(0, prototypes, n)] ^ (r.random((n, 256)) < flip).astype(np.uint8)
-    return np.packbits(b, axis=1, bitorder="little")
 
 
 def trained(ctx, k, depth, per_kf, iters=10, max_kp=MAXKP):
