@@ -132,6 +132,9 @@ def main():
                          "world frame) and the other way round")
     ap.add_argument("--mesh-reference-distance", type=float, default=None, metavar="D",
                     help="with --mesh-reference: the truncation distance in metres (default: the volume's truncation distance)")
+    ap.add_argument("--mesh-reference-register", action="store_true",
+                    help="with --mesh-reference: first register the written mesh to MODEL.ply by point-to-plane ICP from the identity (DESIGN.md "
+                         "section 28), print the pose and the status, and print the distances before and after; the written file is not moved")
     ap.add_argument("--mesh-recolour", choices=("mean", "best"), default=None,
                     help="with --mesh: recolour the vertices of the mesh that is written, after all clean-up options, from the keyframes that see "
                          "them, sampled at full resolution (DESIGN.md section 27): the weighted mean of those keyframes, or the one that faces "
@@ -229,6 +232,8 @@ def main():
         ap.error("--mesh-deviation / --mesh-reference / --mesh-reference-distance need --mesh")
     if args.mesh_reference_distance is not None and not args.mesh_reference:
         ap.error("--mesh-reference-distance needs --mesh-reference")
+    if args.mesh_reference_register and not args.mesh_reference:
+        ap.error("--mesh-reference-register needs --mesh-reference")
     if args.mesh_deviation is not None and (args.mesh_min_component is None and args.mesh_largest_components is None and args.mesh_simplify is None
                                             and args.mesh_smooth is None):
         ap.error("--mesh-deviation needs at least one of --mesh-min-component / --mesh-largest-components / --mesh-simplify / --mesh-smooth")
@@ -458,7 +463,16 @@ def main():
                     figures = MD.mesh_deviation(ctx, verts, tris, raw[0], raw[2], args.mesh_deviation)
                     print(f"rank {rank}: mesh deviation: written -> extracted: {MD.summary_line(figures['a_to_b'])}")
                     print(f"rank {rank}: mesh deviation: extracted -> written: {MD.summary_line(figures['b_to_a'])}")
-                if reference is not None:
+                if reference is not None and args.mesh_reference_register:
+                    from rgbid import meshreg as MR
+                    reg = MR.register_mesh(ctx, verts, tris, dev(reference[0]), dev(reference[2]), reference_distance)
+                    for line in MR.pose_lines(reg):
+                        print(f"rank {rank}: mesh reference: {line}")
+                    for word, figures in (("before", reg["before"]), ("after", reg["after"])):
+                        if figures is not None:
+                            print(f"rank {rank}: mesh reference ({word}): written -> {args.mesh_reference}: {MD.summary_line(figures['a_to_b'])}")
+                            print(f"rank {rank}: mesh reference ({word}): {args.mesh_reference} -> written: {MD.summary_line(figures['b_to_a'])}")
+                elif reference is not None:
                     figures = MD.mesh_deviation(ctx, verts, tris, dev(reference[0]), dev(reference[2]), reference_distance)
                     print(f"rank {rank}: mesh reference: written -> {args.mesh_reference}: {MD.summary_line(figures['a_to_b'])}")
                     print(f"rank {rank}: mesh reference: {args.mesh_reference} -> written: {MD.summary_line(figures['b_to_a'])}")
