@@ -143,6 +143,17 @@ def main():
                     help="with --mesh-recolour: metres between a vertex and the mesh's own depth in a keyframe for the keyframe to see it (default 2 H)")
     ap.add_argument("--mesh-recolour-measured", type=float, default=None, metavar="M",
                     help="with --mesh-recolour: also ask that the keyframe's own depth lies within M metres of the vertex")
+    ap.add_argument("--mesh-texture", default="", metavar="OUT.obj",
+                    help="with --mesh: also write the mesh that is written, after all clean-up options, as OUT.obj with OUT.mtl and the texture "
+                         "atlas OUT.png: every triangle gets a patch of an image baked from the keyframes that see it, sampled at full "
+                         "resolution (DESIGN.md section 29); texels no keyframe sees are filled from the vertex colours")
+    ap.add_argument("--mesh-texture-patch", type=int, default=None, metavar="N", help="with --mesh-texture: texels along a leg of a triangle's patch (2 .. 30, default 6)")
+    ap.add_argument("--mesh-texture-mode", choices=("mean", "best"), default=None,
+                    help="with --mesh-texture: the weighted mean of the keyframes that see a texel (the default), or the one that faces it most")
+    ap.add_argument("--mesh-texture-tolerance", type=float, default=None, metavar="M",
+                    help="with --mesh-texture: metres between a texel and the mesh's own depth in a keyframe for the keyframe to see it (default 2 H)")
+    ap.add_argument("--mesh-texture-measured", type=float, default=None, metavar="M",
+                    help="with --mesh-texture: also ask that the keyframe's own depth lies within M metres of the texel")
     ap.add_argument("--mesh-align-check", action="store_true",
                     help="with --mesh: fuse the even-numbered keyframes, align the odd-numbered ones to that model (DESIGN.md section 21) and print "
                          "the corrections the alignment proposes; nothing is applied")
@@ -216,6 +227,11 @@ def main():
         ap.error("--mesh-recolour needs --mesh")
     if args.mesh_recolour is None and (args.mesh_recolour_tolerance is not None or args.mesh_recolour_measured is not None):
         ap.error("--mesh-recolour-tolerance / --mesh-recolour-measured need --mesh-recolour")
+    if not args.mesh and args.mesh_texture:
+        ap.error("--mesh-texture needs --mesh")
+    if not args.mesh_texture and (args.mesh_texture_patch is not None or args.mesh_texture_mode is not None or args.mesh_texture_tolerance is not None
+                                  or args.mesh_texture_measured is not None):
+        ap.error("--mesh-texture-patch / --mesh-texture-mode / --mesh-texture-tolerance / --mesh-texture-measured need --mesh-texture")
     if not args.mesh and (args.mesh_align_check or args.mesh_align_iterations is not None):
         ap.error("--mesh-align-check / --mesh-align-iterations need --mesh")
     if args.mesh_align_iterations is not None and not args.mesh_align_check:
@@ -268,6 +284,16 @@ def main():
                     mesh_filter["recolour_tolerance"] = RC.tolerance_arg("--mesh-recolour-tolerance", args.mesh_recolour_tolerance)
                 if args.mesh_recolour_measured is not None:
                     mesh_filter["recolour_measured"] = RC.tolerance_arg("--mesh-recolour-measured", args.mesh_recolour_measured)
+            texture = None
+            if args.mesh_texture:
+                from rgbid import recolour as RC
+                from rgbid import texture as TX
+                TX.obj_paths(args.mesh_texture)
+                texture = dict(patch=TX.patch_arg(6 if args.mesh_texture_patch is None else args.mesh_texture_patch), mode=args.mesh_texture_mode or "mean",
+                               surface_tolerance=RC.tolerance_arg("--mesh-texture-tolerance", 2.0 * mesh["voxel"] if args.mesh_texture_tolerance is None
+                                                                  else args.mesh_texture_tolerance))
+                if args.mesh_texture_measured is not None:
+                    texture["measured_tolerance"] = RC.tolerance_arg("--mesh-texture-measured", args.mesh_texture_measured)
             reference = None
             if args.mesh_deviation is not None or args.mesh_reference:
                 from rgbid import meshdist as MD
@@ -455,6 +481,21 @@ def main():
         if rec:
             print(f"rank {rank}: mesh recolour ({rec['mode']}): {rec['coloured']} of {rec['vertices']} vertices coloured from {len(pc.keyframes)} keyframes; pairs: "
                   + ", ".join(f"{rec[k]} {k}" for k in ("gated", "outside", "hidden", "unmeasured", "averted", "taken")))
+        if texture is not None:
+            obj = args.mesh_texture
+            if world > 1:
+                root, ext = os.path.splitext(obj)
+                obj = f"{root}.rank{rank}{ext}"
+            nrm = fused[3] if args.mesh_normals else None
+            try:
+                tex = TX.texture_mesh(ctx, verts, tris, pc.keyframes, tuple(args.K), args.rows, args.cols, normals=nrm, colours=cols, **texture)
+                TX.write_obj(obj, verts, tris, tex["uv"], tex["atlas"], nrm)
+            except ValueError as e:
+                sys.exit(f"rank {rank}: --mesh-texture: {e}")
+            lay, total = tex["layout"], RC.counts_total(tex["counts"])
+            print(f"rank {rank}: mesh texture ({texture['mode']}): {tris.shape[0]} triangles, patch {texture['patch']}, atlas {lay['W']} x {lay['H']}, "
+                  f"{tex['textured']} of {tex['texels']} texels textured from {len(pc.keyframes)} keyframes, {tex['fallback']} from the vertex colours; pairs: "
+                  + ", ".join(f"{total[k]} {k}" for k in RC.COUNTS) + f" -> {obj}")
         if args.mesh_deviation is not None or args.mesh_reference:
             dev = lambda x: torch.from_numpy(np.ascontiguousarray(x.view(np.int32) if x.dtype == np.uint32 else x)).to(verts.device)
             try:
