@@ -102,6 +102,11 @@ def main():
     ap.add_argument("--mesh-simplify", type=float, default=None, metavar="CELL",
                     help="with --mesh: decimate the mesh by vertex clustering with cells of CELL metres (DESIGN.md section 23); after the "
                          "component options when both are given")
+    ap.add_argument("--mesh-fill-holes", type=int, default=None, metavar="N",
+                    help="with --mesh: close the loops of at most N boundary edges by a fan around a new vertex each (DESIGN.md section 30), "
+                         "after the component and simplify options and before --mesh-smooth")
+    ap.add_argument("--mesh-fill-any-facing", action="store_true",
+                    help="with --mesh-fill-holes: also close the loops whose cap would face against their rim's triangles (the outer edges of fragments)")
     ap.add_argument("--mesh-smooth", type=int, default=None, metavar="N",
                     help="with --mesh: move the vertices by N iterations of Taubin's filter (DESIGN.md section 24), after the component and "
                          "simplify options; with --mesh-normals the normals are those of the smoothed surface")
@@ -240,6 +245,10 @@ def main():
         ap.error("--mesh-min-component / --mesh-largest-components need --mesh")
     if not args.mesh and args.mesh_simplify is not None:
         ap.error("--mesh-simplify needs --mesh")
+    if not args.mesh and args.mesh_fill_holes is not None:
+        ap.error("--mesh-fill-holes needs --mesh")
+    if args.mesh_fill_holes is None and args.mesh_fill_any_facing:
+        ap.error("--mesh-fill-any-facing needs --mesh-fill-holes")
     if not args.mesh and args.mesh_smooth is not None:
         ap.error("--mesh-smooth needs --mesh")
     if args.mesh_smooth is None and (args.mesh_smooth_lambda is not None or args.mesh_smooth_mu is not None or args.mesh_smooth_pin_boundary):
@@ -273,6 +282,9 @@ def main():
                 mesh_filter = dict(min_component=args.mesh_min_component, largest_components=args.mesh_largest_components)
             if TS.simplify_arg(args.mesh_simplify) is not None:
                 mesh_filter["simplify"] = args.mesh_simplify
+            if args.mesh_fill_holes is not None:
+                from rgbid import holes as HO
+                mesh_filter["fill_holes"] = HO.fill_holes_arg(dict(max_edges=args.mesh_fill_holes, any_facing=args.mesh_fill_any_facing))
             if args.mesh_smooth is not None:
                 mesh_filter["smooth"] = TS.smooth_arg(dict(iterations=args.mesh_smooth, lam=0.5 if args.mesh_smooth_lambda is None else args.mesh_smooth_lambda,
                                                            mu=-0.53 if args.mesh_smooth_mu is None else args.mesh_smooth_mu,
@@ -463,7 +475,10 @@ def main():
         TS.write_mesh_ply(path, verts, cols, tris, fused[3] if args.mesh_normals else None)
         flt = vol.get("filter")             # the line below tells the extraction's counts, the one after it what the filter left
         simp = vol.get("simplify")          # ... and the third what the decimation made of that
+        fil = vol.get("fill_holes")         # ... and what the filling added is no part of the extraction's counts either
         first = flt or (dict(vertices=simp["vertices"], triangles=simp["triangles"]) if simp else None)
+        if fil and not first:
+            first = dict(vertices=verts.shape[0] - fil["filled"], triangles=tris.shape[0] - fil["new_triangles"])
         print(f"rank {rank}: mesh of {len(pc.keyframes)} keyframes: {vol['nx']} x {vol['ny']} x {vol['nz']} = {vol['voxels']} voxels of {mesh['voxel']:g} m "
               f"(truncation {mesh['trunc']:g} m), {vol['touched']} touched, {first['vertices'] if first else verts.shape[0]} vertices, "
               f"{first['triangles'] if first else tris.shape[0]} triangles -> {path}")
@@ -473,6 +488,9 @@ def main():
         if simp:
             print(f"rank {rank}: mesh simplify: {simp['clusters']} clusters of {args.mesh_simplify:g} m, triangles {simp['lost']} lost, {simp['collapsed']} collapsed, "
                   f"{simp['duplicate']} duplicate, {simp['kept']} kept, {simp['vertices']} -> {simp['out_vertices']} vertices")
+        if fil:
+            print(f"rank {rank}: mesh fill holes: {fil['loops']} loops, {fil['filled']} filled, {fil['outlines']} outlines, {fil['too_long']} too long, "
+                  f"{fil['blocked']} blocked half-edges, {fil['new_triangles']} new triangles")
         smo = vol.get("smooth")
         if smo:
             print(f"rank {rank}: mesh smooth: {smo['iterations']} iterations of lambda {smo['lam']:g}, mu {smo['mu']:g}, {smo['edges']} edges, "
