@@ -585,6 +585,7 @@ struct rgbid_engine {
   bool prof_on = false;
   size_t lane_pad = 0, map_skew = 0;   // placement of the image maps (alloc_img)
   int n_maps = 0;
+  bool full_filtered = false;          // the whole filtered keyframe pyramid is built and allocated (filtered_level_kept)
 };
 
 namespace {
@@ -612,6 +613,13 @@ int alloc_img(rgbid_engine* e, ImgB* im, int rows, int cols, int elem) {
   *im = ImgB{static_cast<char*>(p) + skew, pitch, lane_stride, rows, cols};
   return RGBID_OK;
 }
+
+// The bilateral-filtered keyframe maps iD_kf_f / I_kf_f and their Sobel pairs g*_c exist only where something reads them.  The pairs feed the covariance pass at
+// finest_level and, with RGBID_FILTER_GRADS, replace the iteration gradients of every level; the filtered maps are the pairs' inputs, reduced level by level from
+// level 0.  full_filtered (RGBID_FILTER_GRADS, or RGBID_ENGINE_FULL_FILTERED_PYRAMID=1 for A/B runs and the bit-identity test) keeps the reference's whole chain.
+// These two predicates decide BOTH what rgbid_engine_create allocates and what enqueue_save_odo_kf launches.
+inline bool filtered_level_kept(const rgbid_engine* e, int l) { return e->full_filtered || l <= e->cfg.finest_level; }
+inline bool filtered_grads_kept(const rgbid_engine* e, int l) { return e->full_filtered || l == e->cfg.finest_level; }
 
 inline LaneMask M(const int* flag) { return LaneMask{flag, 1}; }
 const LaneMask ALL{nullptr, 0};
@@ -669,16 +677,27 @@ void enqueue_save_odo_kf(rgbid_engine* e, hipStream_t s, Ledger& led) {
   }
   launch_bilateral2(s, B, e->iD_kf[0], e->iD_kf_f[0], 2.f * 0.0025f, e->I_kf[0], e->I_kf_f[0], 3.f, m, e->cfg.fast_numerics != 0);
   led.add(1, 1, 2 * 8 * npx(e->iD_kf[0]));
+  // The filtered pyramid and its Sobel pairs are built as far as something reads them (filtered_level_kept / filtered_grads_kept): the covariance pass takes
+  // the gradients of finest_level alone, RGBID_FILTER_GRADS those of every level.  NOMINAL: the ledger prices the reference's switch list, so the launches
+  // that are not enqueued (4 of 96 at three levels with finest_level 0) and their bucket-1 bytes stay booked exactly as if they ran
   for (int i = 0; i < L; ++i) {
+    const double ni = npx(e->iD_kf[i]);   // (the filtered map of the level may not exist)
     if (i) {
-      launch_pyr_down2(s, B, e->iD_kf_f[i - 1], e->iD_kf_f[i], e->I_kf_f[i - 1], e->I_kf_f[i], m);
-      led.add(1, 1, 2 * (4 * npx(e->iD_kf_f[i - 1]) + 4 * npx(e->iD_kf_f[i])));
+      if (filtered_level_kept(e, i)) {
+        assert(e->iD_kf_f[i - 1].base && e->I_kf_f[i - 1].base && e->iD_kf_f[i].base && e->I_kf_f[i].base);
+        launch_pyr_down2(s, B, e->iD_kf_f[i - 1], e->iD_kf_f[i], e->I_kf_f[i - 1], e->I_kf_f[i], m);
+      }
+      led.add(1, 1, 2 * (4 * npx(e->iD_kf[i - 1]) + 4 * ni));
     }
-    launch_gradient2(s, B, e->I_kf_f[i], e->gxI_c[i], e->gyI_c[i], e->iD_kf_f[i], e->gxD_c[i], e->gyD_c[i], m);
-    led.add(1, 1, 2 * 12 * npx(e->iD_kf_f[i]));   // Sobel: 12 B/px per map
+    if (filtered_grads_kept(e, i)) {
+      assert(e->iD_kf_f[i].base && e->I_kf_f[i].base && e->gxI_c[i].base && e->gyI_c[i].base && e->gxD_c[i].base && e->gyD_c[i].base);
+      launch_gradient2(s, B, e->I_kf_f[i], e->gxI_c[i], e->gyI_c[i], e->iD_kf_f[i], e->gxD_c[i], e->gyD_c[i], m);
+    }
+    led.add(1, 1, 2 * 12 * ni);   // Sobel: 12 B/px per map
   }
   for (int i = 0; i < L; ++i) {
     if (filter_grads) {
+      assert(e->gxI_c[i].base && e->gyI_c[i].base && e->gxD_c[i].base && e->gyD_c[i].base);
       launch_copy_bytes(s, B, e->gxI_c[i], e->gxI[i], 4, m); launch_copy_bytes(s, B, e->gyI_c[i], e->gyI[i], 4, m);
       launch_copy_bytes(s, B, e->gxD_c[i], e->gxD[i], 4, m); launch_copy_bytes(s, B, e->gyD_c[i], e->gyD[i], 4, m);
       led.add(4, 1, 4 * 8 * npx(e->iD_kf[i]));
@@ -1004,6 +1023,10 @@ int rgbid_engine_create(rgbid_engine** out, rgbid_ctx* ctx, const rgbid_engine_c
   e->lane_pad = 0; e->map_skew = 0x1100;   // 4 KiB + 256 B per map (alloc_img; measured: profiles/r06_experiments/placement.md)
   if (const char* v = getenv("RGBID_ENGINE_LANE_PAD")) e->lane_pad = (size_t)strtoull(v, nullptr, 0) & ~(size_t)255;
   if (const char* v = getenv("RGBID_ENGINE_MAP_SKEW")) e->map_skew = (size_t)strtoull(v, nullptr, 0) & ~(size_t)255;
+  {
+    const char* v = getenv("RGBID_ENGINE_FULL_FILTERED_PYRAMID");   // read once, here: it decides the allocation
+    e->full_filtered = cfg->image_filtering == RGBID_FILTER_GRADS || (v && atoi(v) != 0);
+  }
   int r = RGBID_OK;
 #define A_IMG(im, rr, cc, el) if (!r) r = alloc_img(e, &(im), rr, cc, el)
   A_IMG(e->in_depth, rows, cols, 2); A_IMG(e->in_rgb, rows, cols, 3);
@@ -1011,7 +1034,18 @@ int rgbid_engine_create(rgbid_engine** out, rgbid_ctx* ctx, const rgbid_engine_c
     int pr = rows >> l, pc = cols >> l;
     ImgB* per_level[] = {&e->iD_curr[l], &e->I_curr[l], &e->iD_kf[l], &e->I_kf[l], &e->iD_kf_f[l], &e->I_kf_f[l], &e->gxI[l], &e->gyI[l],
                          &e->gxD[l], &e->gyD[l], &e->gxI_c[l], &e->gyI_c[l], &e->gxD_c[l], &e->gyD_c[l], &e->wiD[l], &e->wI[l]};
-    for (ImgB* im : per_level) A_IMG(*im, pr, pc, 4);
+    for (ImgB* im : per_level) {
+      const bool filtered = im == &e->iD_kf_f[l] || im == &e->I_kf_f[l], grads_c = im == &e->gxI_c[l] || im == &e->gyI_c[l] || im == &e->gxD_c[l] || im == &e->gyD_c[l];
+      if ((filtered && !filtered_level_kept(e, l)) || (grads_c && !filtered_grads_kept(e, l))) { ++e->n_maps; continue; }   // never written or read; its skew slot stays: the other maps keep their places
+      A_IMG(*im, pr, pc, 4);
+    }
+  }
+  // A use of a map that was not allocated is an error here, not a null pointer in a kernel: the covariance pass (enqueue_step) reads the Sobel pairs of finest_level,
+  // a Sobel pair needs its filtered map, a filtered map the level above it.  enqueue_save_odo_kf asserts the same operands where it lists the launches.
+  assert(filtered_grads_kept(e, cfg->finest_level));
+  for (int l = 0; l < e->L && !r; ++l) {
+    if (filtered_grads_kept(e, l)) assert(filtered_level_kept(e, l) && e->gxI_c[l].base && e->gyI_c[l].base && e->gxD_c[l].base && e->gyD_c[l].base);
+    if (filtered_level_kept(e, l)) assert((l == 0 || filtered_level_kept(e, l - 1)) && e->iD_kf_f[l].base && e->I_kf_f[l].base);
   }
   A_IMG(e->r_curr, rows, cols, 4); A_IMG(e->g_curr, rows, cols, 4); A_IMG(e->b_curr, rows, cols, 4);
   A_IMG(e->iD_integr, rows, cols, 4); A_IMG(e->iD_integr_raw, rows, cols, 4); A_IMG(e->w_integr, rows, cols, 4);
