@@ -501,7 +501,7 @@ def cloud_bounds(points, pad=0.0):
 
 def fuse(ctx, keyframes, K, rows, cols, bounds=None, voxel=0.02, trunc=None, min_weight=1, z_min=0.05, z_max=20.0, max_voxels=1 << 27,
          points=None, return_volume=False, normals=False, keep_volume=False, min_component=None, largest_components=None, simplify=None,
-         smooth=None, recolour=None, recolour_tolerance=None, recolour_measured=None, fill_holes=None):
+         smooth=None, recolour=None, recolour_tolerance=None, recolour_measured=None, fill_holes=None, colour_align=None):
     """one-shot over the keyframes of a run (ChunkCloud.keyframes with `depthinv` and, for a coloured mesh, `colour`): a volume over
     `bounds` = x0 y0 z0 x1 y1 z1 (None: the box of the cloud `points`, padded by trunc) with voxels of `voxel` metres, every keyframe
     integrated in order with its world pose, the surface extracted -> (vertices, colours, triangles) as CUDA tensors, with normals
@@ -517,8 +517,17 @@ def fuse(ctx, keyframes, K, rows, cols, bounds=None, voxel=0.02, trunc=None, min
     own depth at its pose agrees with the vertex's within recolour_tolerance metres (None: 2 voxel) and, with recolour_measured, where
     its own `depthinv` agrees within that many metres; the mesh's normals weight the keyframes when it has them; a vertex no keyframe
     sees keeps its colour; the volume's figures gain `recolour`: the vertices, those a keyframe coloured, the (vertex, keyframe) pairs
-    per class.  None leaves every byte as it is."""
+    per class.  None leaves every byte as it is.  colour_align (a dict of rgbid.colouralign.refine_keyframes' keywords, possibly empty)
+    refines the keyframes' poses against the colours of the mesh that is returned before recolour samples them (DESIGN.md section 31;
+    surface_tolerance defaults to recolour's); the volume's figures gain `colour_align`: the refined keyframes, every scale's result
+    and figures.  The volume and the mesh's geometry are those of the given poses.  None leaves every byte as it is."""
     trunc = 4.0 * voxel if trunc is None else trunc
+    if colour_align is not None:
+        from . import colouralign as CA  # colouralign imports raster and recolour, which need nothing of this module
+        colour_align = dict(colour_align)
+        CA.RC.keyframes_arg(keyframes, colour_align.get("measured_tolerance") is not None)
+        CA.scales_arg(colour_align.get("scales", (4, 2, 1)), rows, cols)
+        colour_align.setdefault("surface_tolerance", 2.0 * voxel if recolour_tolerance is None else recolour_tolerance)
     if recolour is not None:
         from . import recolour as RC     # recolour imports raster, which needs nothing of this module
         RC.mode_arg(recolour)
@@ -555,6 +564,11 @@ def fuse(ctx, keyframes, K, rows, cols, bounds=None, voxel=0.02, trunc=None, min
         filtered = min_component is not None or largest_components is not None
         mesh = vol.extract(w, colours=True, normals=normals, min_component=min_component, largest_components=largest_components, simplify=simplify,
                            smooth=smooth, fill_holes=fill_holes)
+        if colour_align is not None:
+            refined, results, figures = CA.refine_keyframes(ctx, mesh[0], mesh[2], keyframes, K, rows, cols, mesh[3] if normals else None,
+                                                            z_min=z_min, z_max=z_max, **colour_align)
+            aligned = dict(keyframes=refined, results=results, figures=figures)
+            keyframes = refined               # what recolour samples; the volume was integrated above
         if recolour is not None:
             nrm = mesh[3] if normals else None
             new_colours, used, pairs = RC.recolour_mesh(ctx, mesh[0], mesh[2], keyframes, K, rows, cols, nrm, mesh[1], recolour, recolour_tolerance,
@@ -574,6 +588,8 @@ def fuse(ctx, keyframes, K, rows, cols, bounds=None, voxel=0.02, trunc=None, min
                 mesh[-1]["smooth"] = vol.last_smooth
             if recolour is not None:
                 mesh[-1]["recolour"] = recoloured
+            if colour_align is not None:
+                mesh[-1]["colour_align"] = aligned
         if keep_volume:
             mesh += (vol,)
             vol = None

@@ -148,6 +148,13 @@ def main():
                     help="with --mesh-recolour: metres between a vertex and the mesh's own depth in a keyframe for the keyframe to see it (default 2 H)")
     ap.add_argument("--mesh-recolour-measured", type=float, default=None, metavar="M",
                     help="with --mesh-recolour: also ask that the keyframe's own depth lies within M metres of the vertex")
+    ap.add_argument("--mesh-colour-align", action="store_true",
+                    help="with --mesh-recolour or --mesh-texture: refine the keyframes' poses against the mesh's colours first (colour map optimisation, "
+                         "rigid part: DESIGN.md section 31); the geometry stays as it is, only the colours are sampled at the refined poses")
+    ap.add_argument("--mesh-colour-align-scales", default=None, metavar="F,F,...", help="with --mesh-colour-align: the coarse-to-fine factors (default 4,2,1)")
+    ap.add_argument("--mesh-colour-align-rounds", type=int, default=None, metavar="N", help="with --mesh-colour-align: target passes per scale (default 4)")
+    ap.add_argument("--mesh-colour-align-fixed", choices=("first", "none"), default=None,
+                    help="with --mesh-colour-align: hold the first keyframe's pose (the default) or none")
     ap.add_argument("--mesh-texture", default="", metavar="OUT.obj",
                     help="with --mesh: also write the mesh that is written, after all clean-up options, as OUT.obj with OUT.mtl and the texture "
                          "atlas OUT.png: every triangle gets a patch of an image baked from the keyframes that see it, sampled at full "
@@ -234,6 +241,11 @@ def main():
         ap.error("--mesh-recolour-tolerance / --mesh-recolour-measured need --mesh-recolour")
     if not args.mesh and args.mesh_texture:
         ap.error("--mesh-texture needs --mesh")
+    if args.mesh_colour_align and args.mesh_recolour is None and not args.mesh_texture:
+        ap.error("--mesh-colour-align needs --mesh-recolour or --mesh-texture")
+    if not args.mesh_colour_align and (args.mesh_colour_align_scales is not None or args.mesh_colour_align_rounds is not None
+                                       or args.mesh_colour_align_fixed is not None):
+        ap.error("--mesh-colour-align-scales / --mesh-colour-align-rounds / --mesh-colour-align-fixed need --mesh-colour-align")
     if not args.mesh_texture and (args.mesh_texture_patch is not None or args.mesh_texture_mode is not None or args.mesh_texture_tolerance is not None
                                   or args.mesh_texture_measured is not None):
         ap.error("--mesh-texture-patch / --mesh-texture-mode / --mesh-texture-tolerance / --mesh-texture-measured need --mesh-texture")
@@ -296,6 +308,16 @@ def main():
                     mesh_filter["recolour_tolerance"] = RC.tolerance_arg("--mesh-recolour-tolerance", args.mesh_recolour_tolerance)
                 if args.mesh_recolour_measured is not None:
                     mesh_filter["recolour_measured"] = RC.tolerance_arg("--mesh-recolour-measured", args.mesh_recolour_measured)
+            if args.mesh_colour_align:
+                from rgbid import colouralign as CA
+                try:
+                    scales = (4, 2, 1) if args.mesh_colour_align_scales is None else tuple(int(f) for f in args.mesh_colour_align_scales.split(","))
+                except ValueError:
+                    ap.error(f"--mesh-colour-align-scales: integers separated by commas, got {args.mesh_colour_align_scales!r}")
+                mesh_filter["colour_align"] = dict(scales=CA.scales_arg(scales, args.rows, args.cols),
+                                                   rounds=4 if args.mesh_colour_align_rounds is None else args.mesh_colour_align_rounds,
+                                                   fixed=None if args.mesh_colour_align_fixed == "none" else (0,))
+                CA.rule_arg(16.0, 0.0, 1e-7, 6, 2, mesh_filter["colour_align"]["rounds"], 3, 1)
             texture = None
             if args.mesh_texture:
                 from rgbid import recolour as RC
@@ -495,6 +517,11 @@ def main():
         if smo:
             print(f"rank {rank}: mesh smooth: {smo['iterations']} iterations of lambda {smo['lam']:g}, mu {smo['mu']:g}, {smo['edges']} edges, "
                   f"{smo['boundary_vertices']} boundary vertices, {'pinned' if smo['pin_boundary'] else 'not pinned'}")
+        aligned = vol.get("colour_align")
+        if aligned:
+            from rgbid import colouralign as CA
+            for line in CA.figure_lines(aligned["figures"], aligned["results"]):
+                print(f"rank {rank}: mesh {line}")
         rec = vol.get("recolour")
         if rec:
             print(f"rank {rank}: mesh recolour ({rec['mode']}): {rec['coloured']} of {rec['vertices']} vertices coloured from {len(pc.keyframes)} keyframes; pairs: "
@@ -506,7 +533,7 @@ def main():
                 obj = f"{root}.rank{rank}{ext}"
             nrm = fused[3] if args.mesh_normals else None
             try:
-                tex = TX.texture_mesh(ctx, verts, tris, pc.keyframes, tuple(args.K), args.rows, args.cols, normals=nrm, colours=cols, **texture)
+                tex = TX.texture_mesh(ctx, verts, tris, aligned["keyframes"] if aligned else pc.keyframes, tuple(args.K), args.rows, args.cols, normals=nrm, colours=cols, **texture)
                 TX.write_obj(obj, verts, tris, tex["uv"], tex["atlas"], nrm)
             except ValueError as e:
                 sys.exit(f"rank {rank}: --mesh-texture: {e}")
