@@ -107,6 +107,14 @@ def main():
                          "after the component and simplify options and before --mesh-smooth")
     ap.add_argument("--mesh-fill-any-facing", action="store_true",
                     help="with --mesh-fill-holes: also close the loops whose cap would face against their rim's triangles (the outer edges of fragments)")
+    ap.add_argument("--mesh-denoise", type=int, default=None, metavar="N",
+                    help="with --mesh: denoise the mesh with its sharp edges kept, N iterations over the face normals (0 .. 256; DESIGN.md section 32), "
+                         "after the component, simplify and fill options and before --mesh-smooth; with --mesh-normals the normals are those of the "
+                         "denoised surface")
+    ap.add_argument("--mesh-denoise-vertex-iterations", type=int, default=None, metavar="M",
+                    help="with --mesh-denoise: the passes that move the vertices along the filtered normals, 0 .. 256 (default 10)")
+    ap.add_argument("--mesh-denoise-threshold", type=float, default=None, metavar="T",
+                    help="with --mesh-denoise: a face hears a neighbour only where the dot product of their normals exceeds T, 0 <= T < 1 (default 0.4)")
     ap.add_argument("--mesh-smooth", type=int, default=None, metavar="N",
                     help="with --mesh: move the vertices by N iterations of Taubin's filter (DESIGN.md section 24), after the component and "
                          "simplify options; with --mesh-normals the normals are those of the smoothed surface")
@@ -261,6 +269,10 @@ def main():
         ap.error("--mesh-fill-holes needs --mesh")
     if args.mesh_fill_holes is None and args.mesh_fill_any_facing:
         ap.error("--mesh-fill-any-facing needs --mesh-fill-holes")
+    if not args.mesh and args.mesh_denoise is not None:
+        ap.error("--mesh-denoise needs --mesh")
+    if args.mesh_denoise is None and (args.mesh_denoise_vertex_iterations is not None or args.mesh_denoise_threshold is not None):
+        ap.error("--mesh-denoise-vertex-iterations / --mesh-denoise-threshold need --mesh-denoise")
     if not args.mesh and args.mesh_smooth is not None:
         ap.error("--mesh-smooth needs --mesh")
     if args.mesh_smooth is None and (args.mesh_smooth_lambda is not None or args.mesh_smooth_mu is not None or args.mesh_smooth_pin_boundary):
@@ -297,6 +309,11 @@ def main():
             if args.mesh_fill_holes is not None:
                 from rgbid import holes as HO
                 mesh_filter["fill_holes"] = HO.fill_holes_arg(dict(max_edges=args.mesh_fill_holes, any_facing=args.mesh_fill_any_facing))
+            if args.mesh_denoise is not None:
+                from rgbid import denoise as DN
+                mesh_filter["denoise"] = DN.denoise_arg(dict(normal_iterations=args.mesh_denoise,
+                                                             vertex_iterations=10 if args.mesh_denoise_vertex_iterations is None else args.mesh_denoise_vertex_iterations,
+                                                             threshold=0.4 if args.mesh_denoise_threshold is None else args.mesh_denoise_threshold))
             if args.mesh_smooth is not None:
                 mesh_filter["smooth"] = TS.smooth_arg(dict(iterations=args.mesh_smooth, lam=0.5 if args.mesh_smooth_lambda is None else args.mesh_smooth_lambda,
                                                            mu=-0.53 if args.mesh_smooth_mu is None else args.mesh_smooth_mu,
@@ -513,6 +530,10 @@ def main():
         if fil:
             print(f"rank {rank}: mesh fill holes: {fil['loops']} loops, {fil['filled']} filled, {fil['outlines']} outlines, {fil['too_long']} too long, "
                   f"{fil['blocked']} blocked half-edges, {fil['new_triangles']} new triangles")
+        den = vol.get("denoise")
+        if den:
+            print(f"rank {rank}: mesh denoise: {den['normal_iterations']} normal iterations with threshold {den['threshold']:g}, "
+                  f"{den['vertex_iterations']} vertex iterations, longest row {den['longest_row']}, {den['empty_rows']} vertices without a triangle")
         smo = vol.get("smooth")
         if smo:
             print(f"rank {rank}: mesh smooth: {smo['iterations']} iterations of lambda {smo['lam']:g}, mu {smo['mu']:g}, {smo['edges']} edges, "
