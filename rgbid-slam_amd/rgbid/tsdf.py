@@ -335,7 +335,7 @@ class Volume(_lib.CtxHandle):
         self.ctx.sync()
 
     def extract(self, min_weight=1, colours=True, normals=False, min_component=None, largest_components=None, simplify=None,
-                smooth=None, fill_holes=None, denoise=None):
+                smooth=None, fill_holes=None, denoise=None, refine=None):
         """the surface among the voxels of weight >= min_weight -> (vertices float32 [nv, 3], colours uint8 [nv, 3] or None, triangles
         int32 [nt, 3] holding the uint32 vertex indices) as CUDA tensors; with normals a fourth element, the vertices' world-frame unit
         normals float32 [nv, 3] (0 0 0 where the gradient vanishes).  With min_component (triangles a connected component needs to stay)
@@ -351,7 +351,11 @@ class Volume(_lib.CtxHandle):
         With denoise (a count of normal iterations, or a dict of normal_iterations, vertex_iterations, threshold) the vertices of the
         mesh, after the filter, the decimation and the filling and before the smoothing, are moved by denoise.denoise_mesh (the filter
         that keeps sharp edges), the normals are recomputed from the denoised triangles (area-weighted) and
-        `last_denoise` holds its figures; with None nothing more is done.  Synchronises."""
+        `last_denoise` holds its figures; with None nothing more is done.  With refine (the longest edge to keep in metres, or a dict of
+        max_edge, rounds, caps_only) the edges of the mesh above that length, after the filling and before the denoising and the
+        smoothing, are split at their midpoints by refine.refine_mesh (DESIGN.md section 33) and `last_refine` holds its figures;
+        caps_only needs fill_holes and splits only the fans it appended and the neighbours that share a split rim edge; with None
+        nothing more is done.  Synchronises."""
         w = weight_arg(min_weight)
         component_filter = component_filter_arg(min_component, largest_components)
         cell = simplify_arg(simplify)
@@ -364,6 +368,12 @@ class Volume(_lib.CtxHandle):
         if denoise is not None:            # without the option rgbid.denoise is not imported
             from . import denoise as DN
             denoising = DN.denoise_arg(denoise)
+        refining = None
+        if refine is not None:             # without the option rgbid.refine is not imported
+            from . import refine as RF
+            refining = RF.refine_arg(refine)
+            if refining["caps_only"] and filling is None:
+                raise ValueError("refine: caps_only needs fill_holes")
         nv, nt = C.c_ulonglong(), C.c_ulonglong()
         self.ctx.wait_torch_stream()
         check(self.L.rgbid_tsdf_extract_plan(self._h, w, C.byref(nv), C.byref(nt)))
@@ -383,7 +393,11 @@ class Volume(_lib.CtxHandle):
             from . import simplify as SP
             verts, cols, tris, nrm, self.last_simplify = SP.simplify_mesh(self.ctx, verts, cols, tris, nrm, cell=cell)
         if filling is not None:
+            n_before = tris.shape[0]
             verts, cols, tris, nrm, self.last_fill = HO.fill_holes(self.ctx, verts, cols, tris, nrm, **filling)
+        if refining is not None:
+            caps = RF.cap_selection(n_before, tris.shape[0], self._dev) if refining["caps_only"] else None
+            verts, cols, tris, nrm, _, self.last_refine = RF.refine_mesh(self.ctx, verts, cols, tris, nrm, refining["max_edge"], refining["rounds"], caps)
         if denoising is not None:
             verts, nrm, self.last_denoise = DN.denoise_mesh(self.ctx, verts, tris, normals=normals and fairing is None, **denoising)
         if fairing is not None:
@@ -511,7 +525,7 @@ def cloud_bounds(points, pad=0.0):
 def fuse(ctx, keyframes, K, rows, cols, bounds=None, voxel=0.02, trunc=None, min_weight=1, z_min=0.05, z_max=20.0, max_voxels=1 << 27,
          points=None, return_volume=False, normals=False, keep_volume=False, min_component=None, largest_components=None, simplify=None,
          smooth=None, recolour=None, recolour_tolerance=None, recolour_measured=None, fill_holes=None, colour_align=None,
-         denoise=None):
+         denoise=None, refine=None):
     """one-shot over the keyframes of a run (ChunkCloud.keyframes with `depthinv` and, for a coloured mesh, `colour`): a volume over
     `bounds` = x0 y0 z0 x1 y1 z1 (None: the box of the cloud `points`, padded by trunc) with voxels of `voxel` metres, every keyframe
     integrated in order with its world pose, the surface extracted -> (vertices, colours, triangles) as CUDA tensors, with normals
@@ -523,7 +537,8 @@ def fuse(ctx, keyframes, K, rows, cols, bounds=None, voxel=0.02, trunc=None, min
     by Taubin's filter last, the normals are those of the smoothed surface and the volume's figures gain `smooth`.  fill_holes is Volume.extract's:
     the small holes are closed before the smoothing and the volume's figures gain `fill_holes`, the thirteen counts.  denoise is
     Volume.extract's: the vertices are moved by the filter that keeps sharp edges after the filling and before the smoothing, the normals
-    are those of the denoised surface and the volume's figures gain `denoise`.  recolour = "mean" or
+    are those of the denoised surface and the volume's figures gain `denoise`.  refine is Volume.extract's: the edges above a length are
+    split after the filling and before the denoising and the volume's figures gain `refine`.  recolour = "mean" or
     "best" replaces the colours of the mesh that is returned, after every other option, by what the keyframes show at full resolution
     (rgbid.recolour.recolour_mesh, DESIGN.md section 27: every keyframe needs its `colour`): a keyframe colours a vertex where the mesh's
     own depth at its pose agrees with the vertex's within recolour_tolerance metres (None: 2 voxel) and, with recolour_measured, where
@@ -559,6 +574,10 @@ def fuse(ctx, keyframes, K, rows, cols, bounds=None, voxel=0.02, trunc=None, min
     if denoise is not None:
         from . import denoise as DN
         DN.denoise_arg(denoise)
+    if refine is not None:
+        from . import refine as RF
+        if RF.refine_arg(refine)["caps_only"] and fill_holes is None:
+            raise ValueError("refine: caps_only needs fill_holes")
     if not keyframes:
         raise ValueError("no keyframes to fuse")
     if bounds is None:
@@ -578,7 +597,7 @@ def fuse(ctx, keyframes, K, rows, cols, bounds=None, voxel=0.02, trunc=None, min
                           np.stack([k["t"] for k in kfs]), K, rows, cols, z_min, z_max)
         filtered = min_component is not None or largest_components is not None
         mesh = vol.extract(w, colours=True, normals=normals, min_component=min_component, largest_components=largest_components, simplify=simplify,
-                           smooth=smooth, fill_holes=fill_holes, denoise=denoise)
+                           smooth=smooth, fill_holes=fill_holes, denoise=denoise, refine=refine)
         if colour_align is not None:
             refined, results, figures = CA.refine_keyframes(ctx, mesh[0], mesh[2], keyframes, K, rows, cols, mesh[3] if normals else None,
                                                             z_min=z_min, z_max=z_max, **colour_align)
@@ -599,6 +618,8 @@ def fuse(ctx, keyframes, K, rows, cols, bounds=None, voxel=0.02, trunc=None, min
                 mesh[-1]["simplify"] = vol.last_simplify
             if fill_holes is not None:
                 mesh[-1]["fill_holes"] = vol.last_fill
+            if refine is not None:
+                mesh[-1]["refine"] = vol.last_refine
             if denoise is not None:
                 mesh[-1]["denoise"] = vol.last_denoise
             if smooth is not None:

@@ -107,6 +107,14 @@ def main():
                          "after the component and simplify options and before --mesh-smooth")
     ap.add_argument("--mesh-fill-any-facing", action="store_true",
                     help="with --mesh-fill-holes: also close the loops whose cap would face against their rim's triangles (the outer edges of fragments)")
+    ap.add_argument("--mesh-refine", type=float, default=None, metavar="L",
+                    help="with --mesh: split the edges of the mesh that are longer than L metres at their midpoints until none is left or the "
+                         "rounds run out (DESIGN.md section 33), after the component, simplify and fill options and before --mesh-denoise and "
+                         "--mesh-smooth")
+    ap.add_argument("--mesh-refine-rounds", type=int, default=None, metavar="R",
+                    help="with --mesh-refine: the most rounds, each of which halves the edges that are too long, 0 .. 16 (default 4)")
+    ap.add_argument("--mesh-refine-caps", action="store_true",
+                    help="with --mesh-refine and --mesh-fill-holes: split only the fans that closed the holes, and the neighbours that share a split rim edge")
     ap.add_argument("--mesh-denoise", type=int, default=None, metavar="N",
                     help="with --mesh: denoise the mesh with its sharp edges kept, N iterations over the face normals (0 .. 256; DESIGN.md section 32), "
                          "after the component, simplify and fill options and before --mesh-smooth; with --mesh-normals the normals are those of the "
@@ -269,6 +277,12 @@ def main():
         ap.error("--mesh-fill-holes needs --mesh")
     if args.mesh_fill_holes is None and args.mesh_fill_any_facing:
         ap.error("--mesh-fill-any-facing needs --mesh-fill-holes")
+    if not args.mesh and args.mesh_refine is not None:
+        ap.error("--mesh-refine needs --mesh")
+    if args.mesh_refine is None and (args.mesh_refine_rounds is not None or args.mesh_refine_caps):
+        ap.error("--mesh-refine-rounds / --mesh-refine-caps need --mesh-refine")
+    if args.mesh_refine_caps and args.mesh_fill_holes is None:
+        ap.error("--mesh-refine-caps needs --mesh-fill-holes")
     if not args.mesh and args.mesh_denoise is not None:
         ap.error("--mesh-denoise needs --mesh")
     if args.mesh_denoise is None and (args.mesh_denoise_vertex_iterations is not None or args.mesh_denoise_threshold is not None):
@@ -309,6 +323,10 @@ def main():
             if args.mesh_fill_holes is not None:
                 from rgbid import holes as HO
                 mesh_filter["fill_holes"] = HO.fill_holes_arg(dict(max_edges=args.mesh_fill_holes, any_facing=args.mesh_fill_any_facing))
+            if args.mesh_refine is not None:
+                from rgbid import refine as RF
+                mesh_filter["refine"] = RF.refine_arg(dict(max_edge=args.mesh_refine, rounds=4 if args.mesh_refine_rounds is None else args.mesh_refine_rounds,
+                                                           caps_only=args.mesh_refine_caps))
             if args.mesh_denoise is not None:
                 from rgbid import denoise as DN
                 mesh_filter["denoise"] = DN.denoise_arg(dict(normal_iterations=args.mesh_denoise,
@@ -516,8 +534,11 @@ def main():
         simp = vol.get("simplify")          # ... and the third what the decimation made of that
         fil = vol.get("fill_holes")         # ... and what the filling added is no part of the extraction's counts either
         first = flt or (dict(vertices=simp["vertices"], triangles=simp["triangles"]) if simp else None)
-        if fil and not first:
-            first = dict(vertices=verts.shape[0] - fil["filled"], triangles=tris.shape[0] - fil["new_triangles"])
+        ref = vol.get("refine")             # ... nor what the edge split added
+        split_v, split_t = (sum(r["marked"] for r in ref["rounds"]), sum(r["new_triangles"] for r in ref["rounds"])) if ref else (0, 0)
+        if (fil or ref) and not first:
+            first = dict(vertices=verts.shape[0] - (fil["filled"] if fil else 0) - split_v,
+                         triangles=tris.shape[0] - (fil["new_triangles"] if fil else 0) - split_t)
         print(f"rank {rank}: mesh of {len(pc.keyframes)} keyframes: {vol['nx']} x {vol['ny']} x {vol['nz']} = {vol['voxels']} voxels of {mesh['voxel']:g} m "
               f"(truncation {mesh['trunc']:g} m), {vol['touched']} touched, {first['vertices'] if first else verts.shape[0]} vertices, "
               f"{first['triangles'] if first else tris.shape[0]} triangles -> {path}")
@@ -530,6 +551,10 @@ def main():
         if fil:
             print(f"rank {rank}: mesh fill holes: {fil['loops']} loops, {fil['filled']} filled, {fil['outlines']} outlines, {fil['too_long']} too long, "
                   f"{fil['blocked']} blocked half-edges, {fil['new_triangles']} new triangles")
+        if ref:
+            print(f"rank {rank}: mesh refine: edges above {ref['max_edge']:g} m split in {ref['rounds_run']} rounds, "
+                  f"{split_v} new vertices, {split_t} new triangles, "
+                  f"{ref['left']} edges left above it")
         den = vol.get("denoise")
         if den:
             print(f"rank {rank}: mesh denoise: {den['normal_iterations']} normal iterations with threshold {den['threshold']:g}, "
