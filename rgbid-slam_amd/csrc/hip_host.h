@@ -1,9 +1,10 @@
 // hip_host.h -- the host-side plumbing every C-ABI handle shares: one status path, one allocation function, one owner of a handle's
-// buffers, one destroy, one stage timer and its read-out, one alignment test.  Host code only; a new feature file takes these instead of writing its own.
+// buffers, one destroy, one stage timer and its read-out, one alignment test, one finiteness test.  Host code only; a new feature file takes these instead of writing its own.
 #pragma once
 #include "../../include/rgbid.h"
 #include "ctx.h"
 
+#include <cmath>
 #include <utility>
 #include <vector>
 
@@ -102,5 +103,11 @@ int stage_times(const StageTimer<N>& t, const bool (&timed)[S], const int (&pair
 
 // what every C-ABI asks of a device array of 32-bit words; null passes (whether null is allowed is the caller's test)
 inline bool aligned4(const void* p) { return !(((uintptr_t)p) & 3); }
+
+// whether the n doubles of a pose, or of several, are all finite
+inline bool finite_all(const double* p, int n) {
+  for (int i = 0; i < n; ++i) if (!std::isfinite(p[i])) return false;
+  return true;
+}
 
 }  // namespace rgbid

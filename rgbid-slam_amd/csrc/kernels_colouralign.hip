@@ -22,6 +22,7 @@
 #include "../../include/rgbid_colouralign.h"
 #include "common.h"
 #include "hip_host.h"
+#include "view_device.h"    // the view entry, steps 3 and 4 of a pair; the host's checks of camera and views
 #include "gn_device.h"      // tree64, the upper tree, the solve, the retraction
 
 #include <cmath>
@@ -41,18 +42,10 @@ constexpr int WAVES = VT / 64;
 constexpr int MAX_IT = RGBID_COLOURALIGN_MAX_ITERATIONS;
 constexpr int TARGET_CHUNK = 16;                            // views a block of the chunked target pass walks
 
-struct CaView {                                             // the view table's entry: 80 bytes
-  float m[12];                                              // r00 r01 r02 r10 r11 r12 r20 r21 r22 tx ty tz, written by k_ca_pose
-  const unsigned char* colour;
-  const float* surface;
-  const float* measured;
+struct CaView : ViewEntry {                                 // the view table's entry: 80 bytes; m is written by k_ca_pose
   int fixed, pad;
 };
-struct CaCam {
-  double min_cos;
-  float fx, fy, cx, cy, z_min, z_max, tol_surface, tol_measured;
-  int rows, cols, two_sided;
-};
+static_assert(sizeof(CaView) == 80, "the view table's stride");
 struct CaLattice {
   unsigned stride, n_l, groups;   // the lattice and its groups of 64 (at least one)
   unsigned restart;               // the first iteration of a round: CONVERGED views run again
@@ -79,81 +72,26 @@ __device__ __forceinline__ int ca_status(const rgbid_colouralign_result* res, un
   return s == RGBID_COLOURALIGN_CONVERGED && restart ? RGBID_COLOURALIGN_RUNNING : s;
 }
 
-__device__ __forceinline__ float rot_row(const float* __restrict__ m, float x, float y, float z) {
-  RGBID_FP_STRICT
-  return (m[0] * x + m[1] * y) + m[2] * z;
-}
-
-// rgbid_recolour.h step 4's test of one texel of the surface plane / the inverse-depth plane
-__device__ __forceinline__ bool surface_ok(float d, float Z, float tol) { return __builtin_isfinite(d) && !(fabsf(Z - d) > tol); }
-__device__ __forceinline__ bool measured_ok(float m, float Z, float tol) {
-  if (!(__builtin_isfinite(m) && m > 0.f)) return false;
-  const float z = 1.f / m;
-  return __builtin_isfinite(z) && !(fabsf(Z - z) > tol);
-}
-
 __device__ __forceinline__ unsigned grey(const unsigned char* __restrict__ c, size_t t) {
   return 77u * c[3 * t] + 150u * c[3 * t + 1] + 29u * c[3 * t + 2];
 }
 
-// steps 3 and 4 of one pair: true iff it is TAKEN.  fin: the vertex is finite; facing: its normal has a finite, non-zero squared length
+// steps 3 and 4 of one pair (view_device.h) and its grey sample: true iff it is TAKEN.  fin: the vertex is finite; facing: its normal has
+// a finite, non-zero squared length
 template <bool GRADIENT>
-__device__ __forceinline__ bool ca_pair(const CaView& view, const CaCam& cam, float x, float y, float z, bool fin, bool facing, float n0, float n1,
+__device__ __forceinline__ bool ca_pair(const CaView& view, const ViewCam& cam, float x, float y, float z, bool fin, bool facing, float n0, float n1,
                                         float n2, CaSample& o) {
-  RGBID_FP_STRICT
-  if (!fin) return false;
-  const float* m = view.m;
-  const float Z = rot_row(m + 6, x, y, z) + m[11];
-  if (!(Z >= cam.z_min && Z <= cam.z_max)) return false;     // GATED: NaN fails; z_max is finite, so infinity does too
-  const float X = rot_row(m, x, y, z) + m[9];
-  const float Y = rot_row(m + 3, x, y, z) + m[10];
-  const float u = cam.fx * (X / Z) + cam.cx;
-  const float w_ = cam.fy * (Y / Z) + cam.cy;
-  const float xf = floorf(u * 256.0f + 0.5f);
-  const float yf = floorf(w_ * 256.0f + 0.5f);
-  if (!(fabsf(xf) <= 8388608.f && fabsf(yf) <= 8388608.f)) return false;   // in float: nothing out of range reaches the cast
-  const int xs = (int)xf, ys = (int)yf;
-  const int last_x = 256 * (cam.cols - 1), last_y = 256 * (cam.rows - 1);  // dims <= 16384: below 2^22
-  if (!(xs >= 0 && xs <= last_x && ys >= 0 && ys <= last_y)) return false; // OUTSIDE
-  const int x0 = xs >> 8, y0 = ys >> 8, x1 = min(x0 + 1, cam.cols - 1), y1 = min(y0 + 1, cam.rows - 1);
-  const unsigned ax = (unsigned)(xs & 255), ay = (unsigned)(ys & 255);
-  // every texel index lies in the plane: 0 <= x0 <= x1 <= cols - 1, 0 <= y0 <= y1 <= rows - 1
-  const size_t r0 = (size_t)y0 * (size_t)cam.cols, r1 = (size_t)y1 * (size_t)cam.cols;
-  const size_t t00 = r0 + (size_t)x0, t10 = r0 + (size_t)x1, t01 = r1 + (size_t)x0, t11 = r1 + (size_t)x1;
-  if (view.surface) {
-    const float* d = view.surface;
-    if (!(surface_ok(d[t00], Z, cam.tol_surface) && surface_ok(d[t10], Z, cam.tol_surface) && surface_ok(d[t01], Z, cam.tol_surface) &&
-          surface_ok(d[t11], Z, cam.tol_surface)))
-      return false;                                          // HIDDEN
-  }
-  if (view.measured) {
-    const float* d = view.measured;
-    if (!(measured_ok(d[t00], Z, cam.tol_measured) && measured_ok(d[t10], Z, cam.tol_measured) && measured_ok(d[t01], Z, cam.tol_measured) &&
-          measured_ok(d[t11], Z, cam.tol_measured)))
-      return false;                                          // UNMEASURED
-  }
-  unsigned w = RGBID_RECOLOUR_UNIT_WEIGHT;
-  if (facing) {
-    const double c0 = (double)rot_row(m, n0, n1, n2), c1 = (double)rot_row(m + 3, n0, n1, n2), c2 = (double)rot_row(m + 6, n0, n1, n2);
-    const double Xd = (double)X, Yd = (double)Y, Zd = (double)Z;
-    const double dot = -((c0 * Xd + c1 * Yd) + c2 * Zd);
-    const double g = (c0 * c0 + c1 * c1) + c2 * c2;
-    const double r = (Xd * Xd + Yd * Yd) + Zd * Zd;
-    double cs = dot / sqrt(g * r);
-    if (cam.two_sided) cs = fabs(cs);
-    if (!(cs > 0.0 && cs >= cam.min_cos)) return false;      // AVERTED: a NaN fails
-    const unsigned f = (unsigned)floor(cs * 1024.0 + 0.5);   // cs <= 1 up to rounding, so the cast is in range
-    w = f < 1u ? 1u : f;
-  }
-  const unsigned char* col = view.colour;
-  const unsigned L00 = grey(col, t00), L10 = grey(col, t10), L01 = grey(col, t01), L11 = grey(col, t11);   // <= 65 280
-  o.X = X; o.Y = Y; o.Z = Z; o.w = w;
-  o.s = (256u - ax) * (256u - ay) * L00 + ax * (256u - ay) * L10 + (256u - ax) * ay * L01 + ax * ay * L11;  // <= 65 280 * 65 536
-  if (GRADIENT) {
-    o.Gx = (int)(256u - ay) * ((int)L10 - (int)L00) + (int)ay * ((int)L11 - (int)L01);
-    o.Gy = (int)(256u - ax) * ((int)L01 - (int)L00) + (int)ax * ((int)L11 - (int)L10);
-  }
-  return true;
+  return VIEW_TAKEN == view_sample(view, cam, x, y, z, fin, facing, n0, n1, n2, [&](const ViewSample& q) {
+    const unsigned char* col = view.colour;
+    const unsigned ax = q.ax, ay = q.ay;
+    const unsigned L00 = grey(col, q.t00), L10 = grey(col, q.t10), L01 = grey(col, q.t01), L11 = grey(col, q.t11);   // <= 65 280
+    o.X = q.X; o.Y = q.Y; o.Z = q.Z; o.w = q.w;
+    o.s = (256u - ax) * (256u - ay) * L00 + ax * (256u - ay) * L10 + (256u - ax) * ay * L01 + ax * ay * L11;  // <= 65 280 * 65 536
+    if (GRADIENT) {
+      o.Gx = (int)(256u - ay) * ((int)L10 - (int)L00) + (int)ay * ((int)L11 - (int)L01);
+      o.Gy = (int)(256u - ax) * ((int)L01 - (int)L00) + (int)ax * ((int)L11 - (int)L10);
+    }
+  });
 }
 
 // a lattice vertex's position and normal
@@ -209,7 +147,7 @@ __global__ __launch_bounds__(VT) void k_ca_pose(const rgbid_colouralign_result* 
 // the cleared state with integer atomics: the sums are integers, so the bytes are the same in any order
 template <bool CHUNKS>
 __global__ __launch_bounds__(VT) void k_ca_target(const float* __restrict__ pos, const float* __restrict__ normals, CaLattice lt,
-                                                  const CaView* __restrict__ views, int V, CaCam cam, unsigned long long* __restrict__ S_plane,
+                                                  const CaView* __restrict__ views, int V, ViewCam cam, unsigned long long* __restrict__ S_plane,
                                                   unsigned long long* __restrict__ W_plane, unsigned* __restrict__ used_plane) {
   const unsigned j = blockIdx.x * VT + threadIdx.x;
   if (j >= lt.n_l) return;
@@ -237,7 +175,7 @@ __global__ __launch_bounds__(VT) void k_ca_target(const float* __restrict__ pos,
 // step 6: one thread per lattice vertex, a wave per group of 64, a block four groups of the view blockIdx.y.  Lanes beyond the lattice and
 // pairs that are not used stay in the wave with +0.0: the butterflies need all 64.  No LDS, no atomic.
 __global__ __launch_bounds__(VT) void k_ca_system(const float* __restrict__ pos, const float* __restrict__ normals, CaLattice lt,
-                                                  const CaView* __restrict__ views, CaCam cam, CaRule rule,
+                                                  const CaView* __restrict__ views, ViewCam cam, CaRule rule,
                                                   const unsigned long long* __restrict__ S_plane, const unsigned long long* __restrict__ W_plane,
                                                   const unsigned* __restrict__ used_plane, const rgbid_colouralign_result* __restrict__ res,
                                                   double* __restrict__ sums, unsigned* __restrict__ used, size_t a_stride) {
@@ -356,11 +294,6 @@ __global__ __launch_bounds__(VT) void k_ca_downscale(const unsigned char* __rest
   out[e] = (unsigned char)((2u * sum + ff) / (2u * ff));
 }
 
-bool finite_all(const double* x, int n) {
-  for (int i = 0; i < n; ++i) if (!std::isfinite(x[i])) return false;
-  return true;
-}
-
 }  // namespace
 
 struct rgbid_colouralign {
@@ -428,14 +361,7 @@ int rgbid_colouralign_run(rgbid_colouralign* h, const float* vertices_dev, const
                           const rgbid_colouralign_rule* rule, rgbid_colouralign_result* result_dev) {
   if (!h || !views || !K || !params || !rule || !result_dev) return RGBID_E_INVALID;
   if (n > h->cap_n || V < 1 || V > h->cap_v) return RGBID_E_INVALID;
-  if (rows < 1 || cols < 1 || rows > RGBID_RASTER_MAX_DIM || cols > RGBID_RASTER_MAX_DIM) return RGBID_E_INVALID;
-  const rgbid_recolour_params& p = *params;
-  if (!(std::isfinite(p.z_min) && std::isfinite(p.z_max) && p.z_min > 0.f && p.z_min <= p.z_max)) return RGBID_E_INVALID;
-  if (!(std::isfinite(p.surface_tolerance) && p.surface_tolerance >= 0.f && std::isfinite(p.measured_tolerance) && p.measured_tolerance >= 0.f))
-    return RGBID_E_INVALID;
-  if (!(p.min_cos >= 0.f && p.min_cos <= 1.f) || (p.two_sided != 0 && p.two_sided != 1)) return RGBID_E_INVALID;
-  for (int k = 0; k < 4; ++k) if (!std::isfinite(K[k])) return RGBID_E_INVALID;
-  if (K[0] == 0.f || K[1] == 0.f) return RGBID_E_INVALID;
+  if (!view_camera_ok(K, rows, cols, *params)) return RGBID_E_INVALID;
   if (n && (!vertices_dev || !aligned4(vertices_dev))) return RGBID_E_INVALID;
   if (!aligned4(normals_dev)) return RGBID_E_INVALID;
   const rgbid_colouralign_rule& q = *rule;
@@ -446,15 +372,8 @@ int rgbid_colouralign_run(rgbid_colouralign* h, const float* vertices_dev, const
   if (q.rounds < 1 || q.iterations < 1 || q.stride < 1 || q.rounds > MAX_IT || q.iterations > MAX_IT || q.rounds * q.iterations > MAX_IT)
     return RGBID_E_INVALID;
   if (((uintptr_t)result_dev) & 7) return RGBID_E_INVALID;
-  for (int v = 0; v < V; ++v) {
-    const rgbid_recolour_view& in = views[v].view;
-    if (views[v].fixed != 0 && views[v].fixed != 1) return RGBID_E_INVALID;
-    if (!in.colour_dev || !aligned4(in.surface_dev) || !aligned4(in.measured_dev)) return RGBID_E_INVALID;
-    if (!finite_all(in.pose.R, 9) || !finite_all(in.pose.t, 3)) return RGBID_E_INVALID;
-    float cw[12];
-    rgbid_render_pose_cw(&in.pose, cw);
-    for (int k = 0; k < 12; ++k) if (!std::isfinite(cw[k])) return RGBID_E_INVALID;
-  }
+  for (int v = 0; v < V; ++v)
+    if ((views[v].fixed != 0 && views[v].fixed != 1) || !view_ok(views[v].view)) return RGBID_E_INVALID;
   (void)hipSetDevice(h->ctx->device);
   hipStream_t s = h->ctx->stream;
   const bool timing = h->timer.on;
@@ -472,11 +391,7 @@ int rgbid_colouralign_run(rgbid_colouralign* h, const float* vertices_dev, const
   RGBID_HIP(hipMemcpyAsync(h->views, h->views_host, sizeof(CaView) * (size_t)V, hipMemcpyHostToDevice, s));
   RGBID_HIP(hipMemcpyAsync(h->poses, h->poses_host, sizeof(double) * 12 * (size_t)V, hipMemcpyHostToDevice, s));
   RGBID_HIP(hipEventRecord(h->copied, s));
-  CaCam cam;
-  cam.min_cos = (double)p.min_cos;
-  cam.fx = K[0]; cam.fy = K[1]; cam.cx = K[2]; cam.cy = K[3]; cam.z_min = p.z_min; cam.z_max = p.z_max;
-  cam.tol_surface = p.surface_tolerance; cam.tol_measured = p.measured_tolerance;
-  cam.rows = rows; cam.cols = cols; cam.two_sided = p.two_sided;
+  const ViewCam cam = view_cam(K, rows, cols, *params);
   CaLattice lt{};
   lt.stride = (unsigned)q.stride;
   lt.n_l = (unsigned)((n + lt.stride - 1) / lt.stride);         // n is 2^31 at most

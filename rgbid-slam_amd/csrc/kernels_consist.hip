@@ -20,6 +20,7 @@
 #include "../../include/rgbid_consist.h"
 #include "common.h"
 #include "hip_host.h"
+#include "view_device.h"    // rot_row
 #include "voxel_device.h"   // flag compaction and the argument checks of the filters
 
 #include <cmath>
@@ -48,11 +49,6 @@ struct ConsistCam {
   int rows, cols, w, nv;
   unsigned min_support, max_conflicts;
 };
-
-__device__ __forceinline__ float rot_row(const float* __restrict__ m, float x, float y, float z) {
-  RGBID_FP_STRICT
-  return (m[0] * x + m[1] * y) + m[2] * z;
-}
 
 // steps 3 - 8 for one record and one view: 0 blind, 1 supports, 1 << 16 contradicts; `gated`: the pair passed steps 4 and 5
 __device__ __forceinline__ unsigned view_verdict(const ConsistView& vw, const ConsistCam& cam, float x, float y, float z, bool& gated) {
@@ -160,11 +156,6 @@ struct KeepRec {
     out[2 * (size_t)pos + 1] = b;
   }
 };
-
-bool finite_all(const double* p, int n) {
-  for (int i = 0; i < n; ++i) if (!std::isfinite(p[i])) return false;
-  return true;
-}
 
 }  // namespace
 

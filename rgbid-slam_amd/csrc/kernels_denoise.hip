@@ -5,22 +5,22 @@
 // The judge is tests/denoise_mirror.py; counts, face table, normals and positions are byte-identical to it.
 //   plan     k_mesh_check<false>     mesh_device.h: counts the triangles with an index >= n_v into a slot copied to the host: a bad index ends
 //                                    the call here
-//            k_denoise_corner_keys   one (vertex, corner) pair per corner, one stable sort_bits by bitlen(n_v) bits
+//            k_mesh_corner_keys      mesh_device.h: one (vertex, corner) pair per corner, one stable sort_bits by bitlen(n_v) bits
 //            k_denoise_faces         faces[i] = the sorted corner / 3
-//            k_denoise_offsets       offsets[w] = the corners of the vertices below w: a bounded binary search per vertex
+//            k_mesh_offsets<false>   mesh_device.h: offsets[w] = the corners of the vertices below w: a bounded binary search per vertex
 //            k_denoise_rowstats      one thread per vertex: the empty rows, the longest row (integer atomics, one per wave)
 //            k_denoise_tristats      one thread per triangle: the repeats, the work of a normal pass (a 64-bit integer atomic per wave)
 //   normals  k_denoise_raw           one thread per triangle: the unit normal of its area vector
 //            k_denoise_normal_pass   one thread per triangle: merges the three ascending rows of its vertices with three cursors, gathers
 //                                    the normals of up to four merged faces before their adds, sums in order in double
 //   vertices k_denoise_vertex_pass   one thread per vertex over its row: the centroids in double in registers, sums in order in double
-// The corner keys and the offsets are kernels_smooth.hip's corner table restated: a kernel that is no template in mesh_device.h would be
-// compiled into every file that includes it.
+// The corner keys, the offsets, the load of a triangle and its area vector are kernels_smooth.hip's too: mesh_device.h has them.
 // No float atomics, no wait on another thread, every loop has its bound when it starts.
 #include "../../include/rgbid_denoise.h"
 #include "common.h"
 #include "hip_host.h"
-#include "mesh_device.h"    // the index check, the argument test, the create; voxel_device.h's ordered gather and sort workspace
+#include "mesh_device.h"    // the index check, the corner table, tri_load, area_vector, the argument and overlap tests, the create;
+                            // voxel_device.h's ordered gather and sort workspace
 
 #include <cmath>
 #include <cstring>
@@ -35,29 +35,8 @@ static_assert(SLOT_VOXELS < SLOT_BAD && SLOT_REPEATS < SLOTS && SLOT_WORK % 2 ==
 constexpr unsigned NO_FACE = 0xFFFFFFFFu;   // above every triangle number: the head of a row that has ended
 
 // ---- face table -------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(VT) void k_denoise_corner_keys(const unsigned* __restrict__ tri, unsigned long long corners, unsigned n_v,
-                                                            unsigned* __restrict__ keys, unsigned* __restrict__ idx) {
-  for (size_t i = (size_t)blockIdx.x * VT + threadIdx.x; i < corners; i += (size_t)gridDim.x * VT) {
-    const unsigned v = tri[i];
-    keys[i] = v < n_v ? v : n_v;
-    idx[i] = (unsigned)i;
-  }
-}
-
 __global__ __launch_bounds__(VT) void k_denoise_faces(const unsigned* __restrict__ corners_sorted, unsigned long long corners, unsigned* __restrict__ faces) {
   for (size_t i = (size_t)blockIdx.x * VT + threadIdx.x; i < corners; i += (size_t)gridDim.x * VT) faces[i] = corners_sorted[i] / 3u;
-}
-
-// offsets[w], w = 0 .. n_v: how many of the `count` ascending keys are below w; nothing is read without a key.  32 halvings at most
-__global__ __launch_bounds__(VT) void k_denoise_offsets(const unsigned* __restrict__ keys, unsigned count, unsigned n_v, unsigned* __restrict__ offsets) {
-  for (size_t w = (size_t)blockIdx.x * VT + threadIdx.x; w <= n_v; w += (size_t)gridDim.x * VT) {
-    unsigned lo = 0, hi = count;
-    for (int it = 0; it < 32 && lo < hi; ++it) {
-      const unsigned mid = lo + ((hi - lo) >> 1);
-      if (keys[mid] < w) lo = mid + 1; else hi = mid;
-    }
-    offsets[w] = lo;
-  }
 }
 
 __global__ __launch_bounds__(VT) void k_denoise_rowstats(const unsigned* __restrict__ offsets, unsigned n_v, unsigned* __restrict__ slots) {
@@ -92,42 +71,14 @@ __global__ __launch_bounds__(VT) void k_denoise_tristats(const unsigned* __restr
 }
 
 // ---- raw normals ------------------------------------------------------------------------------------------------------------------
-struct Tri {
-  float p[3][3];
-  bool ok;                            // the triangle and its indices exist and the three positions are finite
-};
-
-// the three positions of triangle t; a triangle or an index that names nothing reads nothing
-__device__ __forceinline__ Tri tri_load(const float* __restrict__ pos, const unsigned* __restrict__ tri, unsigned t, unsigned n_t, unsigned n_v) {
-  Tri q;
-  q.ok = false;
-  for (int k = 0; k < 3; ++k) for (int a = 0; a < 3; ++a) q.p[k][a] = 0.f;
-  if (t >= n_t) return q;
-  const unsigned i[3] = {tri[3 * (size_t)t], tri[3 * (size_t)t + 1], tri[3 * (size_t)t + 2]};
-  if (!(i[0] < n_v && i[1] < n_v && i[2] < n_v)) return q;
-  for (int k = 0; k < 3; ++k)
-    for (int a = 0; a < 3; ++a) q.p[k][a] = pos[3 * (size_t)i[k] + a];
-  q.ok = finite3(q.p[0][0], q.p[0][1], q.p[0][2]) && finite3(q.p[1][0], q.p[1][1], q.p[1][2]) && finite3(q.p[2][0], q.p[2][1], q.p[2][2]);
-  return q;
-}
-
 __global__ __launch_bounds__(VT) void k_denoise_raw(const float* __restrict__ pos, const unsigned* __restrict__ tri, unsigned n_t, unsigned n_v,
                                                     float* __restrict__ out) {
   RGBID_FP_STRICT
   const size_t t = (size_t)blockIdx.x * VT + threadIdx.x;
   if (t >= n_t) return;
-  const Tri q = tri_load(pos, tri, (unsigned)t, n_t, n_v);
+  const TriPos q = tri_load(pos, tri, (unsigned)t, n_t, n_v);
   double s[3] = {0, 0, 0};
-  if (q.ok) {
-    double e1[3], e2[3];
-    for (int a = 0; a < 3; ++a) {
-      e1[a] = (double)q.p[1][a] - (double)q.p[0][a];
-      e2[a] = (double)q.p[2][a] - (double)q.p[0][a];
-    }
-    s[0] = (e1[1] * e2[2]) - (e1[2] * e2[1]);
-    s[1] = (e1[2] * e2[0]) - (e1[0] * e2[2]);
-    s[2] = (e1[0] * e2[1]) - (e1[1] * e2[0]);
-  }
+  if (q.ok) area_vector(q, s);
   float n[3];
   unit_of(s, n);                      // zeros when |s|^2 is 0 or not finite
   for (int a = 0; a < 3; ++a) out[3 * t + a] = n[a];
@@ -237,7 +188,7 @@ __global__ __launch_bounds__(VT) void k_denoise_normal_pass(const float* __restr
 
 // ---- the vertex pass --------------------------------------------------------------------------------------------------------------
 struct Member {
-  Tri tri;
+  TriPos tri;
   float n[3];
   unsigned id;
 };
@@ -327,16 +278,6 @@ struct rgbid_denoise {
   void mark(int i) { timer.mark(i, ctx->stream); }
 };
 
-namespace {
-
-// whether the byte ranges [a, a + na) and [b, b + nb) share a byte
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return na && nb && x < y + nb && y < x + na;
-}
-
-}  // namespace
-
 extern "C" {
 
 int rgbid_denoise_create(rgbid_denoise** out, rgbid_ctx* ctx, unsigned long long max_vertices, unsigned long long max_triangles) {
@@ -382,13 +323,15 @@ int rgbid_denoise_plan(rgbid_denoise* h, unsigned long long n_vertices, unsigned
   const unsigned long long corners = 3ull * n_t;
   const unsigned* keys = nullptr;
   if (corners) {
-    hipLaunchKernelGGL(k_denoise_corner_keys, dim3(grid_of((corners + VT - 1) / VT)), dim3(VT), 0, s, triangles_dev, corners, n_v, w.keys_as<unsigned>(0),
+    // <unsigned> is no choice: the kernel is a template only so that a file that does not launch it does not compile it
+    hipLaunchKernelGGL(k_mesh_corner_keys<unsigned>, dim3(grid_of((corners + VT - 1) / VT)), dim3(VT), 0, s, triangles_dev, corners, n_v, w.keys_as<unsigned>(0),
                        w.idx[0]);
     const int p = w.sort_bits<unsigned>(s, (unsigned)corners, bitlen(n_v), 0);
     keys = w.keys_as<unsigned>(p);
     hipLaunchKernelGGL(k_denoise_faces, dim3(grid_of((corners + VT - 1) / VT)), dim3(VT), 0, s, w.idx[p], corners, h->faces);
   }
-  hipLaunchKernelGGL(k_denoise_offsets, dim3(grid_of(((unsigned long long)n_v + 1 + VT - 1) / VT)), dim3(VT), 0, s, keys, (unsigned)corners, n_v, h->offsets);
+  hipLaunchKernelGGL(k_mesh_offsets<false>, dim3(grid_of(((unsigned long long)n_v + 1 + VT - 1) / VT)), dim3(VT), 0, s, keys, (const unsigned*)nullptr,
+                     (const unsigned*)nullptr, (unsigned)corners, n_v, h->offsets);
   hipLaunchKernelGGL(k_denoise_rowstats, dim3((n_v + VT - 1) / VT), dim3(VT), 0, s, h->offsets, n_v, w.slots);
   if (n_t) hipLaunchKernelGGL(k_denoise_tristats, dim3((n_t + VT - 1) / VT), dim3(VT), 0, s, triangles_dev, h->offsets, n_t, n_v, w.slots);
   h->mark(3);

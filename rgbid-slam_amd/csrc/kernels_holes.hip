@@ -6,7 +6,7 @@
 //          sort_rounds         voxel_device.h: one (key, item) pair per corner 3 t + c, keyed by the ends of its edge (a triangle with a
 //                              repeated index gets the sentinel n_v), two stable rounds: by the larger end, then by the smaller.  Equal
 //                              undirected edges are adjacent, the sentinels last
-//          k_holes_ends        the larger end of the sorted corners beside their smaller end; counts the directed edges
+//          k_mesh_corner_ends  mesh_device.h: the larger end of the sorted corners beside their smaller end; counts the directed edges
 //          flag compaction     over the runs of length one: boundary[rank] = the owner corner
 //          k_holes_degrees     out(v), in(v) and the leaving owner: integer atomics (add, add, min), a function of the mesh alone
 //          k_holes_vstats      counts the boundary vertices and those that are not simple
@@ -24,8 +24,8 @@
 #include "../../include/rgbid_holes.h"
 #include "common.h"
 #include "hip_host.h"
-#include "mesh_device.h"    // the index check, the argument test, the create; voxel_device.h's sort_rounds, flag compaction and unit_of;
-                            // the sort workspace
+#include "mesh_device.h"    // the index check, the corners as edges, p3_load, cross3, the argument and overlap tests, the create;
+                            // voxel_device.h's sort_rounds, flag compaction, value scan and unit_of; the sort workspace
 
 #include <cstring>
 
@@ -43,46 +43,6 @@ constexpr unsigned BLOCKED = 0x80000000u;   // the top bit of a jump: the chain 
 constexpr unsigned NONE = 0xFFFFFFFFu;
 
 // ---- boundary half-edges ------------------------------------------------------------------------------------------------------------
-// the mesh as the corner kernels see it: item 3 t + c is the directed edge from corner c to corner c + 1 of triangle t
-struct CornerView {
-  const unsigned* tri;
-  unsigned n_t, n_v;
-  unsigned long long items;          // 3 n_t
-  // -> whether the item is a directed edge; an item or an index that names nothing reads nothing
-  __device__ __forceinline__ bool ends(unsigned item, unsigned& from, unsigned& to) const {
-    if (item >= items) return false;
-    const unsigned t = item / 3u, c = item - 3u * t;
-    const unsigned i0 = tri[3 * (size_t)t], i1 = tri[3 * (size_t)t + 1], i2 = tri[3 * (size_t)t + 2];
-    from = c == 0 ? i0 : c == 1 ? i1 : i2;
-    to = c == 0 ? i1 : c == 1 ? i2 : i0;
-    return i0 < n_v && i1 < n_v && i2 < n_v && i0 != i1 && i1 != i2 && i2 != i0;
-  }
-};
-
-// sort_rounds' key of round r (0: the larger end, 1: the smaller) for a corner; the sentinel n_v for a corner that gives no edge
-struct CornerKey {
-  CornerView view;
-  __device__ __forceinline__ unsigned long long size() const { return view.items; }
-  __device__ __forceinline__ unsigned operator()(unsigned item, int r) const {
-    unsigned a, b;
-    const bool ok = view.ends(item, a, b);
-    return ok ? (r ? min(a, b) : max(a, b)) : view.n_v;
-  }
-};
-
-// after the two rounds: the larger end of every sorted corner; the corners that give an edge are counted
-__global__ __launch_bounds__(VT) void k_holes_ends(CornerView view, const unsigned* __restrict__ order, unsigned* __restrict__ his,
-                                                   unsigned* __restrict__ directed) {
-  unsigned c = 0;
-  for (size_t m = (size_t)blockIdx.x * VT + threadIdx.x; m < view.items; m += (size_t)gridDim.x * VT) {
-    unsigned a, b;
-    const bool ok = view.ends(order[m], a, b);
-    his[m] = ok ? max(a, b) : view.n_v;
-    c += ok;
-  }
-  wave_add_to(directed, c);
-}
-
 // the flag compaction's source: sorted corner m is a run of length one of its undirected edge -> boundary[rank] = its corner
 struct LoneSrc {
   const unsigned* los;
@@ -226,40 +186,6 @@ __global__ __launch_bounds__(VT) void k_holes_rank(const unsigned* __restrict__ 
   to_out[i] = tt;
 }
 
-// ---- the exclusive scan of one value per item, in the tile order of the flag compaction (voxel_device.h) -------------------------------
-// A source says how many items it has (size), the value of an item (value) and what an item does with the sum before it (write).
-template <class S>
-__global__ __launch_bounds__(VT) void k_holes_sum_count(S s, unsigned* __restrict__ bc) {
-  __shared__ unsigned lds[VT / 64];
-  const unsigned n = s.size();
-  const size_t t0 = (size_t)blockIdx.x * RUN_TILE;
-  unsigned c = 0;
-  for (int j = 0; j < RUN_IPT; ++j) {
-    const size_t i = t0 + j * VT + threadIdx.x;
-    if (i < n) c += s.value((unsigned)i);
-  }
-  unsigned tot;
-  block_scan_incl(c, lds, tot);
-  if (threadIdx.x == 0) bc[blockIdx.x] = tot;
-}
-
-template <class S>
-__global__ __launch_bounds__(VT) void k_holes_sum_write(S s, const unsigned* __restrict__ bc) {
-  __shared__ unsigned lds[VT / 64];
-  const unsigned n = s.size();
-  const size_t t0 = (size_t)blockIdx.x * RUN_TILE;
-  if (t0 >= n) return;                 // uniform over the block
-  unsigned carry = bc[blockIdx.x];
-  for (int j = 0; j < RUN_IPT; ++j) {
-    const size_t i = t0 + j * VT + threadIdx.x;
-    const unsigned v = i < n ? s.value((unsigned)i) : 0u;
-    unsigned tot;
-    const unsigned incl = block_scan_incl(v, lds, tot);
-    if (i < n) s.write((unsigned)i, carry + incl - v, v);
-    carry += tot;
-  }
-}
-
 // the loops' lengths -> offsets[loop], offsets[L] behind the last; the longest loop
 struct LengthSrc {
   const unsigned* heads;
@@ -299,30 +225,12 @@ __global__ __launch_bounds__(VT) void k_holes_table(const unsigned* __restrict__
 }
 
 // ---- select ---------------------------------------------------------------------------------------------------------------------------
-struct P3 {
-  double p[3];
-  bool finite;
-};
-
-// the position of vertex id in double; an index that names no vertex reads nothing and is not finite
-__device__ __forceinline__ P3 p3_load(const float* __restrict__ pos, unsigned id, unsigned n_v) {
-  P3 q = {{NAN, NAN, NAN}, false};
-  if (id < n_v) {
-    const size_t o = 3 * (size_t)id;
-    const float x = pos[o], y = pos[o + 1], z = pos[o + 2];
-    q.p[0] = (double)x; q.p[1] = (double)y; q.p[2] = (double)z;
-    q.finite = finite3(x, y, z);
-  }
-  return q;
-}
-
-// acc += u x w, every component two products and one difference, the three sums one add each
+// acc += u x w, the three sums one add each
 __device__ __forceinline__ void cross_add(double acc[3], const double u[3], const double w[3]) {
   RGBID_FP_STRICT
-  const double c0 = (u[1] * w[2]) - (u[2] * w[1]);
-  const double c1 = (u[2] * w[0]) - (u[0] * w[2]);
-  const double c2 = (u[0] * w[1]) - (u[1] * w[0]);
-  acc[0] += c0; acc[1] += c1; acc[2] += c2;
+  double c[3];
+  cross3(u, w, c);
+  acc[0] += c[0]; acc[1] += c[1]; acc[2] += c[2];
 }
 
 // One thread per loop: the order of the sums is the contract, so a loop is not split across lanes.  The walk is bounded by k, which is
@@ -501,17 +409,6 @@ struct rgbid_holes {
 
 namespace {
 
-unsigned blocks_of(unsigned long long items) { return (unsigned)((items + VT - 1) / VT); }
-
-// the exclusive scan of a value source of at most `items` items: tile sums, the workspace's one-block scan of them, the write
-template <class S>
-void value_scan(hipStream_t s, SortWorkspace& w, const S& src, unsigned items, int slot) {
-  const unsigned tiles = (items + RUN_TILE - 1) / RUN_TILE;
-  hipLaunchKernelGGL(k_holes_sum_count<S>, dim3(tiles), dim3(VT), 0, s, src, w.bc);
-  hipLaunchKernelGGL(k_vox_scan1, dim3(1), dim3(VT), 0, s, w.bc, tiles, w.slots, slot, (unsigned*)nullptr, 0u);
-  hipLaunchKernelGGL(k_holes_sum_write<S>, dim3(tiles), dim3(VT), 0, s, src, w.bc);
-}
-
 // step 2 and the degrees of step 3: everything the host has to read before it knows the number of rounds
 void boundary_stage(rgbid_holes* h) {
   hipStream_t s = h->ctx->stream;
@@ -521,7 +418,7 @@ void boundary_stage(rgbid_holes* h) {
   const unsigned items = (unsigned)view.items;
   const int p = w.sort_rounds(s, CornerKey{view}, n_v, items, {0, 1});   // by the larger end, then by the smaller
   unsigned* his = w.keys_as<unsigned>(p ^ 1);
-  hipLaunchKernelGGL(k_holes_ends, dim3(grid_of(blocks_of(items))), dim3(VT), 0, s, view, w.idx[p], his, w.slots + SLOT_DIRECTED);
+  hipLaunchKernelGGL(k_mesh_corner_ends<true>, dim3(grid_of(blocks_of(items))), dim3(VT), 0, s, view, w.idx[p], his, w.slots + SLOT_DIRECTED);
   unsigned* boundary = w.idx[p ^ 1];
   const LoneSrc lone{w.keys_as<unsigned>(p), his, w.idx[p], items, n_v, boundary};
   w.count_scan(s, lone, items, SLOT_RUNS);
@@ -564,14 +461,9 @@ void loop_stage(rgbid_holes* h, unsigned n_s) {
   for (int j = 0; j < rounds; ++j, q ^= 1)
     hipLaunchKernelGGL(k_holes_rank, dim3(blocks), dim3(VT), 0, s, hops[q], to[q], hops[q ^ 1], to[q ^ 1], n_s);
   const LengthSrc len{h->heads, hops[q], w.slots + SLOT_LOOPS, n_s, cap_l, h->offsets, w.slots + SLOT_LONGEST};
-  value_scan(s, w, len, cap_l, SLOT_INLOOPS);
+  w.value_scan(s, len, cap_l, SLOT_INLOOPS);
   hipLaunchKernelGGL(k_holes_table, dim3(blocks), dim3(VT), 0, s, h->simple, h->out_owner, lab[p], jump[p], hops[q], h->loop_of, h->offsets,
                      w.slots + SLOT_LOOPS, n_s, h->n_v, cap_l, h->loop_vertices, h->loop_owners);
-}
-
-bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return a && b && a_bytes && b_bytes && x < y + b_bytes && y < x + a_bytes;
 }
 
 }  // namespace
@@ -699,7 +591,7 @@ int rgbid_holes_select(rgbid_holes* h, const float* vertices_dev, unsigned max_e
   w.count_scan(s, filled, n_l, SLOT_RUNS);
   w.write(s, filled, n_l);
   const BaseSrc base{h->status, h->offsets, n_l, h->bases};
-  value_scan(s, w, base, n_l, SLOT_VOXELS);
+  w.value_scan(s, base, n_l, SLOT_VOXELS);
   h->mark(5);
   RGBID_HIP(hipGetLastError());
   if (int r = w.read_slots(s)) return r;

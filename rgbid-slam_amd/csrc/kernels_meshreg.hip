@@ -271,11 +271,6 @@ struct rgbid_meshreg {
 
 namespace {
 
-bool finite_all(const double* x, int n) {
-  for (int i = 0; i < n; ++i) if (!std::isfinite(x[i])) return false;
-  return true;
-}
-
 template <class P>
 int align_call(rgbid_meshreg* h, const P& pts, unsigned long long n, int V, const double* poses, float huber, double damping, double eps,
                unsigned min_points, int n_levels, const rgbid_meshreg_level* levels, rgbid_meshreg_result* result_dev) {

@@ -20,6 +20,7 @@
 #include "../../include/rgbid_raster.h"
 #include "common.h"
 #include "hip_host.h"
+#include "view_device.h"    // rot_row
 #include "mesh_device.h"    // the index check, the argument test, the create; voxel_device.h's VT, grid_of, the stable flag compaction
 
 #include <cmath>
@@ -63,11 +64,6 @@ static_assert(sizeof(RasterVertex) == 16, "one 16-byte load");
 __global__ __launch_bounds__(VT) void k_rast_clear(uint4* __restrict__ keys, size_t n16) {
   const size_t i = (size_t)blockIdx.x * VT + threadIdx.x;
   if (i < n16) keys[i] = make_uint4(~0u, ~0u, ~0u, ~0u);
-}
-
-__device__ __forceinline__ float rot_row(const float* __restrict__ m, float x, float y, float z) {
-  RGBID_FP_STRICT
-  return (m[0] * x + m[1] * y) + m[2] * z;
 }
 
 // step 3: rec[view][vertex]; the position is read once for all views of the chunk
@@ -347,11 +343,6 @@ __global__ __launch_bounds__(VT) void k_rast_sum(const unsigned long long* __res
   unsigned long long sum = 0;
   for (int s = 0; s < COUNT_SLOTS; ++s) sum += parts[((size_t)v * COUNT_SLOTS + s) * COUNT_LINE + k];
   counts[i] = sum;
-}
-
-bool finite_all(const double* p, int n) {
-  for (int i = 0; i < n; ++i) if (!std::isfinite(p[i])) return false;
-  return true;
 }
 
 constexpr int MARKS = 5;                                    // per chunk: project [0, 1], setup + small [1, 2], large [2, 3], resolve [3, 4]

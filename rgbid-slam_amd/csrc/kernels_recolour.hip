@@ -14,6 +14,7 @@
 #include "../../include/rgbid_recolour.h"
 #include "common.h"
 #include "hip_host.h"
+#include "view_device.h"    // the view entry, rot_row, the texel tests, the accumulation, the class tally, step 7's byte; the host's checks
 
 #include <cmath>
 #include <new>
@@ -22,52 +23,18 @@ using namespace rgbid;
 
 namespace {
 
-constexpr int VT = 256;                                     // threads of a block: four waves
-constexpr int CHUNK = RGBID_RECOLOUR_VIEW_CHUNK;
-constexpr int N_COUNTS = 6, COUNT_LINE = 8;                 // a view's six counts lie in one 64-byte line
-constexpr int WAVES = VT / 64;
-enum { C_GATED = 0, C_OUTSIDE, C_HIDDEN, C_UNMEASURED, C_AVERTED, C_TAKEN };
-static_assert(VT == 256 && CHUNK * N_COUNTS <= VT, "one thread per (view, class) adds the block's counts up");
-
-struct RecolourView {
-  float m[12];                                              // r00 r01 r02 r10 r11 r12 r20 r21 r22 tx ty tz
-  const unsigned char* colour;
-  const float* surface;
-  const float* measured;
-};
-struct RecolourViews {                                      // kernel argument: 16 x 72 bytes
-  RecolourView v[CHUNK];
-};
-struct RecolourCam {
-  double min_cos;
-  float fx, fy, cx, cy, z_min, z_max, tol_surface, tol_measured;
-  int rows, cols, nv, two_sided;                            // nv: views of this launch
-  unsigned first_view;                                      // global index of the launch's first view
-};
-
-__device__ __forceinline__ float rot_row(const float* __restrict__ m, float x, float y, float z) {
-  RGBID_FP_STRICT
-  return (m[0] * x + m[1] * y) + m[2] * z;
-}
-
-// step 4's test of one texel of the surface plane / the inverse-depth plane
-__device__ __forceinline__ bool surface_ok(float d, float Z, float tol) { return __builtin_isfinite(d) && !(fabsf(Z - d) > tol); }
-__device__ __forceinline__ bool measured_ok(float m, float Z, float tol) {
-  if (!(__builtin_isfinite(m) && m > 0.f)) return false;
-  const float z = 1.f / m;
-  return __builtin_isfinite(z) && !(fabsf(Z - z) > tol);
-}
+constexpr int VT = VIEW_BLOCK;                              // threads of a block: four waves
+constexpr int CHUNK = VIEWS_PER_CHUNK;
 
 // steps 3 - 6 of one chunk of views.  counts: the count lines of the launch's first view
 template <bool BEST>
-__global__ __launch_bounds__(VT) void k_recolour_add(const float* __restrict__ pos, const float* __restrict__ normals, unsigned n_v, RecolourViews vw,
-                                                     RecolourCam cam, unsigned long long* __restrict__ state, unsigned* __restrict__ used_plane,
-                                                     unsigned long long* __restrict__ counts) {
+__global__ __launch_bounds__(VT) void k_recolour_add(const float* __restrict__ pos, const float* __restrict__ normals, unsigned n_v, ViewChunk vw,
+                                                     ViewCam cam, int nv, unsigned first_view, unsigned long long* __restrict__ state,
+                                                     unsigned* __restrict__ used_plane, unsigned long long* __restrict__ counts) {
   RGBID_FP_STRICT
-  __shared__ unsigned tally[WAVES][CHUNK * N_COUNTS];
+  __shared__ unsigned tally[VIEW_WAVES][CHUNK * VIEW_N_COUNTS];
   const unsigned i = blockIdx.x * VT + threadIdx.x;
   const bool live = i < n_v;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float x = 0.f, y = 0.f, z = 0.f, n0 = 0.f, n1 = 0.f, n2 = 0.f;
   bool fin = false, facing = false;
   unsigned long long a0 = 0, a1 = 0, a2 = 0, a3 = 0;       // MEAN: S_0 S_1 S_2 W; BEST: s_0 s_1 s_2 key
@@ -84,12 +51,12 @@ __global__ __launch_bounds__(VT) void k_recolour_add(const float* __restrict__ p
     used = used_plane[i];
   }
   const int last_x = 256 * (cam.cols - 1), last_y = 256 * (cam.rows - 1);   // dims <= 16384: below 2^22
-  for (int v = 0; v < cam.nv; ++v) {
-    const RecolourView& view = vw.v[v];                     // wave-uniform: scalar registers
+  for (int v = 0; v < nv; ++v) {
+    const ViewEntry& view = vw.v[v];                        // wave-uniform: scalar registers
     const float* m = view.m;
     int cls = -1;                                           // a thread behind the last vertex has no class
     if (live) {
-      cls = C_GATED;
+      cls = VIEW_GATED;
       if (fin) {
         const float Z = rot_row(m + 6, x, y, z) + m[11];
         if (Z >= cam.z_min && Z <= cam.z_max) {             // NaN fails; z_max is finite, so infinity does too
@@ -101,81 +68,58 @@ __global__ __launch_bounds__(VT) void k_recolour_add(const float* __restrict__ p
           const float yf = floorf(w_ * 256.0f + 0.5f);
           if (fabsf(xf) <= 8388608.f && fabsf(yf) <= 8388608.f) {   // in float: nothing out of range reaches the cast
             const int xs = (int)xf, ys = (int)yf;
-            cls = C_OUTSIDE;
+            cls = VIEW_OUTSIDE;
             if (xs >= 0 && xs <= last_x && ys >= 0 && ys <= last_y) {
               const int x0 = xs >> 8, y0 = ys >> 8, x1 = min(x0 + 1, cam.cols - 1), y1 = min(y0 + 1, cam.rows - 1);
               const unsigned ax = (unsigned)(xs & 255), ay = (unsigned)(ys & 255);
               // every texel index lies in the plane: 0 <= x0 <= x1 <= cols - 1, 0 <= y0 <= y1 <= rows - 1
               const size_t r0 = (size_t)y0 * (size_t)cam.cols, r1 = (size_t)y1 * (size_t)cam.cols;
               const size_t t00 = r0 + (size_t)x0, t10 = r0 + (size_t)x1, t01 = r1 + (size_t)x0, t11 = r1 + (size_t)x1;
-              cls = C_TAKEN;
+              cls = VIEW_TAKEN;
               if (view.surface) {
                 const float* d = view.surface;
                 const float d00 = d[t00], d10 = d[t10], d01 = d[t01], d11 = d[t11];
                 if (!(surface_ok(d00, Z, cam.tol_surface) && surface_ok(d10, Z, cam.tol_surface) && surface_ok(d01, Z, cam.tol_surface) &&
                       surface_ok(d11, Z, cam.tol_surface)))
-                  cls = C_HIDDEN;
+                  cls = VIEW_HIDDEN;
               }
-              if (cls == C_TAKEN && view.measured) {
+              if (cls == VIEW_TAKEN && view.measured) {
                 const float* d = view.measured;
                 const float m00 = d[t00], m10 = d[t10], m01 = d[t01], m11 = d[t11];
                 if (!(measured_ok(m00, Z, cam.tol_measured) && measured_ok(m10, Z, cam.tol_measured) && measured_ok(m01, Z, cam.tol_measured) &&
                       measured_ok(m11, Z, cam.tol_measured)))
-                  cls = C_UNMEASURED;
+                  cls = VIEW_UNMEASURED;
               }
               unsigned w = RGBID_RECOLOUR_UNIT_WEIGHT;
-              if (cls == C_TAKEN && facing) {
+              if (cls == VIEW_TAKEN && facing) {
                 const double c0 = (double)rot_row(m, n0, n1, n2), c1 = (double)rot_row(m + 3, n0, n1, n2), c2 = (double)rot_row(m + 6, n0, n1, n2);
                 const double Xd = (double)X, Yd = (double)Y, Zd = (double)Z;
                 const double dot = -((c0 * Xd + c1 * Yd) + c2 * Zd);
-                const double g = (c0 * c0 + c1 * c1) + c2 * c2;
-                const double r = (Xd * Xd + Yd * Yd) + Zd * Zd;
-                double cs = dot / sqrt(g * r);
+                const double gg = (c0 * c0 + c1 * c1) + c2 * c2;
+                const double rr = (Xd * Xd + Yd * Yd) + Zd * Zd;
+                double cs = dot / sqrt(gg * rr);
                 if (cam.two_sided) cs = fabs(cs);
                 if (cs > 0.0 && cs >= cam.min_cos) {        // a NaN fails; cs <= 1 up to rounding, so the cast is in range
                   const unsigned f = (unsigned)floor(cs * 1024.0 + 0.5);
                   w = f < 1u ? 1u : f;
                 } else {
-                  cls = C_AVERTED;
+                  cls = VIEW_AVERTED;
                 }
               }
-              if (cls == C_TAKEN) {
-                const unsigned char* col = view.colour;
-                const unsigned w00 = (256u - ax) * (256u - ay), w10 = ax * (256u - ay), w01 = (256u - ax) * ay, w11 = ax * ay;   // sum 65 536
-                unsigned s[3];
-                for (int k = 0; k < 3; ++k)
-                  s[k] = w00 * col[3 * t00 + k] + w10 * col[3 * t10 + k] + w01 * col[3 * t01 + k] + w11 * col[3 * t11 + k];    // <= 255 * 65 536
-                ++used;
-                if (BEST) {
-                  const unsigned long long key = ((unsigned long long)w << 32) | (unsigned long long)(0xFFFFFFFFu - (cam.first_view + (unsigned)v));
-                  if (key > a3) { a3 = key; a0 = s[0]; a1 = s[1]; a2 = s[2]; }
-                } else {
-                  a0 += (unsigned long long)w * s[0]; a1 += (unsigned long long)w * s[1]; a2 += (unsigned long long)w * s[2];
-                  a3 += w;
-                }
-              }
+              if (cls == VIEW_TAKEN)
+                view_accumulate<BEST>(view.colour, ViewSample{X, Y, Z, w, ax, ay, t00, t10, t01, t11}, first_view + (unsigned)v, a0, a1, a2, a3, used);
             }
           }
         }
       }
     }
-    // the wave's pairs per class; every thread of the block is here
-    for (int k = 0; k < N_COUNTS; ++k) {
-      const unsigned n = (unsigned)__popcll(__ballot(cls == k));
-      if (lane == 0) tally[wave][v * N_COUNTS + k] = n;
-    }
+    view_tally(tally, v, cls);
   }
   if (live) {
     state[i] = a0; state[(size_t)n_v + i] = a1; state[2 * (size_t)n_v + i] = a2; state[3 * (size_t)n_v + i] = a3;
     used_plane[i] = used;
   }
-  __syncthreads();
-  if ((int)threadIdx.x < cam.nv * N_COUNTS) {
-    unsigned n = 0;
-    for (int w = 0; w < WAVES; ++w) n += tally[w][threadIdx.x];
-    const unsigned v = threadIdx.x / N_COUNTS, k = threadIdx.x - v * N_COUNTS;
-    if (n) atomicAdd(counts + (size_t)v * COUNT_LINE + k, (unsigned long long)n);
-  }
+  view_tally_add(tally, nv, counts);
 }
 
 // step 7.  colours_in and colours_out may be the same buffer: a thread reads its three bytes before it writes them
@@ -192,24 +136,11 @@ __global__ __launch_bounds__(VT) void k_recolour_finish(const unsigned long long
   if (!colours_out) return;
   unsigned char rgb[3] = {0, 0, 0};
   if (used) {
-    for (int k = 0; k < 3; ++k) {
-      const unsigned long long a = state[(size_t)k * n_v + i];
-      if (BEST) {
-        rgb[k] = (unsigned char)((a + 32768ull) >> 16);
-      } else {
-        const unsigned long long D = 65536ull * a3;        // W >= 1 with used >= 1
-        rgb[k] = (unsigned char)((2ull * a + D) / (2ull * D));
-      }
-    }
+    for (int k = 0; k < 3; ++k) rgb[k] = view_state_byte<BEST>(state[(size_t)k * n_v + i], a3);
   } else if (colours_in) {
     for (int k = 0; k < 3; ++k) rgb[k] = colours_in[3 * (size_t)i + k];
   }
   for (int k = 0; k < 3; ++k) colours_out[3 * (size_t)i + k] = rgb[k];
-}
-
-bool finite_all(const double* p, int n) {
-  for (int i = 0; i < n; ++i) if (!std::isfinite(p[i])) return false;
-  return true;
 }
 
 enum { M_ADD0 = 0, M_ADD1, M_FIN0, M_FIN1, MARKS };
@@ -220,7 +151,7 @@ struct rgbid_recolour {
   rgbid_ctx* ctx = nullptr;
   unsigned long long cap_v = 0;
   unsigned long long* state = nullptr;         // 36 bytes per vertex of capacity: [4][n_v] uint64, then [n_v] uint32
-  unsigned long long* counts = nullptr;        // [MAX_VIEWS][COUNT_LINE]
+  unsigned long long* counts = nullptr;        // [MAX_VIEWS][VIEW_COUNT_LINE]
   bool begun = false;
   unsigned long long n_v = 0;                  // begin's
   int mode = RGBID_RECOLOUR_MEAN, views = 0;   // views since begin
@@ -242,7 +173,7 @@ int rgbid_recolour_create(rgbid_recolour** out, rgbid_ctx* ctx, unsigned long lo
   r->ctx = ctx;
   r->cap_v = max_vertices;
   int e = r->buf.alloc(&r->state, (size_t)max_vertices * 36 + 4);   // the uint32 plane ends on a whole 8 bytes
-  if (!e) e = r->buf.alloc(&r->counts, sizeof(unsigned long long) * COUNT_LINE * RGBID_RECOLOUR_MAX_VIEWS);
+  if (!e) e = r->buf.alloc(&r->counts, sizeof(unsigned long long) * VIEW_COUNT_LINE * RGBID_RECOLOUR_MAX_VIEWS);
   if (e) { destroy_handle(r); return e; }
   *out = r;
   return RGBID_OK;
@@ -262,56 +193,30 @@ int rgbid_recolour_add(rgbid_recolour* r, const float* vertices_dev, const float
                        const rgbid_recolour_view* views, const float K[4], int rows, int cols, const rgbid_recolour_params* params) {
   if (!r || !views || !K || !params || V < 1 || !r->begun || V > RGBID_RECOLOUR_MAX_VIEWS - r->views) return RGBID_E_INVALID;
   if (n_vertices != r->n_v || n_vertices > r->cap_v) return RGBID_E_INVALID;
-  if (rows < 1 || cols < 1 || rows > RGBID_RASTER_MAX_DIM || cols > RGBID_RASTER_MAX_DIM) return RGBID_E_INVALID;
-  const rgbid_recolour_params& p = *params;
-  if (!(std::isfinite(p.z_min) && std::isfinite(p.z_max) && p.z_min > 0.f && p.z_min <= p.z_max)) return RGBID_E_INVALID;
-  if (!(std::isfinite(p.surface_tolerance) && p.surface_tolerance >= 0.f && std::isfinite(p.measured_tolerance) && p.measured_tolerance >= 0.f))
-    return RGBID_E_INVALID;
-  if (!(p.min_cos >= 0.f && p.min_cos <= 1.f) || (p.two_sided != 0 && p.two_sided != 1)) return RGBID_E_INVALID;
-  for (int k = 0; k < 4; ++k) if (!std::isfinite(K[k])) return RGBID_E_INVALID;
-  if (K[0] == 0.f || K[1] == 0.f) return RGBID_E_INVALID;
+  if (!view_camera_ok(K, rows, cols, *params)) return RGBID_E_INVALID;
   if (n_vertices && (!vertices_dev || !aligned4(vertices_dev))) return RGBID_E_INVALID;
   if (!aligned4(normals_dev)) return RGBID_E_INVALID;
-  for (int v = 0; v < V; ++v) {
-    if (!views[v].colour_dev || !aligned4(views[v].surface_dev) || !aligned4(views[v].measured_dev)) return RGBID_E_INVALID;
-    if (!finite_all(views[v].pose.R, 9) || !finite_all(views[v].pose.t, 3)) return RGBID_E_INVALID;
-    float cw[12];
-    rgbid_render_pose_cw(&views[v].pose, cw);
-    for (int k = 0; k < 12; ++k) if (!std::isfinite(cw[k])) return RGBID_E_INVALID;
-  }
+  for (int v = 0; v < V; ++v) if (!view_ok(views[v])) return RGBID_E_INVALID;
   (void)hipSetDevice(r->ctx->device);
   hipStream_t st = r->ctx->stream;
   const unsigned n_v = (unsigned)n_vertices;                // 2^31 at most
-  unsigned long long* lines = r->counts + (size_t)r->views * COUNT_LINE;
-  RGBID_HIP(hipMemsetAsync(lines, 0, sizeof(unsigned long long) * COUNT_LINE * (size_t)V, st));
-  RecolourCam cam;
-  cam.min_cos = (double)p.min_cos;
-  cam.fx = K[0]; cam.fy = K[1]; cam.cx = K[2]; cam.cy = K[3]; cam.z_min = p.z_min; cam.z_max = p.z_max;
-  cam.tol_surface = p.surface_tolerance; cam.tol_measured = p.measured_tolerance;
-  cam.rows = rows; cam.cols = cols; cam.two_sided = p.two_sided;
+  unsigned long long* lines = r->counts + (size_t)r->views * VIEW_COUNT_LINE;
+  RGBID_HIP(hipMemsetAsync(lines, 0, sizeof(unsigned long long) * VIEW_COUNT_LINE * (size_t)V, st));
+  const ViewCam cam = view_cam(K, rows, cols, *params);
   r->timed[0] = false;
   r->timer.mark(M_ADD0, st);
-  RecolourViews vw;
+  ViewChunk vw;
   for (int v0 = 0; n_v && v0 < V; v0 += CHUNK) {
     const int nv = V - v0 < CHUNK ? V - v0 : CHUNK;
-    for (int v = 0; v < CHUNK; ++v) {
-      RecolourView& o = vw.v[v];
-      if (v < nv) {
-        const rgbid_recolour_view& in = views[v0 + v];
-        rgbid_render_pose_cw(&in.pose, o.m);
-        o.colour = in.colour_dev; o.surface = in.surface_dev; o.measured = in.measured_dev;
-      } else {
-        for (int k = 0; k < 12; ++k) o.m[k] = 0.f;
-        o.colour = nullptr; o.surface = nullptr; o.measured = nullptr;
-      }
-    }
-    cam.nv = nv;
-    cam.first_view = (unsigned)(r->views + v0);
+    view_pack(views + v0, nv, vw);
+    const unsigned first_view = (unsigned)(r->views + v0);  // global index of the launch's first view
     const dim3 grid((n_v + VT - 1) / VT), block(VT);
     if (r->mode == RGBID_RECOLOUR_BEST)
-      hipLaunchKernelGGL(k_recolour_add<true>, grid, block, 0, st, vertices_dev, normals_dev, n_v, vw, cam, r->state, r->used_plane(), lines + (size_t)v0 * COUNT_LINE);
+      hipLaunchKernelGGL(k_recolour_add<true>, grid, block, 0, st, vertices_dev, normals_dev, n_v, vw, cam, nv, first_view, r->state, r->used_plane(),
+                         lines + (size_t)v0 * VIEW_COUNT_LINE);
     else
-      hipLaunchKernelGGL(k_recolour_add<false>, grid, block, 0, st, vertices_dev, normals_dev, n_v, vw, cam, r->state, r->used_plane(), lines + (size_t)v0 * COUNT_LINE);
+      hipLaunchKernelGGL(k_recolour_add<false>, grid, block, 0, st, vertices_dev, normals_dev, n_v, vw, cam, nv, first_view, r->state, r->used_plane(),
+                         lines + (size_t)v0 * VIEW_COUNT_LINE);
   }
   r->timer.mark(M_ADD1, st);
   r->timed[0] = r->timer.on;
@@ -344,14 +249,7 @@ int rgbid_recolour_finish(rgbid_recolour* r, const uint8_t* colours_in_dev, uint
 
 int rgbid_recolour_counts(rgbid_recolour* r, int first_view, int V, unsigned long long* out) {
   if (!r || !out || !r->begun || first_view < 0 || V < 1 || first_view > r->views || V > r->views - first_view) return RGBID_E_INVALID;
-  (void)hipSetDevice(r->ctx->device);
-  std::vector<unsigned long long> lines((size_t)V * COUNT_LINE);
-  RGBID_HIP(hipMemcpyAsync(lines.data(), r->counts + (size_t)first_view * COUNT_LINE, sizeof(unsigned long long) * lines.size(), hipMemcpyDeviceToHost,
-                           r->ctx->stream));
-  RGBID_HIP(hipStreamSynchronize(r->ctx->stream));
-  for (int v = 0; v < V; ++v)
-    for (int k = 0; k < N_COUNTS; ++k) out[(size_t)v * N_COUNTS + k] = lines[(size_t)v * COUNT_LINE + k];
-  return RGBID_OK;
+  return view_counts_read(r->ctx, r->counts + (size_t)first_view * VIEW_COUNT_LINE, V, out);
 }
 
 int rgbid_recolour_timing(rgbid_recolour* r, int enable, float ms[2]) {

@@ -6,7 +6,7 @@
 //          sort_rounds         voxel_device.h: one (key, item) pair per corner 3 t + c, keyed by the ends of its edge (a triangle with a
 //                              repeated index gets the sentinel n_v), two stable rounds: by the larger end, then by the smaller.  Equal
 //                              undirected edges are adjacent and in ascending (lo, hi) order, the sentinels last
-//          k_refine_ends       the larger end of the sorted corners beside their smaller end
+//          k_mesh_corner_ends  mesh_device.h: the larger end of the sorted corners beside their smaller end
 //          value scan          over the run heads: item m of run e writes corner_edge[corner] = e, the head the ends of e, a member of a
 //                              selected triangle the eligibility flag (every writer writes the same byte)
 //          k_refine_mark       one thread per edge, two position gathers: the mark beside the flag; counts the eligible edges
@@ -20,8 +20,8 @@
 #include "../../include/rgbid_refine.h"
 #include "common.h"
 #include "hip_host.h"
-#include "mesh_device.h"    // the index check, the argument test, the create; voxel_device.h's sort_rounds, flag compaction and unit_of;
-                            // the sort workspace
+#include "mesh_device.h"    // the index check, the corners as edges, p3_load, the argument and overlap tests, the create;
+                            // voxel_device.h's sort_rounds, flag compaction, value scan and unit_of; the sort workspace
 
 #include <cmath>
 #include <cstring>
@@ -38,76 +38,6 @@ constexpr unsigned NONE = 0xFFFFFFFFu;
 constexpr unsigned char ELIGIBLE = 1, MARKED = 2;
 
 // ---- the edge table ---------------------------------------------------------------------------------------------------------------------
-// the mesh as the corner kernels see it: item 3 t + c is the edge from corner c to corner c + 1 of triangle t
-struct CornerView {
-  const unsigned* tri;
-  unsigned n_t, n_v;
-  unsigned long long items;          // 3 n_t
-  // -> whether the item names an edge; an item or an index that names nothing reads nothing
-  __device__ __forceinline__ bool ends(unsigned item, unsigned& from, unsigned& to) const {
-    if (item >= items) return false;
-    const unsigned t = item / 3u, c = item - 3u * t;
-    const unsigned i0 = tri[3 * (size_t)t], i1 = tri[3 * (size_t)t + 1], i2 = tri[3 * (size_t)t + 2];
-    from = c == 0 ? i0 : c == 1 ? i1 : i2;
-    to = c == 0 ? i1 : c == 1 ? i2 : i0;
-    return i0 < n_v && i1 < n_v && i2 < n_v && i0 != i1 && i1 != i2 && i2 != i0;
-  }
-};
-
-// sort_rounds' key of round r (0: the larger end, 1: the smaller) for a corner; the sentinel n_v for a corner that names no edge
-struct CornerKey {
-  CornerView view;
-  __device__ __forceinline__ unsigned long long size() const { return view.items; }
-  __device__ __forceinline__ unsigned operator()(unsigned item, int r) const {
-    unsigned a, b;
-    const bool ok = view.ends(item, a, b);
-    return ok ? (r ? min(a, b) : max(a, b)) : view.n_v;
-  }
-};
-
-// after the two rounds: the larger end of every sorted corner
-__global__ __launch_bounds__(VT) void k_refine_ends(CornerView view, const unsigned* __restrict__ order, unsigned* __restrict__ his) {
-  for (size_t m = (size_t)blockIdx.x * VT + threadIdx.x; m < view.items; m += (size_t)gridDim.x * VT) {
-    unsigned a, b;
-    const bool ok = view.ends(order[m], a, b);
-    his[m] = ok ? max(a, b) : view.n_v;
-  }
-}
-
-// ---- the exclusive scan of one value per item, in the tile order of the flag compaction (voxel_device.h) -------------------------------
-// A source says how many items it has (size), the value of an item (value) and what an item does with the sum before it (write).
-template <class S>
-__global__ __launch_bounds__(VT) void k_refine_sum_count(S s, unsigned* __restrict__ bc) {
-  __shared__ unsigned lds[VT / 64];
-  const unsigned n = s.size();
-  const size_t t0 = (size_t)blockIdx.x * RUN_TILE;
-  unsigned c = 0;
-  for (int j = 0; j < RUN_IPT; ++j) {
-    const size_t i = t0 + j * VT + threadIdx.x;
-    if (i < n) c += s.value((unsigned)i);
-  }
-  unsigned tot;
-  block_scan_incl(c, lds, tot);
-  if (threadIdx.x == 0) bc[blockIdx.x] = tot;
-}
-
-template <class S>
-__global__ __launch_bounds__(VT) void k_refine_sum_write(S s, const unsigned* __restrict__ bc) {
-  __shared__ unsigned lds[VT / 64];
-  const unsigned n = s.size();
-  const size_t t0 = (size_t)blockIdx.x * RUN_TILE;
-  if (t0 >= n) return;                 // uniform over the block
-  unsigned carry = bc[blockIdx.x];
-  for (int j = 0; j < RUN_IPT; ++j) {
-    const size_t i = t0 + j * VT + threadIdx.x;
-    const unsigned v = i < n ? s.value((unsigned)i) : 0u;
-    unsigned tot;
-    const unsigned incl = block_scan_incl(v, lds, tot);
-    if (i < n) s.write((unsigned)i, carry + incl - v, v);
-    carry += tot;
-  }
-}
-
 // sorted corner m: 1 for the first of its edge's run.  The sum before it, plus its own value, less one is its edge: the edges are ranked
 // in the order of the sort.  Every member tells its corner the edge; the head writes the ends; a member of a selected triangle the flag
 struct EdgeSrc {
@@ -138,23 +68,6 @@ struct EdgeSrc {
 };
 
 // ---- the marks --------------------------------------------------------------------------------------------------------------------------
-struct P3 {
-  double p[3];
-  bool finite;
-};
-
-// the position of vertex id in double; an index that names no vertex reads nothing and is not finite
-__device__ __forceinline__ P3 p3_load(const float* __restrict__ pos, unsigned id, unsigned n_v) {
-  P3 q = {{NAN, NAN, NAN}, false};
-  if (id < n_v) {
-    const size_t o = 3 * (size_t)id;
-    const float x = pos[o], y = pos[o + 1], z = pos[o + 2];
-    q.p[0] = (double)x; q.p[1] = (double)y; q.p[2] = (double)z;
-    q.finite = finite3(x, y, z);
-  }
-  return q;
-}
-
 // step 3's q between two positions in double
 __device__ __forceinline__ double q_of(const double a[3], const double b[3]) {
   RGBID_FP_STRICT
@@ -365,17 +278,6 @@ struct rgbid_refine {
 
 namespace {
 
-unsigned blocks_of(unsigned long long items) { return (unsigned)((items + VT - 1) / VT); }
-
-// the exclusive scan of a value source of `items` > 0 items: tile sums, the workspace's one-block scan of them, the write
-template <class S>
-void value_scan(hipStream_t s, SortWorkspace& w, const S& src, unsigned items, int slot) {
-  const unsigned tiles = (items + RUN_TILE - 1) / RUN_TILE;
-  hipLaunchKernelGGL(k_refine_sum_count<S>, dim3(tiles), dim3(VT), 0, s, src, w.bc);
-  hipLaunchKernelGGL(k_vox_scan1, dim3(1), dim3(VT), 0, s, w.bc, tiles, w.slots, slot, (unsigned*)nullptr, 0u);
-  hipLaunchKernelGGL(k_refine_sum_write<S>, dim3(tiles), dim3(VT), 0, s, src, w.bc);
-}
-
 // steps 2 and 3 behind the index check, n_t > 0
 int plan_stage(rgbid_refine* h, const unsigned* tri, const float* pos, const unsigned char* selection, double l2) {
   hipStream_t s = h->ctx->stream;
@@ -385,11 +287,11 @@ int plan_stage(rgbid_refine* h, const unsigned* tri, const float* pos, const uns
   const unsigned items = (unsigned)view.items;
   const int p = w.sort_rounds(s, CornerKey{view}, n_v, items, {0, 1});   // by the larger end, then by the smaller
   unsigned* his = w.keys_as<unsigned>(p ^ 1);
-  hipLaunchKernelGGL(k_refine_ends, dim3(grid_of(blocks_of(items))), dim3(VT), 0, s, view, w.idx[p], his);
+  hipLaunchKernelGGL(k_mesh_corner_ends<false>, dim3(grid_of(blocks_of(items))), dim3(VT), 0, s, view, w.idx[p], his, (unsigned*)nullptr);
   unsigned* corner_edge = w.idx[p ^ 1];
   RGBID_HIP(hipMemsetAsync(h->flags, 0, (size_t)items, s));
   const EdgeSrc edges{w.keys_as<unsigned>(p), his, w.idx[p], selection, items, n_v, corner_edge, h->edge_lo, h->edge_hi, h->flags};
-  value_scan(s, w, edges, items, SLOT_RUNS);
+  w.value_scan(s, edges, items, SLOT_RUNS);
   hipLaunchKernelGGL(k_refine_mark, dim3(grid_of(blocks_of(items))), dim3(VT), 0, s, pos, h->edge_lo, h->edge_hi, w.slots + SLOT_RUNS, items, n_v, l2,
                      h->flags, h->edge_rank, w.slots + SLOT_ELIGIBLE);
   // the sorted keys are read no more: the second halves of the key buffers take the marked edges' ends
@@ -401,16 +303,11 @@ int plan_stage(rgbid_refine* h, const unsigned* tri, const float* pos, const uns
   const Pattern pt{tri, corner_edge, h->edge_rank, n_t, n_v, items};
   hipLaunchKernelGGL(k_refine_k, dim3(grid_of(blocks_of(n_t))), dim3(VT), 0, s, pt, h->kk, w.slots);
   const BaseSrc base{h->kk, n_t, h->base};
-  value_scan(s, w, base, n_t, SLOT_NEW);
+  w.value_scan(s, base, n_t, SLOT_NEW);
   h->corner_edge = corner_edge;
   h->mlo = mlo;
   h->mhi = mhi;
   return RGBID_OK;
-}
-
-bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return a && b && a_bytes && b_bytes && x < y + b_bytes && y < x + a_bytes;
 }
 
 }  // namespace

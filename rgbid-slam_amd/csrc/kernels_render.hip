@@ -14,6 +14,7 @@
 #include "../../include/rgbid_render.h"
 #include "common.h"
 #include "hip_host.h"
+#include "view_device.h"    // rot_row
 
 #include <cmath>
 #include <new>
@@ -41,11 +42,6 @@ struct RenderCam {
 __global__ __launch_bounds__(RT) void k_render_clear(uint4* __restrict__ keys, size_t n16) {
   const size_t i = (size_t)blockIdx.x * RT + threadIdx.x;
   if (i < n16) keys[i] = make_uint4(~0u, ~0u, ~0u, ~0u);
-}
-
-__device__ __forceinline__ float rot_row(const float* __restrict__ m, float x, float y, float z) {
-  RGBID_FP_STRICT
-  return (m[0] * x + m[1] * y) + m[2] * z;
 }
 
 // Only x, y, z decide here and they lie in the record's first 16 bytes; the second half of the record is the resolve's business.  The lines
@@ -135,11 +131,6 @@ __global__ __launch_bounds__(RT) void k_render_resolve(const unsigned long long*
     float* p = normal + 3 * (at - pix) + pix;               // [view][3][rows][cols]
     p[0] = nx; p[npix] = ny; p[2 * npix] = nz;
   }
-}
-
-bool finite_all(const double* p, int n) {
-  for (int i = 0; i < n; ++i) if (!std::isfinite(p[i])) return false;
-  return true;
 }
 
 }  // namespace

@@ -10,17 +10,18 @@
 //         k_smooth_ends      the u of the sorted items beside their v
 //         flag compaction    over the heads (v, u)[m] != (v, u)[m - 1]: heads[rank] = m, heads[P] = M
 //         k_smooth_rows      neighbours[r] = u, incidences[r] = heads[r + 1] - heads[r]
-//         k_smooth_offsets   offsets[w] = the rows of the vertices below w: a bounded binary search per vertex
+//         k_mesh_offsets<true>  mesh_device.h: offsets[w] = the rows of the vertices below w: a bounded binary search per vertex
 //         k_smooth_rowstats  one thread per vertex over its own row: the boundary byte, the counts (integer atomics, one per wave)
-//         corner table       k_smooth_corner_keys, one stable sort of (vertex, corner) by bitlen(n_v) bits, k_smooth_offsets, a copy
+//         corner table       mesh_device.h's k_mesh_corner_keys, one stable sort of (vertex, corner) by bitlen(n_v) bits, k_mesh_offsets<false>,
+//                            a copy
 //   run   k_smooth_pass      one thread per vertex: gathers its row's positions, sums in order in double
 //   normals k_smooth_normals one thread per vertex: gathers its corners' triangles, sums the area vectors in order in double
 // No float atomics, no wait on another thread, every loop has its bound when it starts.
 #include "../../include/rgbid_smooth.h"
 #include "common.h"
 #include "hip_host.h"
-#include "mesh_device.h"    // the index check, the argument test, the create; voxel_device.h's sort_rounds, flag compaction and ordered
-                            // gather; the sort workspace
+#include "mesh_device.h"    // the index check, the corner table, tri_load, area_vector, the argument test, the create; voxel_device.h's
+                            // sort_rounds, flag compaction and ordered gather; the sort workspace
 
 #include <cmath>
 #include <cstring>
@@ -91,22 +92,6 @@ __global__ __launch_bounds__(VT) void k_smooth_rows(const unsigned* __restrict__
   }
 }
 
-// offsets[w], w = 0 .. n_v: how many of the ascending keys are below w.  The key of entry r is keys[heads[r]], keys[r] without heads;
-// the entries are *n_slot, `count` without a slot.  32 halvings at most
-__global__ __launch_bounds__(VT) void k_smooth_offsets(const unsigned* __restrict__ keys, const unsigned* __restrict__ heads, const unsigned* __restrict__ n_slot,
-                                                       unsigned count, unsigned n_v, unsigned* __restrict__ offsets) {
-  const unsigned n = n_slot ? *n_slot : count;
-  for (size_t w = (size_t)blockIdx.x * VT + threadIdx.x; w <= n_v; w += (size_t)gridDim.x * VT) {
-    unsigned lo = 0, hi = n;
-    for (int it = 0; it < 32 && lo < hi; ++it) {
-      const unsigned mid = lo + ((hi - lo) >> 1);
-      const unsigned k = keys[heads ? heads[mid] : mid];
-      if (k < w) lo = mid + 1; else hi = mid;
-    }
-    offsets[w] = lo;
-  }
-}
-
 // one thread per vertex over its own row: the boundary byte and what the row adds to the counts
 __global__ __launch_bounds__(VT) void k_smooth_rowstats(const unsigned* __restrict__ offsets, const unsigned* __restrict__ inc, unsigned n_v,
                                                         unsigned char* __restrict__ boundary, unsigned* __restrict__ slots) {
@@ -136,17 +121,6 @@ __global__ __launch_bounds__(VT) void k_smooth_rowstats(const unsigned* __restri
     if (nonmanifold) atomicAdd(slots + SLOT_NONMANIFOLD, nonmanifold);
     if (deg0) atomicAdd(slots + SLOT_DEG0, deg0);
     if (deg) atomicMax(slots + SLOT_MAXDEG, deg);
-  }
-}
-
-// ---- corner table -----------------------------------------------------------------------------------------------------------------
-// one round, so not sort_rounds': k_vox_round_keys' test of the order and its round argument would make this stream half as long again
-__global__ __launch_bounds__(VT) void k_smooth_corner_keys(const unsigned* __restrict__ tri, unsigned long long corners, unsigned n_v,
-                                                           unsigned* __restrict__ keys, unsigned* __restrict__ idx) {
-  for (size_t i = (size_t)blockIdx.x * VT + threadIdx.x; i < corners; i += (size_t)gridDim.x * VT) {
-    const unsigned v = tri[i];
-    keys[i] = v < n_v ? v : n_v;
-    idx[i] = (unsigned)i;
   }
 }
 
@@ -207,39 +181,13 @@ __global__ __launch_bounds__(VT) void k_smooth_pass(const float* __restrict__ in
 }
 
 // ---- normals ------------------------------------------------------------------------------------------------------------------------
-struct TriPos {
-  float p[3][3];
-  bool ok;
-};
-
-// the three positions of the triangle of corner c; a corner, a triangle or an index that names nothing reads nothing
-__device__ __forceinline__ TriPos tri_load(const float* __restrict__ pos, const unsigned* __restrict__ tri, unsigned c, unsigned n_t, unsigned n_v) {
-  TriPos q;
-  q.ok = false;
-  for (int k = 0; k < 3; ++k) for (int a = 0; a < 3; ++a) q.p[k][a] = 0.f;
-  const unsigned t = c / 3u;
-  if (t >= n_t) return q;
-  const unsigned i[3] = {tri[3 * (size_t)t], tri[3 * (size_t)t + 1], tri[3 * (size_t)t + 2]};
-  if (!(i[0] < n_v && i[1] < n_v && i[2] < n_v)) return q;
-  for (int k = 0; k < 3; ++k)
-    for (int a = 0; a < 3; ++a) q.p[k][a] = pos[3 * (size_t)i[k] + a];
-  q.ok = finite3(q.p[0][0], q.p[0][1], q.p[0][2]) && finite3(q.p[1][0], q.p[1][1], q.p[1][2]) && finite3(q.p[2][0], q.p[2][1], q.p[2][2]);
-  return q;
-}
-
-// one measurable triangle's area vector, in order: every component two products and one difference
+// one measurable triangle's area vector, in order
 __device__ __forceinline__ void tri_add(double s[3], const TriPos& q) {
   RGBID_FP_STRICT
   if (!q.ok) return;
-  double e1[3], e2[3];
-  for (int a = 0; a < 3; ++a) {
-    e1[a] = (double)q.p[1][a] - (double)q.p[0][a];
-    e2[a] = (double)q.p[2][a] - (double)q.p[0][a];
-  }
-  const double n0 = (e1[1] * e2[2]) - (e1[2] * e2[1]);
-  const double n1 = (e1[2] * e2[0]) - (e1[0] * e2[2]);
-  const double n2 = (e1[0] * e2[1]) - (e1[1] * e2[0]);
-  s[0] += n0; s[1] += n1; s[2] += n2;
+  double n[3];
+  area_vector(q, n);
+  s[0] += n[0]; s[1] += n[1]; s[2] += n[2];
 }
 
 __global__ __launch_bounds__(VT) void k_smooth_normals(const float* __restrict__ pos, const unsigned* __restrict__ tri, unsigned n_t, unsigned n_v,
@@ -249,7 +197,7 @@ __global__ __launch_bounds__(VT) void k_smooth_normals(const float* __restrict__
   const size_t v = (size_t)blockIdx.x * VT + threadIdx.x;
   if (v >= n_v) return;
   double s[3] = {0, 0, 0};
-  gather_in_order(corners, corner_offsets[v], corner_offsets[v + 1], s, [&](unsigned c) { return tri_load(pos, tri, c, n_t, n_v); }, tri_add);
+  gather_in_order(corners, corner_offsets[v], corner_offsets[v + 1], s, [&](unsigned c) { return tri_load(pos, tri, c / 3u, n_t, n_v); }, tri_add);
   float n[3];
   unit_of(s, n);
   for (int a = 0; a < 3; ++a) out[3 * v + a] = n[a];
@@ -304,7 +252,7 @@ int adjacency_stage(rgbid_smooth* h, unsigned n_pairs) {
                        h->inc);
   }
   // without a pair the slot holds 0 and nothing is read through the null tables
-  hipLaunchKernelGGL(k_smooth_offsets, dim3(grid_of(((unsigned long long)n_v + 1 + VT - 1) / VT)), dim3(VT), 0, s, vs, heads, w.slots + SLOT_RUNS, 0u, n_v,
+  hipLaunchKernelGGL(k_mesh_offsets<true>, dim3(grid_of(((unsigned long long)n_v + 1 + VT - 1) / VT)), dim3(VT), 0, s, vs, heads, w.slots + SLOT_RUNS, 0u, n_v,
                      h->offsets);
   hipLaunchKernelGGL(k_smooth_rowstats, dim3((n_v + VT - 1) / VT), dim3(VT), 0, s, h->offsets, h->inc, n_v, h->boundary, w.slots);
   RGBID_HIP(hipGetLastError());
@@ -319,12 +267,13 @@ int corner_stage(rgbid_smooth* h) {
   const unsigned long long corners = 3ull * h->n_t;
   const unsigned* keys = nullptr;
   if (corners) {
-    hipLaunchKernelGGL(k_smooth_corner_keys, dim3(grid_of((corners + VT - 1) / VT)), dim3(VT), 0, s, h->tri, corners, n_v, w.keys_as<unsigned>(0), w.idx[0]);
+    // <unsigned> is no choice: the kernel is a template only so that a file that does not launch it does not compile it
+    hipLaunchKernelGGL(k_mesh_corner_keys<unsigned>, dim3(grid_of((corners + VT - 1) / VT)), dim3(VT), 0, s, h->tri, corners, n_v, w.keys_as<unsigned>(0), w.idx[0]);
     const int p = w.sort_bits<unsigned>(s, (unsigned)corners, bitlen(n_v), 0);
     keys = w.keys_as<unsigned>(p);
     RGBID_HIP(hipMemcpyAsync(h->corners, w.idx[p], sizeof(unsigned) * (size_t)corners, hipMemcpyDeviceToDevice, s));
   }
-  hipLaunchKernelGGL(k_smooth_offsets, dim3(grid_of(((unsigned long long)n_v + 1 + VT - 1) / VT)), dim3(VT), 0, s, keys, (const unsigned*)nullptr,
+  hipLaunchKernelGGL(k_mesh_offsets<false>, dim3(grid_of(((unsigned long long)n_v + 1 + VT - 1) / VT)), dim3(VT), 0, s, keys, (const unsigned*)nullptr,
                      (const unsigned*)nullptr, (unsigned)corners, n_v, h->corner_offsets);
   RGBID_HIP(hipGetLastError());
   return RGBID_OK;

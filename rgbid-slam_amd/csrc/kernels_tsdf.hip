@@ -35,6 +35,7 @@
 #include "../../include/rgbid_tsdf.h"
 #include "common.h"
 #include "hip_host.h"
+#include "view_device.h"    // rot_row
 #include "voxel_device.h"   // flag compaction, the one-block scan, grid_of
 
 #include <cmath>
@@ -78,11 +79,6 @@ struct TsdfState {                // the contract's planes are the storage
 // their last two entries swapped (tests/test_cpu_tsdf.py re-derives the bits from the orientation rule)
 __constant__ const unsigned char TET_CORNER[6][4] = {{0, 1, 3, 7}, {0, 1, 5, 7}, {0, 2, 3, 7}, {0, 2, 6, 7}, {0, 4, 5, 7}, {0, 4, 6, 7}};
 __constant__ const unsigned short TET_SWAP[6] = {0x4d24, 0x32da, 0x32da, 0x4d24, 0x4d24, 0x32da};
-
-__device__ __forceinline__ float rot_row(const float* __restrict__ m, float x, float y, float z) {
-  RGBID_FP_STRICT
-  return (m[0] * x + m[1] * y) + m[2] * z;
-}
 
 __device__ __forceinline__ float centre(float o, unsigned i, float voxel) {
   RGBID_FP_STRICT
@@ -811,11 +807,6 @@ __global__ __launch_bounds__(VT) void k_tsdf_tri_write(TsdfGrid g, TsdfState st,
     }
     carry += tot;
   }
-}
-
-bool finite_all(const double* p, int n) {
-  for (int i = 0; i < n; ++i) if (!std::isfinite(p[i])) return false;
-  return true;
 }
 
 // the largest float32 that is not above m: a floorf result is <= m exactly iff it is <= this

@@ -1,7 +1,7 @@
 // voxel_device.h -- what the map filters over rgbid_cloud_point records share (kernels_voxel.hip, kernels_outlier.hip, kernels_consist.hip),
 // and the mesh operators with them (mesh_device.h).  Device half: the box of the finite points of a point source (32-byte records or
 // 12-byte vertices), the float32 grid and its cell keys, the stable LSD radix sort of (key, index) pairs, the keys of a sort by a tuple,
-// the ordered sum over gathered members and the stable flag compaction (the wave and block primitives they stand on are
+// the ordered sum over gathered members, the stable flag compaction and the exclusive value scan (the wave and block primitives they stand on are
 // wave_device.h's).  Host half: SortWorkspace, the buffers of one handle and the launches over them, and the argument checks every
 // plan / emit of a filter makes.
 // Everything has internal linkage: each including file compiles its own copy of the kernels it launches.
@@ -346,6 +346,40 @@ __global__ __launch_bounds__(VT) void k_vox_flag_write(S s, const unsigned* __re
   }
 }
 
+// ---- the exclusive scan of one value per item, in the tile order of the flag compaction ------------------------------------------------
+// A source says how many items it has (size), the value of an item (value) and what an item does with the sum before it (write).
+template <class S>
+__global__ __launch_bounds__(VT) void k_vox_sum_count(S s, unsigned* __restrict__ bc) {
+  __shared__ unsigned lds[VT / 64];
+  const unsigned n = s.size();
+  const size_t t0 = (size_t)blockIdx.x * RUN_TILE;
+  unsigned c = 0;
+  for (int j = 0; j < RUN_IPT; ++j) {
+    const size_t i = t0 + j * VT + threadIdx.x;
+    if (i < n) c += s.value((unsigned)i);
+  }
+  unsigned tot;
+  block_scan_incl(c, lds, tot);
+  if (threadIdx.x == 0) bc[blockIdx.x] = tot;
+}
+
+template <class S>
+__global__ __launch_bounds__(VT) void k_vox_sum_write(S s, const unsigned* __restrict__ bc) {
+  __shared__ unsigned lds[VT / 64];
+  const unsigned n = s.size();
+  const size_t t0 = (size_t)blockIdx.x * RUN_TILE;
+  if (t0 >= n) return;                 // uniform over the block
+  unsigned carry = bc[blockIdx.x];
+  for (int j = 0; j < RUN_IPT; ++j) {
+    const size_t i = t0 + j * VT + threadIdx.x;
+    const unsigned v = i < n ? s.value((unsigned)i) : 0u;
+    unsigned tot;
+    const unsigned incl = block_scan_incl(v, lds, tot);
+    if (i < n) s.write((unsigned)i, carry + incl - v, v);
+    carry += tot;
+  }
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------------------
 unsigned grid_of(unsigned long long items) { return items < VOX_MAX_GRID ? (unsigned)(items ? items : 1) : VOX_MAX_GRID; }
 
@@ -520,6 +554,15 @@ struct SortWorkspace {
   template <class S>
   void write(hipStream_t s, const S& src, unsigned items) {
     hipLaunchKernelGGL(k_vox_flag_write<S>, dim3((items + RUN_TILE - 1) / RUN_TILE), dim3(VT), 0, s, src, bc);
+  }
+  // The exclusive scan of a value source of at most `items` > 0 items: tile sums, the one-block scan of them (the total in slots[slot]),
+  // every item's write with the sum before it.  It uses bc as a count_scan does
+  template <class S>
+  void value_scan(hipStream_t s, const S& src, unsigned items, int slot) {
+    const unsigned tiles = (items + RUN_TILE - 1) / RUN_TILE;
+    hipLaunchKernelGGL(k_vox_sum_count<S>, dim3(tiles), dim3(VT), 0, s, src, bc);
+    hipLaunchKernelGGL(k_vox_scan1, dim3(1), dim3(VT), 0, s, bc, tiles, slots, slot, (unsigned*)nullptr, 0u);
+    hipLaunchKernelGGL(k_vox_sum_write<S>, dim3(tiles), dim3(VT), 0, s, src, bc);
   }
 };
 
