@@ -62,7 +62,8 @@ __device__ __forceinline__ bool measured_ok(float m, float Z, float tol) {
 // steps 3 and 4 of one pair -> its class; a TAKEN pair hands its sample to taken(const ViewSample&) before the return.  fin: the point is
 // finite; facing: its normal has a finite, non-zero squared length.  kernels_colouralign.hip's pair.  k_recolour_add and k_texture_add
 // keep the same sequence written out as nested ifs around rot_row, surface_ok, measured_ok and view_accumulate: through this function
-// they lost a wave per SIMD or left the parent's time, so a change to the rule is made here and in those two
+// they lost a wave per SIMD or left the parent's time, so a change to the rule is made here and in those two;
+// tests/test_gpu_view_rule.py holds the three to the same boundary table and to each other
 template <class F>
 __device__ __forceinline__ int view_sample(const ViewEntry& view, const ViewCam& cam, float x, float y, float z, bool fin, bool facing, float n0,
                                            float n1, float n2, F&& taken) {
